@@ -16,8 +16,17 @@ Workloads (BASELINE.json configs): `config2` (default) 1024 x 3-min tracks per G
 `mixed` (config 4) lengths uniform on whole seconds in [30, 600]; `bpm-only` (config 5) 4096
 tracks per GPU with an escalation-heavy BPM mix, stages a1-a19 only.
 
-Also reported: the dominant STFT kernel's HBM roofline (algorithmic bytes / HIP-event kernel time
-vs 8 TB/s) and the CPU restatement (oracle) timed on this box's host cores on a bounded sample.
+A plain run (`bench.py --gpus 1 --steps N --warmup W`) does only what the headline figure needs:
+it sets up, warms up, times the N steps and prints the result line, with the dominant STFT kernel's
+HBM roofline as the pipeline's own HIP events of those steps give it (algorithmic bytes / kernel
+time vs 8 TB/s).  `--dump-outputs DIR` also writes what the last timed step returned, as
+DIR/<name>.npy per numeric result field (dump_outputs below lists them and what it leaves out), so
+two builds can be compared output for output: the inputs are seeded and the same from run to run.
+
+`--full` adds everything that takes runs of its own: the shader clock sampled during the timed
+steps, the STFT kernel launched alone (`roofline.isolated`), the CPU restatement (oracle) timed on
+the host's cores on a bounded sample with the parity of that sample, the reference's 30-s sine
+workload, and for bpm-only the comparison with the full pipeline.
 """
 import argparse
 import concurrent.futures as cf
@@ -77,6 +86,12 @@ class DryEngine:
     class _Res:
         def __init__(self, n):
             self.status = [0] * n
+
+        def field(self, name, failed=0):
+            return [0] * len(self.status)
+
+        def values(self, name, count):
+            return [np.zeros(0, np.float32) for _ in self.status]
 
         def free(self):
             pass
@@ -180,12 +195,17 @@ def main():
     ap.add_argument("--workload", choices=sorted(WORKLOADS), default="config2")
     ap.add_argument("--tracks", type=int, default=0, help="tracks per GPU per step (0 = the workload's)")
     ap.add_argument("--seconds", type=float, default=180.0, help="track length (config2 / bpm-only)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: clock sampling, the isolated STFT "
+                         "probe, the CPU baseline with its parity sample, the 30-s sine, the bpm-only check")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's results as DIR/<name>.npy")
     ap.add_argument("--cpu-threads", type=int, default=0,
                     help="0 = every host core this process may use (its affinity set, capped by the box's CPU share)")
     ap.add_argument("--cpu-tracks", type=int, default=0, help="0 = 2 per thread")
     ap.add_argument("--cpu-1thread-tracks", type=int, default=2, help="tracks timed alone on one thread")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-probe", action="store_true", help="skip the isolated STFT probe (A/B runs)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline leg")
+    ap.add_argument("--no-probe", action="store_true", help="with --full: skip the isolated STFT probe (A/B runs)")
     ap.add_argument("--bpm-mode", type=int, default=-1, help="synthetic BPM mix (-1 = the workload's; 1 = config 5)")
     ap.add_argument("--dry-run", action="store_true", help="host-logic rehearsal without a GPU (tests)")
     ap.add_argument("--share-device", action="store_true",
@@ -235,7 +255,7 @@ def main():
         eng.analyze(buf, offs, lens, sr, stage_mask).free()
     barrier()
     eng.synchronize()
-    clock = ClockSampler(eng.dev) if (rank == 0 and not args.dry_run) else None
+    clock = ClockSampler(eng.dev) if (args.full and rank == 0 and not args.dry_run) else None
     if clock:
         clock.__enter__()
     t0 = time.perf_counter()
@@ -269,6 +289,8 @@ def main():
     if tdist is not None:
         shards = [None] * world
         tdist.all_gather_object(shards, shard)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, res, rank, world)
     n_err = sum(1 for st in res.status if st != 0)
     total_tracks = n * world * args.steps
     value = total_tracks / dt
@@ -307,7 +329,7 @@ def main():
         if (stft["ms2"] + stft["ms8"]) > 0 else None,
     }
 
-    if not args.dry_run and rank == 0 and not args.no_probe:
+    if args.full and not args.dry_run and rank == 0 and not args.no_probe:
         # the same kernel launched alone (nothing else on the chip): the kernel's own bandwidth, as
         # opposed to `achieved` above, which is measured inside the two-stream pipeline where the
         # tempo path shares the CUs (tools/stft_probe.py)
@@ -333,12 +355,12 @@ def main():
         # fraction of this rank's tracks whose base estimate escalated to multi-resolution
         # (src/lib.rs:410-459; BASELINE.md asks for the escalation rate beside the throughput)
         extras["escalation_rate"] = round(res.count("tempogram_multi_res_triggered") / max(n, 1), 4)
-        if stage_mask == 1:
+        if args.full and stage_mask == 1:
             extras["bpm_only_vs_full"] = bpm_only_check(eng, buf, offs, lens, sr, res, min(n, 64))
     if args.workload == "mixed":
         extras["mean_track_seconds"] = round(float(lens.mean()) / sr, 2)
         extras["audio_seconds_per_s"] = round(float(lens.sum()) / sr * world * args.steps / dt, 1)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and not args.dry_run:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and not args.dry_run:
         cpu, parity = cpu_baseline(buf, offs, lens, res, n, sr, args)
         extras["sine_30s"] = sine_30s(sr)
 
@@ -358,6 +380,7 @@ def main():
             "n_gpus": world,
             "steps": args.steps,
             "warmup": args.warmup,
+            "full": args.full,
             "ms_per_step": round(dt / args.steps * 1000.0, 3),
             "higher_is_better": True,
             "scaling": "weak",
@@ -393,6 +416,49 @@ def main():
         print(json.dumps(out), flush=True)
     if tdist is not None:
         tdist.destroy_process_group()
+
+
+# per-track sdsp_result fields written by --dump-outputs; the two bit masks as float64 (a uint32
+# mask is exact in float32 only below 2^24)
+DUMP_SCALARS = ("status", "bpm", "bpm_confidence", "key_mode", "key_tonic", "key_confidence", "key_clarity",
+                "grid_stability", "duration_seconds", "sample_rate", "onset_method_consensus", "methods_used", "flags",
+                "n_warnings", "tempogram_multi_res_triggered", "tempogram_multi_res_used",
+                "tempogram_percussive_triggered", "tempogram_percussive_used")
+DUMP_F64 = ("methods_used", "flags")
+DUMP_LISTS = (("beats", "n_beats"), ("downbeats", "n_downbeats"), ("bars", "n_bars"))
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(path, res, rank, world):
+    """--dump-outputs: the results of the last timed step as the caller received them (sdsp_result,
+    include/stratum_hip.h), written as <path>/<name>.npy (rank R of a multi-GPU job:
+    <path>/rankR_<name>.npy), float32 but for the two bit masks (DUMP_F64).  The DUMP_SCALARS fields
+    are arrays over the tracks (0 for a failed track; `status` says which failed); beats / downbeats /
+    bars are the tracks' lists end to end, n_beats / n_downbeats / n_bars their lengths.  Left out:
+    processing_time_ms (wall time, differs from run to run), the strings (algorithm_version, the
+    warning texts, whose number n_warnings is written, and error_message, whose status is) and the
+    tempogram candidates (the benchmark's default config emits none).  Should the arrays exceed
+    DUMP_MAX_BYTES (64 MB), a fixed seeded sample of the tracks is written; `tracks` holds the
+    indices of the tracks written."""
+    n = len(res.status)
+    lists = {name: res.values(name, cnt) for name, cnt in DUMP_LISTS}
+    scalar_bytes = 4 + sum(8 if name in DUMP_F64 else 4 for name in DUMP_SCALARS) + 4 * len(DUMP_LISTS)
+    per_track = np.array([scalar_bytes + sum(v[i].nbytes for v in lists.values()) for i in range(n)], np.int64)
+    keep = np.arange(n)
+    if per_track.sum() > DUMP_MAX_BYTES:
+        order = np.random.default_rng(0x0D0F).permutation(n)
+        keep = np.sort(order[: int(np.searchsorted(np.cumsum(per_track[order]), DUMP_MAX_BYTES, side="right"))])
+    arrays = {"tracks": keep.astype(np.float32)}
+    for name in DUMP_SCALARS:
+        vals = np.asarray(res.status if name == "status" else res.field(name), dtype=np.float64)
+        arrays[name] = vals[keep].astype(np.float64 if name in DUMP_F64 else np.float32)
+    for name, cnt in DUMP_LISTS:
+        arrays[cnt] = np.array([lists[name][i].size for i in keep], np.float32)
+        arrays[name] = np.concatenate([lists[name][i] for i in keep] + [np.zeros(0, np.float32)])
+    os.makedirs(path, exist_ok=True)
+    prefix = f"rank{rank}_" if world > 1 else ""
+    for name, a in arrays.items():
+        np.save(os.path.join(path, prefix + name + ".npy"), a)
 
 
 class ClockSampler:

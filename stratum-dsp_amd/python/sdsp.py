@@ -332,6 +332,22 @@ class ResultBatch:
         tempogram_multi_res_triggered), without building result dicts."""
         return sum(1 for i in range(self.n) if self.status[i] == 0 and getattr(self._outs[i], field) == value)
 
+    def field(self, name, failed=0):
+        """The native scalar result field `name` of every track (`failed` for a failed track),
+        without building result dicts."""
+        return [getattr(self._outs[i], name) if self.status[i] == 0 else failed for i in range(self.n)]
+
+    def values(self, name, count):
+        """The native float list `name` of every track, `count` naming its length field (beats /
+        n_beats, downbeats / n_downbeats, bars / n_bars), as float32 arrays (copies; empty for a
+        failed track)."""
+        out = []
+        for i in range(self.n):
+            k = int(getattr(self._outs[i], count)) if self.status[i] == 0 else 0
+            out.append(np.ctypeslib.as_array(getattr(self._outs[i], name), shape=(k,)).copy() if k
+                       else np.zeros(0, np.float32))
+        return out
+
     def free(self):
         if self._outs is not None:
             for i in range(self.n):

@@ -18,5 +18,5 @@ SDSP_SERIAL_STREAMS=1 timeout -k 10 300 rocprofv3 --kernel-trace --stats --outpu
 python3 $R/tools/kstats.py $O/serial/s_kernel_stats.csv 25 > $O/serial_kstats.txt 2>&1; head -25 $O/serial_kstats.txt
 timeout -k 10 300 rocprofv3 --kernel-trace --output-format csv -d $O/conc -o c -- python3 $R/bench.py --tracks 1024 --steps 2 --warmup 1 --no-cpu-baseline > $O/conc.json 2> $O/conc.err || { echo "conc trace failed"; tail -20 $O/conc.err; exit 1; }
 python3 $R/tools/kdur.py $O/conc/c_kernel_trace.csv 3000 > $O/conc_kdur.txt 2>&1; head -24 $O/conc_kdur.txt
-timeout -k 10 300 python3 $R/bench.py --steps 5 --warmup 2 --no-cpu-baseline > $O/bench.json 2> $O/bench.err || { echo "bench failed"; tail -20 $O/bench.err; exit 1; }
+timeout -k 10 300 python3 $R/bench.py --full --steps 5 --warmup 2 --no-cpu-baseline > $O/bench.json 2> $O/bench.err || { echo "bench failed"; tail -20 $O/bench.err; exit 1; }
 python3 -c "import json,sys; d=json.load(open('$O/bench.json')); r=d['roofline']; print('bench', d['value'], 'frac', r['frac'], 'ms/launch', r['ms_per_launch'], 'isolated', r.get('isolated'), d['step_ms'])"

@@ -7,7 +7,7 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}
 O=$R/gpurun_out/prof_$tag
 mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-timeout -k 10 600 python3 $R/bench.py > $O/bench.json 2> $O/bench.err &&
+timeout -k 10 600 python3 $R/bench.py --full > $O/bench.json 2> $O/bench.err &&
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/conc -o $tag -- python3 $R/bench.py --tracks 1024 --steps 2 --warmup 1 --no-cpu-baseline --no-probe > $O/conc.json 2> $O/conc.err &&
 python3 $R/tools/kdur.py $O/conc/${tag}_kernel_trace.csv 3000 > $O/conc_kdur.txt &&
 SDSP_SERIAL_STREAMS=1 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/serial -o $tag -- python3 $R/bench.py --tracks 1024 --steps 2 --warmup 1 --no-cpu-baseline --no-probe > $O/serial.json 2> $O/serial.err &&

@@ -9,7 +9,7 @@ R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 cd "$R"
 mkdir -p gpurun_out
 for r in $(seq "${1:-0}" "${2:-7}"); do
-  timeout -k 10 240 python3 -u bench.py --rank-shard "$r" --steps 3 --warmup 1 --no-probe --cpu-tracks 16 \
+  timeout -k 10 240 python3 -u bench.py --full --rank-shard "$r" --steps 3 --warmup 1 --no-probe --cpu-tracks 16 \
     --cpu-1thread-tracks 1 > "gpurun_out/shard_$r.json" 2> "gpurun_out/shard_$r.err"
   python3 -c "import json,sys; d=json.load(open(sys.argv[1])); print(sys.argv[2], d['value'], d['errors'], d.get('escalation_rate'), d['parity_sample'])" \
     "gpurun_out/shard_$r.json" "$r"
