@@ -347,6 +347,37 @@ int32_t sdsp_decode_audio_file(const char* path, float** samples, uint64_t* n_sa
                                char* err, uint64_t errlen);
 void sdsp_free_samples(float* samples);
 
+/*
+ * Batched FLAC decode on the device (new; the reference decodes on the host): n_files native FLAC
+ * files held in memory ("fLaC", or an ID3v2 tag then "fLaC") are decoded by HIP kernels on `device`
+ * into one device buffer of concatenated mono f32 tracks, bit-identical to sdsp_decode_audio_file
+ * on the same bytes.  Track i is (*d_samples)[offsets[i] .. offsets[i] + lens[i]) at
+ * sample_rates[i]: the arguments of sdsp_analyze_batch_device, per sample rate.  *d_samples is
+ * owned by the caller (sdsp_device_free).  `stream` is a hipStream_t (NULL = the library's own);
+ * the call returns after the buffer is complete.
+ *
+ * status[i] and errs + 256 * i (NUL-terminated) are what sdsp_decode_audio_file returns for the
+ * same bytes in a file; a failed file has lens[i] = 0 and the others still decode.  A file the
+ * device path does not take (not native FLAC, 2 GiB or more, more frame-header candidates than one
+ * per 8 bytes, or past the HBM budget of the call) is decoded by the host decoder, uploaded and
+ * counted in host_fallback_files.  Returns SDSP_OK unless the call itself could not run (no HIP
+ * device: SDSP_ERR_PROCESSING and "Processing error: no HIP device" in every errs slot).
+ */
+typedef struct sdsp_flac_decode_stats {
+    uint64_t files, device_files, host_fallback_files, error_files;
+    uint64_t candidates, frames_accepted, frames_rejected;
+    uint64_t bytes_in, samples_out;
+    double scan_ms, frames_ms, chain_ms, gather_ms, total_ms;
+} sdsp_flac_decode_stats;
+
+int32_t sdsp_decode_flac_batch_device(const uint8_t* const* files, const uint64_t* sizes, uint64_t n_files,
+                                      int32_t device, void* stream,
+                                      float** d_samples, /* out: free with sdsp_device_free */
+                                      uint64_t* offsets, uint64_t* lens, uint32_t* sample_rates,
+                                      int32_t* status, char* errs /* n_files x 256 */);
+/* Counters and phase times (HIP events; total_ms is the call's wall time) of the last call on `device`. */
+int32_t sdsp_last_flac_decode_stats(int32_t device, sdsp_flac_decode_stats* out);
+
 /* Library identification: "stratum-hip <abi> gfx950" */
 const char* sdsp_version(void);
 

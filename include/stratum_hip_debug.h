@@ -100,6 +100,17 @@ int32_t sdsp_debug_frame_rms(const float* host_x, uint64_t n_total, const uint64
 int32_t sdsp_probe_stft(int32_t device, uint64_t nfft, uint64_t hop, uint64_t n_tracks, uint64_t len, int32_t reps,
                         int32_t stride, double* ms_per_launch, double* bytes_per_launch);
 
+/*
+ * The device FLAC decoder's four phases on the CPU, through the same frame-level code
+ * (csrc/flac_core.hpp): frame_header at every byte offset of the frame region, a frame decode of
+ * every candidate into its own scratch slot, the chain over the sorted candidates, the gather of the
+ * accepted slots.  Status, text and samples equal sdsp_decode_audio_file's for the same bytes in a
+ * file; *samples is malloc'ed (sdsp_free_samples).  counts (NULL allowed) receives candidates,
+ * accepted and rejected frames.  No device is touched.
+ */
+int32_t sdsp_debug_flac_decode_phased(const uint8_t* data, uint64_t n, float** samples, uint64_t* n_samples,
+                                      uint32_t* sample_rate, uint64_t counts[3], char* err, uint64_t errlen);
+
 #ifdef __cplusplus
 }
 #endif

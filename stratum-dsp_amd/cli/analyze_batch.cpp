@@ -5,7 +5,16 @@
 // with compute_confidence, printed in input order as text lines or JSONL, with the same
 // summary on stderr.
 //
-//   analyze_batch [--jobs N] [--devices MASK] [--json] <file1> <file2> ...
+//
+// --gpu-decode (opt-in; the output is the same): the workers only read the files' bytes; native FLAC
+// files ("fLaC", or an ID3v2 tag then "fLaC") are grouped by STREAMINFO rate, cut into chunks under
+// a device-memory bound, and each chunk is decoded on a GPU (sdsp_decode_flac_batch_device) and
+// analysed from the device buffer (sdsp_analyze_batch_device): no host PCM exists for them and host
+// memory holds their compressed bytes only.  Chunks go round-robin over the devices of --devices,
+// one host thread per device.  Every other format (Ogg FLAC and Matroska included) takes the path
+// above.
+//
+//   analyze_batch [--jobs N] [--devices MASK] [--json] [--gpu-decode] <file1> <file2> ...
 #include <algorithm>
 #include <atomic>
 #include <chrono>
@@ -21,6 +30,9 @@ namespace {
 struct Item {
     std::string path;
     std::vector<float> samples;
+    std::vector<uint8_t> bytes;  // --gpu-decode: a native FLAC file's compressed bytes
+    uint64_t need = 0;           // --gpu-decode: device bytes the file's decode is expected to take
+    bool flac = false;
     uint32_t sr = 0;
     bool decoded = false;
     std::string error;
@@ -39,11 +51,53 @@ float percentile(std::vector<float> xs, float p) {
     return xs[idx];
 }
 
+// "fLaC", or an ID3v2 tag then "fLaC": the files the decode front-end sends to its native FLAC decoder
+bool native_flac(const std::vector<uint8_t>& b) {
+    auto at = [&](size_t o) { return b.size() >= o + 4 && std::memcmp(b.data() + o, "fLaC", 4) == 0; };
+    if (at(0)) return true;
+    if (b.size() < 10 || std::memcmp(b.data(), "ID3", 3) != 0) return false;
+    return at(10 + (((size_t)(b[6] & 0x7f) << 21) | ((size_t)(b[7] & 0x7f) << 14) | ((size_t)(b[8] & 0x7f) << 7) |
+                    (size_t)(b[9] & 0x7f)));
+}
+
+// STREAMINFO's sample rate and sample count for grouping and sizing (0, 0 when the metadata cannot be
+// walked: the decoder then reports the file's error)
+void flac_streaminfo(const std::vector<uint8_t>& b, uint32_t* rate, uint64_t* total) {
+    *rate = 0;
+    *total = 0;
+    size_t pos = 0;
+    if (b.size() >= 10 && std::memcmp(b.data(), "ID3", 3) == 0)
+        pos = 10 + (((size_t)(b[6] & 0x7f) << 21) | ((size_t)(b[7] & 0x7f) << 14) | ((size_t)(b[8] & 0x7f) << 7) |
+                    (size_t)(b[9] & 0x7f)) + ((b[5] & 0x10) ? 10 : 0);
+    pos += 4;
+    for (bool last = false; !last;) {
+        if (pos + 4 > b.size()) return;
+        last = (b[pos] & 0x80) != 0;
+        const int type = b[pos] & 0x7F;
+        const size_t len = ((size_t)b[pos + 1] << 16) | ((size_t)b[pos + 2] << 8) | b[pos + 3];
+        pos += 4;
+        if (pos + len > b.size()) return;
+        if (type == 0 && len >= 34) {
+            const uint8_t* p = b.data() + pos;
+            *rate = ((uint32_t)p[10] << 12) | ((uint32_t)p[11] << 4) | (p[12] >> 4);
+            *total = ((uint64_t)(p[13] & 0x0F) << 32) | ((uint64_t)p[14] << 24) | ((uint64_t)p[15] << 16) |
+                     ((uint64_t)p[16] << 8) | p[17];
+            return;
+        }
+        pos += len;
+    }
+}
+
+struct Chunk {
+    uint32_t rate;
+    std::vector<size_t> idx;
+};
+
 }  // namespace
 
 int main(int argc, char** argv) {
     Args a(argv + 1, argv + argc);
-    bool json = false;
+    bool json = false, gpu_decode = false;
     uint64_t jobs = 0;
     uint32_t devices = 0;
     std::vector<std::string> paths;
@@ -51,6 +105,8 @@ int main(int argc, char** argv) {
         const std::string& s = a[i];
         if (s == "--json") {
             json = true;
+        } else if (s == "--gpu-decode") {
+            gpu_decode = true;
         } else if (s == "--jobs" || s == "--devices") {
             uint64_t v;
             if (i + 1 >= a.size() || !parse_usize_str(a[i + 1], &v)) {
@@ -64,10 +120,11 @@ int main(int argc, char** argv) {
             i++;
         } else if (s == "--help" || s == "-h") {
             std::fprintf(stderr,
-                         "Usage: analyze_batch [--jobs N] [--devices MASK] [--json] <file1> <file2> ...\n\n"
+                         "Usage: analyze_batch [--jobs N] [--devices MASK] [--json] [--gpu-decode] <file1> <file2> ...\n\n"
                          "--jobs N        Decode workers (default: CPU-1)\n"
                          "--devices MASK  GPU bitmask (default: all visible GPUs)\n"
-                         "--json          Emit one JSON object per line (JSONL)\n");
+                         "--json          Emit one JSON object per line (JSONL)\n"
+                         "--gpu-decode    Decode native FLAC files on the GPUs (same output)\n");
             return 0;
         } else {
             paths.push_back(s);
@@ -94,6 +151,23 @@ int main(int argc, char** argv) {
         for (size_t i; (i = next++) < items.size();) {
             Item& it = items[i];
             it.path = paths[i];
+            if (gpu_decode) {  // read the bytes; only a native FLAC file keeps them
+                if (FILE* fp = std::fopen(it.path.c_str(), "rb")) {
+                    uint8_t chunk[1 << 16];
+                    size_t got;
+                    while ((got = std::fread(chunk, 1, sizeof chunk, fp)) > 0) it.bytes.insert(it.bytes.end(), chunk, chunk + got);
+                    std::fclose(fp);
+                }
+                if (native_flac(it.bytes)) {
+                    uint64_t total = 0;
+                    flac_streaminfo(it.bytes, &it.sr, &total);
+                    if (it.sr == 0) it.sr = 44100;
+                    it.need = 3 * (uint64_t)it.bytes.size() + 8 * (total ? total : 16 * (uint64_t)it.bytes.size());
+                    it.flac = true;
+                    continue;
+                }
+                std::vector<uint8_t>().swap(it.bytes);
+            }
             float* p = nullptr;
             uint64_t n = 0;
             char err[512];
@@ -112,9 +186,97 @@ int main(int argc, char** argv) {
 
     sdsp_config cfg;
     sdsp_config_default(&cfg);
+    auto take = [](Item& it, const sdsp_result& r) {
+        if (r.status != 0) {
+            it.error = std::string("analysis failed: ") + r.error_message;
+            return;
+        }
+        sdsp_confidence c;
+        sdsp_compute_confidence(&r, &c);
+        it.ok = true;
+        it.bpm = r.bpm;
+        it.bpm_conf = c.bpm_confidence;
+        it.key = key_name(r);
+        it.key_conf = c.key_confidence;
+        it.ms = r.processing_time_ms;
+        it.tr[0] = r.tempogram_multi_res_triggered;
+        it.tr[1] = r.tempogram_multi_res_used;
+        it.tr[2] = r.tempogram_percussive_triggered;
+        it.tr[3] = r.tempogram_percussive_used;
+    };
+
+    if (gpu_decode) {
+        // chunks of one STREAMINFO rate, at most 8 GiB of expected device memory and 512 files each
+        // (the decoder checks its own budget again and sends what does not fit to the host decoder)
+        std::map<uint32_t, std::vector<size_t>> flac_by_sr;
+        for (size_t i = 0; i < items.size(); i++)
+            if (items[i].flac) flac_by_sr[items[i].sr].push_back(i);
+        std::vector<Chunk> chunks;
+        for (auto& kv : flac_by_sr) {
+            uint64_t acc = 0;
+            for (size_t i : kv.second) {
+                if (chunks.empty() || chunks.back().rate != kv.first || chunks.back().idx.size() >= 512 ||
+                    (acc && acc + items[i].need > (8ull << 30))) {
+                    chunks.push_back(Chunk{kv.first, {}});
+                    acc = 0;
+                }
+                chunks.back().idx.push_back(i);
+                acc += items[i].need;
+            }
+        }
+        std::vector<int> devs;
+        for (int d = 0; d < 32; d++)
+            if (devices & (1u << d)) devs.push_back(d);
+        auto run_chunk = [&](const Chunk& ch, int dev) {
+            const size_t n = ch.idx.size();
+            std::vector<const uint8_t*> ptrs(n);
+            std::vector<uint64_t> sizes(n), offs(n), lens(n);
+            std::vector<uint32_t> rates(n);
+            std::vector<int32_t> status(n);
+            std::vector<char> errs(256 * n);
+            for (size_t k = 0; k < n; k++) {
+                ptrs[k] = items[ch.idx[k]].bytes.data();
+                sizes[k] = items[ch.idx[k]].bytes.size();
+            }
+            float* d_samples = nullptr;
+            const int32_t rc = sdsp_decode_flac_batch_device(ptrs.data(), sizes.data(), n, dev, nullptr, &d_samples, offs.data(),
+                                                             lens.data(), rates.data(), status.data(), errs.data());
+            std::vector<size_t> okk;
+            std::vector<uint64_t> o2, l2;
+            for (size_t k = 0; k < n; k++) {
+                Item& it = items[ch.idx[k]];
+                std::vector<uint8_t>().swap(it.bytes);
+                if (rc != 0 || status[k] != 0) {
+                    it.error = std::string("decode failed: ") + (errs.data() + 256 * k);
+                    continue;
+                }
+                it.decoded = true;
+                okk.push_back(k);
+                o2.push_back(offs[k]);
+                l2.push_back(lens[k]);
+            }
+            if (!okk.empty()) {
+                std::vector<sdsp_result> outs(okk.size());
+                (void)sdsp_analyze_batch_device(d_samples, o2.data(), l2.data(), okk.size(), ch.rate, &cfg, dev, nullptr,
+                                                outs.data());
+                for (size_t j = 0; j < okk.size(); j++) {
+                    take(items[ch.idx[okk[j]]], outs[j]);
+                    sdsp_result_free(&outs[j]);
+                }
+            }
+            if (d_samples) sdsp_device_free(dev, d_samples);
+        };
+        std::vector<std::thread> dev_threads;
+        for (size_t w = 0; w < devs.size(); w++)
+            dev_threads.emplace_back([&, w]() {
+                for (size_t c = w; c < chunks.size(); c += devs.size()) run_chunk(chunks[c], devs[w]);
+            });
+        for (auto& t : dev_threads) t.join();
+    }
+
     std::map<uint32_t, std::vector<size_t>> by_sr;
     for (size_t i = 0; i < items.size(); i++)
-        if (items[i].decoded) by_sr[items[i].sr].push_back(i);
+        if (items[i].decoded && !items[i].flac) by_sr[items[i].sr].push_back(i);
     for (auto& kv : by_sr) {
         const std::vector<size_t>& idx = kv.second;
         std::vector<const float*> ptrs;
@@ -128,24 +290,7 @@ int main(int argc, char** argv) {
         // library did not analyse carry an error status), so each result is read and freed
         (void)sdsp_analyze_batch(ptrs.data(), lens.data(), idx.size(), kv.first, &cfg, devices, outs.data());
         for (size_t k = 0; k < idx.size(); k++) {
-            Item& it = items[idx[k]];
-            const sdsp_result& r = outs[k];
-            if (r.status != 0) {
-                it.error = std::string("analysis failed: ") + r.error_message;
-            } else {
-                sdsp_confidence c;
-                sdsp_compute_confidence(&r, &c);
-                it.ok = true;
-                it.bpm = r.bpm;
-                it.bpm_conf = c.bpm_confidence;
-                it.key = key_name(r);
-                it.key_conf = c.key_confidence;
-                it.ms = r.processing_time_ms;
-                it.tr[0] = r.tempogram_multi_res_triggered;
-                it.tr[1] = r.tempogram_multi_res_used;
-                it.tr[2] = r.tempogram_percussive_triggered;
-                it.tr[3] = r.tempogram_percussive_used;
-            }
+            take(items[idx[k]], outs[k]);
             sdsp_result_free(&outs[k]);
         }
     }

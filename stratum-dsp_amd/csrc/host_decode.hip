@@ -22,7 +22,8 @@
 
 #include "../../include/stratum_hip.h"
 
-bool sdsp_decode_flac(const std::vector<uint8_t>& f, std::vector<float>* out, uint32_t* sr, std::string* err);
+#include "flac_host.hpp"
+
 bool sdsp_decode_aiff(const std::vector<uint8_t>& f, std::vector<float>* out, uint32_t* sr, std::string* err);
 bool sdsp_decode_caf(const std::vector<uint8_t>& f, std::vector<float>* out, uint32_t* sr, std::string* err);
 bool sdsp_decode_ogg(const std::vector<uint8_t>& f, std::vector<float>* out, uint32_t* sr, std::string* err);
@@ -309,6 +310,56 @@ bool decode_wav(const std::vector<uint8_t>& f, std::vector<float>* out, uint32_t
 }  // namespace
 
 namespace {
+size_t id3_skip(const uint8_t* d, size_t n) {
+    // an ID3v2 tag (10-byte header, syncsafe size) may precede FLAC or MP3 data
+    if (n >= 10 && std::memcmp(d, "ID3", 3) == 0)
+        return 10 + (((size_t)(d[6] & 0x7f) << 21) | ((size_t)(d[7] & 0x7f) << 14) | ((size_t)(d[8] & 0x7f) << 7) |
+                     (size_t)(d[9] & 0x7f));
+    return 0;
+}
+bool magic_at(const uint8_t* d, size_t n, size_t off, const char* m) {
+    const size_t k = std::strlen(m);
+    return n >= off + k && std::memcmp(d + off, m, k) == 0;
+}
+}  // namespace
+
+bool sdsp_is_native_flac(const uint8_t* d, size_t n) {
+    const size_t id3 = id3_skip(d, n);
+    return magic_at(d, n, 0, "fLaC") || (id3 && magic_at(d, n, id3, "fLaC"));
+}
+
+// The front-end on bytes in memory, by magic number; false with the reason in err.
+bool sdsp_decode_audio_bytes(const std::vector<uint8_t>& buf, std::vector<float>* mono_out, uint32_t* sr_out, char* err,
+                             uint64_t errlen) {
+    std::vector<float>& mono = *mono_out;
+    uint32_t& sr = *sr_out;
+    auto magic = [&](size_t off, const char* m) { return magic_at(buf.data(), buf.size(), off, m); };
+    const size_t id3 = id3_skip(buf.data(), buf.size());
+    std::string why;
+    bool ok;
+    if (sdsp_is_native_flac(buf.data(), buf.size())) {
+        ok = sdsp_decode_flac(buf, &mono, &sr, &why);
+    } else if (magic(0, "FORM") && (magic(8, "AIFF") || magic(8, "AIFC"))) {
+        ok = sdsp_decode_aiff(buf, &mono, &sr, &why);
+    } else if (magic(0, "caff")) {
+        ok = sdsp_decode_caf(buf, &mono, &sr, &why);
+    } else if (magic(0, "OggS")) {
+        ok = sdsp_decode_ogg(buf, &mono, &sr, &why);
+    } else if (buf.size() >= 4 && buf[0] == 0x1A && buf[1] == 0x45 && buf[2] == 0xDF && buf[3] == 0xA3) {
+        ok = sdsp_decode_mkv(buf, &mono, &sr, &why);
+    } else if (magic(4, "ftyp")) {
+        ok = sdsp_decode_mp4(buf, &mono, &sr, &why);
+    } else if (id3 || (buf.size() >= 2 && buf[0] == 0xFF && (buf[1] & 0xE0) == 0xE0)) {
+        ok = false, why = (buf.size() >= 2 && !id3 && (buf[1] & 0xF6) == 0xF0) ? "unsupported codec: AAC (ADTS)"
+                                                                             : "unsupported codec: MPEG audio (MP1/MP2/MP3)";
+    } else {
+        return decode_wav(buf, &mono, &sr, err, errlen);
+    }
+    if (!ok) fail(err, errlen, why);
+    return ok;
+}
+
+namespace {
 int32_t decode_audio_file(const char* path, float** samples, uint64_t* n_samples, uint32_t* sample_rate, char* err,
                           uint64_t errlen) {
     if (err && errlen) err[0] = 0;
@@ -327,40 +378,7 @@ int32_t decode_audio_file(const char* path, float** samples, uint64_t* n_samples
     std::fclose(fp);
     std::vector<float> mono;
     uint32_t sr = 0;
-    auto magic = [&](size_t off, const char* m) {
-        const size_t n = std::strlen(m);
-        return buf.size() >= off + n && std::memcmp(buf.data() + off, m, n) == 0;
-    };
-    // an ID3v2 tag (10-byte header, syncsafe size) may precede FLAC or MP3 data
-    size_t id3 = 0;
-    if (magic(0, "ID3") && buf.size() >= 10)
-        id3 = 10 + (((size_t)(buf[6] & 0x7f) << 21) | ((size_t)(buf[7] & 0x7f) << 14) | ((size_t)(buf[8] & 0x7f) << 7) |
-                    (size_t)(buf[9] & 0x7f));
-    std::string why;
-    bool ok;
-    if (magic(0, "fLaC") || (id3 && magic(id3, "fLaC"))) {
-        ok = sdsp_decode_flac(buf, &mono, &sr, &why);
-    } else if (magic(0, "FORM") && (magic(8, "AIFF") || magic(8, "AIFC"))) {
-        ok = sdsp_decode_aiff(buf, &mono, &sr, &why);
-    } else if (magic(0, "caff")) {
-        ok = sdsp_decode_caf(buf, &mono, &sr, &why);
-    } else if (magic(0, "OggS")) {
-        ok = sdsp_decode_ogg(buf, &mono, &sr, &why);
-    } else if (buf.size() >= 4 && buf[0] == 0x1A && buf[1] == 0x45 && buf[2] == 0xDF && buf[3] == 0xA3) {
-        ok = sdsp_decode_mkv(buf, &mono, &sr, &why);
-    } else if (magic(4, "ftyp")) {
-        ok = sdsp_decode_mp4(buf, &mono, &sr, &why);
-    } else if (id3 || (buf.size() >= 2 && buf[0] == 0xFF && (buf[1] & 0xE0) == 0xE0)) {
-        ok = false, why = (buf.size() >= 2 && !id3 && (buf[1] & 0xF6) == 0xF0) ? "unsupported codec: AAC (ADTS)"
-                                                                             : "unsupported codec: MPEG audio (MP1/MP2/MP3)";
-    } else {
-        if (!decode_wav(buf, &mono, &sr, err, errlen)) return SDSP_ERR_DECODING;
-        ok = true;
-    }
-    if (!ok) {
-        fail(err, errlen, why);
-        return SDSP_ERR_DECODING;
-    }
+    if (!sdsp_decode_audio_bytes(buf, &mono, &sr, err, errlen)) return SDSP_ERR_DECODING;
     float* p = (float*)std::malloc(std::max<size_t>(mono.size(), 1) * sizeof(float));
     if (!p) return SDSP_ERR_PROCESSING;
     if (!mono.empty()) std::memcpy(p, mono.data(), mono.size() * sizeof(float));

@@ -14,7 +14,8 @@ import subprocess
 
 import numpy as np
 
-from sdsp_abi import ERROR_NAMES, FLAG_NAMES, SdspConfidence, SdspConfig, SdspResult, SdspStageTimes, result_to_dict
+from sdsp_abi import (ERROR_NAMES, FLAG_NAMES, SdspConfidence, SdspConfig, SdspFlacDecodeStats, SdspResult,
+                      SdspStageTimes, result_to_dict)
 
 PKG = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LIB_PATH = os.environ.get("SDSP_LIB_PATH") or os.path.join(PKG, "lib", "libstratum_hip.so")  # override: layout/ablation builds
@@ -91,6 +92,16 @@ def _load(path):
         L.sdsp_decode_audio_file.argtypes = [C.c_char_p, C.POINTER(fp), u64p, C.POINTER(C.c_uint32), C.c_char_p,
                                              C.c_uint64]
         L.sdsp_free_samples.argtypes = [fp]
+        u32p = C.POINTER(C.c_uint32)
+        L.sdsp_decode_flac_batch_device.argtypes = [C.POINTER(C.c_char_p), u64p, C.c_uint64, C.c_int32, C.c_void_p,
+                                                    C.POINTER(C.c_void_p), u64p, u64p, u32p, C.POINTER(C.c_int32),
+                                                    C.c_char_p]
+        L.sdsp_decode_flac_batch_device.restype = C.c_int32
+        L.sdsp_last_flac_decode_stats.argtypes = [C.c_int32, C.POINTER(SdspFlacDecodeStats)]
+        L.sdsp_last_flac_decode_stats.restype = C.c_int32
+        L.sdsp_debug_flac_decode_phased.argtypes = [C.c_char_p, C.c_uint64, C.POINTER(fp), u64p, u32p, u64p, C.c_char_p,
+                                                    C.c_uint64]
+        L.sdsp_debug_flac_decode_phased.restype = C.c_int32
         L.sdsp_free_samples.restype = None
         for f in ("sdsp_device_malloc", "sdsp_device_free", "sdsp_memcpy_h2d", "sdsp_memcpy_d2h",
                   "sdsp_device_synchronize", "sdsp_compute_confidence", "sdsp_key_name", "sdsp_decode_audio_file"):
@@ -307,6 +318,63 @@ def decode_audio_file(path):
     finally:
         lib().sdsp_free_samples(p)
     return x, sr.value
+
+
+def flac_decode_stats(device=0):
+    """sdsp_last_flac_decode_stats: counters and phase times of the last device FLAC decode on `device`."""
+    t = SdspFlacDecodeStats()
+    if lib().sdsp_last_flac_decode_stats(device, C.byref(t)) != 0:
+        raise RuntimeError("sdsp_last_flac_decode_stats failed")
+    return {k: getattr(t, k) for k, _ in SdspFlacDecodeStats._fields_}
+
+
+def decode_flac_batch_device(blobs, device=0, stream=None):
+    """sdsp_decode_flac_batch_device: the FLAC files in `blobs` (bytes objects) decoded on `device`.
+    Returns (DeviceBuffer of the concatenated mono f32 tracks, offsets, lens, rates, errors, stats):
+    track i is buffer[offsets[i] : offsets[i] + lens[i]] at rates[i]; errors[i] is None or the
+    AnalysisError sdsp.decode_audio_file raises for the same bytes (then lens[i] == 0).  Raises
+    AnalysisError when the call itself cannot run (no HIP device)."""
+    blobs = [bytes(b) for b in blobs]
+    n = len(blobs)
+    ptrs = (C.c_char_p * max(n, 1))(*blobs)
+    sizes = np.array([len(b) for b in blobs], np.uint64)
+    offs, lens = np.zeros(max(n, 1), np.uint64), np.zeros(max(n, 1), np.uint64)
+    rates, status = np.zeros(max(n, 1), np.uint32), np.zeros(max(n, 1), np.int32)
+    errs = C.create_string_buffer(256 * max(n, 1))
+    d = C.c_void_p()
+    u64p = C.POINTER(C.c_uint64)
+    st = lib().sdsp_decode_flac_batch_device(ptrs, sizes.ctypes.data_as(u64p), n, device, C.c_void_p(stream or 0),
+                                             C.byref(d), offs.ctypes.data_as(u64p), lens.ctypes.data_as(u64p),
+                                             rates.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                             status.ctypes.data_as(C.POINTER(C.c_int32)), errs)
+    text = [errs.raw[256 * i:256 * (i + 1)].split(b"\0", 1)[0].decode(errors="replace") for i in range(n)]
+    if st != 0:
+        raise AnalysisError(st, text[0] if n and text[0] else "device FLAC decode failed")
+    buf = DeviceBuffer.__new__(DeviceBuffer)
+    buf.device, buf.ptr = device, d.value
+    buf.n = int((offs[:n] + lens[:n]).max()) if n else 0
+    errors = [AnalysisError(int(status[i]), "Decoding error: " + text[i]) if status[i] != 0 else None for i in range(n)]
+    return buf, offs[:n].copy(), lens[:n].copy(), rates[:n].copy(), errors, flac_decode_stats(device)
+
+
+def debug_flac_decode_phased(data):
+    """sdsp_debug_flac_decode_phased: the device decoder's four phases on the CPU.  Returns (mono
+    float32 array, sample_rate, (candidates, accepted, rejected)); raises AnalysisError as
+    decode_audio_file does."""
+    data = bytes(data)
+    p = C.POINTER(C.c_float)()
+    n = C.c_uint64()
+    sr = C.c_uint32()
+    counts = (C.c_uint64 * 3)()
+    err = C.create_string_buffer(512)
+    st = lib().sdsp_debug_flac_decode_phased(data, len(data), C.byref(p), C.byref(n), C.byref(sr), counts, err, 512)
+    if st != 0:
+        raise AnalysisError(st, "Decoding error: " + err.value.decode(errors="replace"))
+    try:
+        x = np.ctypeslib.as_array(p, shape=(n.value,)).copy() if n.value else np.zeros(0, np.float32)
+    finally:
+        lib().sdsp_free_samples(p)
+    return x, sr.value, tuple(int(v) for v in counts)
 
 
 class ResultBatch:

@@ -206,6 +206,27 @@ class SdspStageTimes(C.Structure):
     ]
 
 
+class SdspFlacDecodeStats(C.Structure):
+    """sdsp_flac_decode_stats: counters and phase times of the last sdsp_decode_flac_batch_device call."""
+
+    _fields_ = [
+        ("files", u64),
+        ("device_files", u64),
+        ("host_fallback_files", u64),
+        ("error_files", u64),
+        ("candidates", u64),
+        ("frames_accepted", u64),
+        ("frames_rejected", u64),
+        ("bytes_in", u64),
+        ("samples_out", u64),
+        ("scan_ms", C.c_double),
+        ("frames_ms", C.c_double),
+        ("chain_ms", C.c_double),
+        ("gather_ms", C.c_double),
+        ("total_ms", C.c_double),
+    ]
+
+
 class SdspConfidence(C.Structure):
     _fields_ = [
         ("bpm_confidence", f32),
