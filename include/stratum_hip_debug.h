@@ -93,6 +93,58 @@ int32_t sdsp_debug_frame_rms(const float* host_x, uint64_t n_total, const uint64
                              float* host_out, int32_t device);
 
 /*
+ * Tracks of the last analysis call on `device` whose key path was rerun in place over the last
+ * sub-batch's band-path buffers (the sequential energy fold without a second STFT);
+ * the other reruns counted in sdsp_stage_times.key_reruns ran the nested key-only pipeline.
+ */
+int32_t sdsp_debug_last_tail_reruns(int32_t device, uint64_t* n_tracks);
+
+/*
+ * Stage probe of the tempo path: the pipeline's own tempo pass (features, novelty, both tempograms;
+ * the same parameter set-up and launches as an analysis call) over host magnitude spectrograms
+ * instead of an STFT.  host_mags holds the tracks' rows back to back, frame_size / 2 + 1 values per
+ * row (cfg->frame_size), frames[t] >= 1 rows for track t; total = the sum of frames.  The caller
+ * allocates every array of `out`; the probe fills them in the kernels' own layout:
+ *   E, H, SFX      4 x total, variant-major (full, low, mid, high); SFX and SFO of the frame pair
+ *                  (f, f + 1) at f, so the last frame of a track is not written
+ *   SFO            total
+ *   MEL            mel_cap x total, mel-major; n_mels rows written
+ *   nov            5 x total (full, low, mid, high, mel), frames - 1 values per track and present
+ *                  variant; nov_sum 5 x n_tracks, variant-major
+ *   acf, fft       per (track, variant) slot t * 5 + v: acf_cap (fft_cap) pairs (bpm, value) in the
+ *                  order the kernels wrote them; acf_n / fft_n (n_tracks x 5) the entries written
+ *                  (0 for an absent variant or a track of one frame)
+ * and the band edges [bs, be), band_on[4], present[5], n_mels and the ACF grid size NB it used.
+ * Fails with SDSP_ERR_INVALID_INPUT when a capacity is too small.  Allocates only buffers of its
+ * own, released before it returns.
+ */
+typedef struct sdsp_debug_tempo_out {
+    float *E, *H, *SFX, *SFO, *MEL, *nov, *nov_sum, *acf, *fft;
+    int32_t *acf_n, *fft_n;
+    uint32_t mel_cap, acf_cap, fft_cap;
+    int32_t n_mels, NB;
+    int32_t bs[4], be[4], band_on[4], present[5];
+} sdsp_debug_tempo_out;
+int32_t sdsp_debug_tempo_stages(const float* host_mags, const uint64_t* frames, uint64_t n_tracks, uint32_t sample_rate,
+                                uint32_t hop, const sdsp_config* cfg, sdsp_debug_tempo_out* out, int32_t device);
+
+/*
+ * Stage probe of the key path: the pipeline's own key conditioning and chroma launches over host
+ * key spectrograms (rows of key-FFT / 2 + 1 values, 4097 by default; frames[t] >= 1 rows per track).
+ *   mode 0  the path the configuration selects (default: k_mask_rp on [pk_lo - 1, pk_hi + 1], then
+ *           k_hpcp_band with block-folded energies and the per-frame bound edel)
+ *   mode 1  the in-place rerun's sequence: mode 0's band mask, the mask outside the band, k_hpcp
+ *   mode 2  the nested rerun's sequence: one full-width band-kernel mask, k_hpcp
+ * Modes 1 and 2 need a configuration with sdsp_debug_key_energy_blocked() == 1.  Returns the
+ * spectrogram after conditioning (total x bins), chroma (total x 12), energy (total) and, where the
+ * band path ran (mode 0), edel (total; untouched otherwise).  info = {st_lo, st_hi, band path ran,
+ * bins}; st_lo > st_hi when no band-limited mask ran.
+ */
+int32_t sdsp_debug_key_stages(const float* host_mags, const uint64_t* frames, uint64_t n_tracks, uint32_t sample_rate,
+                              const sdsp_config* cfg, int32_t mode, float* masked, float* chroma, float* energy,
+                              float* edel, int32_t info[4], int32_t device);
+
+/*
  * Isolated STFT kernel timing: `reps` launches over n_tracks device-resident noise tracks of len
  * samples; mean launch time (HIP events on the launch stream) and algorithmic bytes per launch
  * (4 N_in + 4 F (nfft/2 + 1) per track).  stride 0 = the pipeline's row stride.

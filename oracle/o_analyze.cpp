@@ -135,6 +135,52 @@ extern "C" void sdsp_oracle_config_default(sdsp_config* c) {
     c->key_minor_leading_tone_bonus_weight = 0.2f;
 }
 
+namespace orc {
+
+// the BandCfg analyze builds from the configuration (src/lib.rs:337-374) ...
+BandCfg band_cfg_of(const sdsp_config& c) {
+    return BandCfg{(bool)c.enable_tempogram_band_fusion,
+                   c.tempogram_band_low_max_hz,
+                   c.tempogram_band_mid_max_hz,
+                   c.tempogram_band_high_max_hz,
+                   c.tempogram_band_w_full,
+                   c.tempogram_band_w_low,
+                   c.tempogram_band_w_mid,
+                   c.tempogram_band_w_high,
+                   (bool)c.tempogram_band_seed_only,
+                   c.tempogram_band_support_threshold,
+                   c.tempogram_band_consensus_bonus,
+                   (bool)c.enable_tempogram_mel_novelty,
+                   (size_t)c.tempogram_mel_n_mels,
+                   c.tempogram_mel_fmin_hz,
+                   c.tempogram_mel_fmax_hz,
+                   (size_t)c.tempogram_mel_max_filter_bins,
+                   c.tempogram_mel_weight,
+                   c.tempogram_novelty_w_spectral,
+                   c.tempogram_novelty_w_energy,
+                   c.tempogram_novelty_w_hfc,
+                   (size_t)c.tempogram_novelty_local_mean_window,
+                   (size_t)c.tempogram_novelty_smooth_window,
+                   (size_t)c.tempogram_superflux_max_filter_bins};
+}
+// ... and use_aux_variants (src/lib.rs:375-377): without them the tempogram takes no BandCfg
+bool band_cfg_used(const sdsp_config& c) {
+    return c.enable_tempogram_band_fusion || c.enable_tempogram_mel_novelty || c.tempogram_band_consensus_bonus > 0.0f;
+}
+
+// key spectrogram conditioning (src/lib.rs:1011-1060)
+void key_condition_inplace(Spec& ks, const sdsp_config& c, uint32_t sr, size_t kfft) {
+    if (c.enable_key_hpss_harmonic)
+        key_hpss_mask_inplace(ks, sr, kfft, 100.0f, 5000.0f, (size_t)c.key_hpss_frame_step,
+                              (size_t)c.key_hpss_time_margin, (size_t)c.key_hpss_freq_margin, c.key_hpss_mask_power);
+    else if (c.enable_key_harmonic_mask)
+        harmonic_mask_inplace(ks, (size_t)c.key_spectrogram_smooth_margin, c.key_harmonic_mask_power);
+    else if (c.enable_key_spectrogram_time_smoothing)
+        smooth_time_inplace(ks, (size_t)c.key_spectrogram_smooth_margin);
+}
+
+}  // namespace orc
+
 namespace {
 
 struct Out {
@@ -262,31 +308,8 @@ void analyze(const float* samples, size_t n, uint32_t sr, const sdsp_config& c, 
     tr.legacy = legacy;
 
     // tempogram (:337-812)
-    BandCfg band{(bool)c.enable_tempogram_band_fusion,
-                 c.tempogram_band_low_max_hz,
-                 c.tempogram_band_mid_max_hz,
-                 c.tempogram_band_high_max_hz,
-                 c.tempogram_band_w_full,
-                 c.tempogram_band_w_low,
-                 c.tempogram_band_w_mid,
-                 c.tempogram_band_w_high,
-                 (bool)c.tempogram_band_seed_only,
-                 c.tempogram_band_support_threshold,
-                 c.tempogram_band_consensus_bonus,
-                 (bool)c.enable_tempogram_mel_novelty,
-                 (size_t)c.tempogram_mel_n_mels,
-                 c.tempogram_mel_fmin_hz,
-                 c.tempogram_mel_fmax_hz,
-                 (size_t)c.tempogram_mel_max_filter_bins,
-                 c.tempogram_mel_weight,
-                 c.tempogram_novelty_w_spectral,
-                 c.tempogram_novelty_w_energy,
-                 c.tempogram_novelty_w_hfc,
-                 (size_t)c.tempogram_novelty_local_mean_window,
-                 (size_t)c.tempogram_novelty_smooth_window,
-                 (size_t)c.tempogram_superflux_max_filter_bins};
-    const bool use_aux = c.enable_tempogram_band_fusion || c.enable_tempogram_mel_novelty ||
-                         c.tempogram_band_consensus_bonus > 0.0f;
+    const BandCfg band = band_cfg_of(c);
+    const bool use_aux = band_cfg_used(c);
     bool has_tg = false;
     BpmEstimate tg{};
     if (!c.force_legacy_bpm && !mags.empty()) {
@@ -485,16 +508,7 @@ void analyze(const float* samples, size_t n, uint32_t sr, const sdsp_config& c, 
         const size_t khop = c.enable_key_stft_override ? std::max<size_t>(c.key_stft_hop_size, 1) : HOP;
         if (kfft & (kfft - 1)) not_impl("non power-of-two key_stft_frame_size");
         Spec ks = c.enable_key_stft_override ? compute_stft(trim.data(), trim.size(), kfft, khop) : mags;
-        if (!ks.empty()) {  // :1011-1060
-            if (c.enable_key_hpss_harmonic)
-                key_hpss_mask_inplace(ks, sr, kfft, 100.0f, 5000.0f, (size_t)c.key_hpss_frame_step,
-                                      (size_t)c.key_hpss_time_margin, (size_t)c.key_hpss_freq_margin,
-                                      c.key_hpss_mask_power);
-            else if (c.enable_key_harmonic_mask)
-                harmonic_mask_inplace(ks, (size_t)c.key_spectrogram_smooth_margin, c.key_harmonic_mask_power);
-            else if (c.enable_key_spectrogram_time_smoothing)
-                smooth_time_inplace(ks, (size_t)c.key_spectrogram_smooth_margin);
-        }
+        if (!ks.empty()) key_condition_inplace(ks, c, sr, kfft);  // :1011-1060
         // log-frequency spectrogram (:1062-1095)
         std::vector<float> chroma, energies;
         bool use_log = false;
@@ -860,6 +874,27 @@ void sdsp_oracle_fft(float* io_interleaved, uint64_t M) {
     std::memcpy(x.data(), io_interleaved, (size_t)M * sizeof(Cx));
     fft_complex(x);
     std::memcpy(io_interleaved, x.data(), (size_t)M * sizeof(Cx));
+}
+
+// Key stage export (tests/test_gpu_key_stages.py): the configuration's key spectrogram conditioning
+// in place over `spec` (frames x bins, bins = fft / 2 + 1), then hpcp_frames with its peaks, harmonics,
+// decay and mag_power: chroma (frames x 12) and the frame energies.
+int32_t sdsp_oracle_key_stages(float* spec, uint64_t frames, uint64_t bins, uint32_t sr, const sdsp_config* c,
+                               float* chroma, float* energies) {
+    if (frames == 0 || bins < 2) return -1;
+    Spec ks;
+    ks.frames = (size_t)frames;
+    ks.bins = (size_t)bins;
+    ks.d.assign(spec, spec + frames * bins);
+    const size_t kfft = (size_t)(bins - 1) * 2;
+    key_condition_inplace(ks, *c, sr, kfft);
+    std::vector<float> ch, en;
+    hpcp_frames(ks, sr, kfft, c->soft_mapping_sigma, (size_t)c->key_hpcp_peaks_per_frame, (size_t)c->key_hpcp_num_harmonics,
+                c->key_hpcp_harmonic_decay, c->key_hpcp_mag_power, &ch, &en);
+    std::memcpy(spec, ks.d.data(), ks.d.size() * sizeof(float));
+    std::memcpy(chroma, ch.data(), ch.size() * sizeof(float));
+    std::memcpy(energies, en.data(), en.size() * sizeof(float));
+    return 0;
 }
 
 // combined full-band novelty of an STFT magnitude array (frames x bins), default band cfg

@@ -229,6 +229,11 @@ std::vector<size_t> spectral_flux_onsets(const Spec& m, float pct) {
     if (!(pct >= 0.0f && pct <= 1.0f)) fail(SDSP_ERR_INVALID_INPUT, "Threshold percentile must be in [0, 1]");
     if (m.bins == 0) fail(SDSP_ERR_INVALID_INPUT, "Empty magnitude frames");
     if (m.frames < 2) return {};
+    return peaks_over_percentile(spectral_flux_curve(m), pct);
+}
+
+// spectral_flux.rs:116-157: L2 half-wave flux between max-normalised frames
+std::vector<float> spectral_flux_curve(const Spec& m) {
     const size_t B = m.bins;
     std::vector<float> mx(m.frames);
     for (size_t t = 0; t < m.frames; t++) {
@@ -251,7 +256,7 @@ std::vector<size_t> spectral_flux_onsets(const Spec& m, float pct) {
         }
         flux[t - 1] = __builtin_sqrtf(sum);
     }
-    return peaks_over_percentile(flux, pct);
+    return flux;
 }
 
 // src/features/onset/hfc.rs:70-214
@@ -473,6 +478,18 @@ const char* sdsp_oracle_probe_error(void) { return g_probe_err.c_str(); }
 int64_t sdsp_oracle_energy_flux_onsets(const float* s, uint64_t n, uint64_t frame, uint64_t hop, float thr_db,
                                        uint64_t* out, uint64_t cap) {
     return probe_call([&]() -> int64_t { return put_list(energy_flux_onsets(s, n, frame, hop, thr_db), out, cap); });
+}
+
+// the spectral-flux onset feature curve (frames - 1 values; 0 below two frames)
+int64_t sdsp_oracle_spectral_flux_curve(const float* spec, uint64_t frames, uint64_t bins, float* out) {
+    return probe_call([&]() -> int64_t {
+        Spec m;
+        spec_from_rows(spec, frames, bins, nullptr, &m);
+        if (m.frames < 2 || m.bins == 0) return 0;
+        const std::vector<float> f = spectral_flux_curve(m);
+        std::memcpy(out, f.data(), f.size() * sizeof(float));
+        return (int64_t)f.size();
+    });
 }
 
 // detect_spectral_flux_onsets (spectral_flux.rs:69-221) -> onset frame indices

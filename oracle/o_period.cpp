@@ -374,8 +374,8 @@ static std::vector<float> scalar_flux_norm(const std::vector<float>& e) {
 }
 
 // superflux over the band [start,end) of log frames (novelty.rs:336-455; full band == [0,n))
-static std::vector<float> superflux(const std::vector<float>& lf, size_t frames, size_t bins, size_t k,
-                                    size_t start, size_t end) {
+static std::vector<float> superflux_raw(const std::vector<float>& lf, size_t frames, size_t bins, size_t k,
+                                        size_t start, size_t end) {
     std::vector<float> flux;
     if (frames < 2) return flux;
     k = std::max<size_t>(k, 1);
@@ -393,6 +393,12 @@ static std::vector<float> superflux(const std::vector<float>& lf, size_t frames,
         }
         flux.push_back(__builtin_sqrtf(sum));
     }
+    return flux;
+}
+static std::vector<float> superflux(const std::vector<float>& lf, size_t frames, size_t bins, size_t k, size_t start,
+                                    size_t end, std::vector<float>* raw_out = nullptr) {
+    std::vector<float> flux = superflux_raw(lf, frames, bins, k, start, end);
+    if (raw_out) *raw_out = flux;
     normalize_in_place(flux);
     return flux;
 }
@@ -473,7 +479,7 @@ static std::vector<float> frame_hfc(const Spec& m, size_t s, size_t e) {
 
 // MelFilterbank::new + apply_logmag + mel_superflux_novelty, novelty.rs:71-190, 553-609
 static std::vector<float> mel_superflux(const Spec& m, const NovFrames& lf, uint32_t sr, size_t n_mels_in,
-                                        float fmin_hz, float fmax_hz, size_t kk) {
+                                        float fmin_hz, float fmax_hz, size_t kk, StageVariant* dump = nullptr) {
     if (m.frames < 2) return {};
     if (sr == 0) fail(SDSP_ERR_INVALID_INPUT, "Sample rate must be > 0");
     const size_t n_bins = m.bins;
@@ -521,6 +527,10 @@ static std::vector<float> mel_superflux(const Spec& m, const NovFrames& lf, uint
             if (v <= 0.0f) continue;
             for (auto& cw : contrib[b]) mv[cw.first] += v * cw.second;
         }
+    }
+    if (dump) {
+        dump->melf = melf;
+        dump->e = n_mels;
     }
     const size_t k = std::max<size_t>(kk, 1);
     std::vector<float> flux;
@@ -641,7 +651,22 @@ std::vector<float> combined_full_novelty(const Spec& m, uint32_t sr, const BandC
 
 // tempogram.rs:255-775 (estimate_bpm_tempogram_impl); cands = full scored list (callers truncate)
 void tempogram_impl(const Spec& m, uint32_t sr, uint32_t hop, float min_bpm, float max_bpm, float res,
-                    const BandCfg* band, BpmEstimate* est, std::vector<TempoCand>* cands_out) {
+                    const BandCfg* band, BpmEstimate* est, std::vector<TempoCand>* cands_out,
+                    std::vector<StageVariant>* dump) {
+    // stage export (tests): what each seeded variant was computed from, as it is computed
+    auto note = [&](const char* name, size_t s, size_t e, const std::vector<float>& fe, const std::vector<float>& fh,
+                    const std::vector<float>& raw, const std::vector<float>& sf) {
+        if (!dump) return;
+        StageVariant sv;
+        sv.name = name;
+        sv.s = s;
+        sv.e = e;
+        sv.energy = fe;
+        sv.hfc = fh;
+        sv.sfx_raw = raw;
+        sv.sf = sf;
+        dump->push_back(sv);
+    };
     const size_t n_bins = m.frames ? m.bins : 0;
     if (n_bins == 0) fail(SDSP_ERR_INVALID_INPUT, "Empty magnitude frames");
     const size_t fft_size = std::max<size_t>((n_bins >= 1 ? n_bins - 1 : 0) * 2, 2);
@@ -661,9 +686,12 @@ void tempogram_impl(const Spec& m, uint32_t sr, uint32_t hop, float min_bpm, flo
     NovFrames lf = log_frames(m);
     std::vector<float> nov_full;
     {
-        auto sf = superflux(lf.logf_, m.frames, m.bins, sf_k, 0, m.bins);
-        auto en = m.frames >= 2 ? scalar_flux_norm(frame_energy(m, 0, m.bins)) : std::vector<float>{};
-        auto hf = m.frames >= 2 ? scalar_flux_norm(frame_hfc(m, 0, m.bins)) : std::vector<float>{};
+        std::vector<float> raw;
+        auto sf = superflux(lf.logf_, m.frames, m.bins, sf_k, 0, m.bins, &raw);
+        const auto fe = frame_energy(m, 0, m.bins), fh = frame_hfc(m, 0, m.bins);
+        auto en = m.frames >= 2 ? scalar_flux_norm(fe) : std::vector<float>{};
+        auto hf = m.frames >= 2 ? scalar_flux_norm(fh) : std::vector<float>{};
+        note("full", 0, m.bins, fe, fh, raw, sf);
         if (band)
             nov_full = combine(sf, en, hf, band->nw_spectral, band->nw_energy, band->nw_hfc, band->local_mean_window,
                                band->smooth_window);
@@ -674,6 +702,11 @@ void tempogram_impl(const Spec& m, uint32_t sr, uint32_t hop, float min_bpm, flo
     auto mk = [&](const char* name, float w, const std::vector<float>& nov) {
         Variant v{name, w, fft_tempogram(nov, sr, hop, min_bpm, max_bpm), acf_tempogram(nov, sr, hop, min_bpm, max_bpm, res),
                   0.0f, 0.0f};
+        if (dump) {  // the variant's record is the last one noted
+            dump->back().nov = nov;
+            dump->back().fft = v.fft;
+            dump->back().ac = v.ac;
+        }
         v.max_fft = sd_maxf(v.fft.empty() ? 1.0f : v.fft[0].second, 1e-12f);
         v.max_ac = sd_maxf(v.ac.empty() ? 1.0f : v.ac[0].second, 1e-12f);
         return v;
@@ -698,22 +731,32 @@ void tempogram_impl(const Spec& m, uint32_t sr, uint32_t hop, float min_bpm, flo
             if (!(sd_isfinite_f(b.w) && b.w > 0.0f)) continue;
             if (b.e <= b.s + 1) continue;
             const size_t s = std::min(b.s, n_bins), e = std::min(b.e, n_bins);
-            std::vector<float> sp, en, hf;
+            std::vector<float> sp, en, hf, raw, fe, fh;
             if (m.frames >= 2 && e > s + 1) {
-                sp = superflux(lf.logf_, m.frames, m.bins, sf_k, s, e);
-                en = scalar_flux_norm(frame_energy(m, s, e));
-                hf = scalar_flux_norm(frame_hfc(m, s, e));
+                sp = superflux(lf.logf_, m.frames, m.bins, sf_k, s, e, &raw);
+                fe = frame_energy(m, s, e);
+                fh = frame_hfc(m, s, e);
+                en = scalar_flux_norm(fe);
+                hf = scalar_flux_norm(fh);
             }
             auto nov = combine(sp, en, hf, band->nw_spectral, band->nw_energy, band->nw_hfc, band->local_mean_window,
                                band->smooth_window);
             if (nov.empty()) continue;
+            note(b.n, s, e, fe, fh, raw, sp);
             seeds.push_back(mk(b.n, b.w, nov));
         }
     }
     if (band && band->enable_mel) {
+        StageVariant mel;
         auto mc = mel_superflux(m, lf, sr, band->mel_n_mels, band->mel_fmin_hz, band->mel_fmax_hz,
-                                band->mel_max_filter_bins);
-        if (!mc.empty()) seeds.push_back(mk("mel", band->w_mel, mc));
+                                band->mel_max_filter_bins, dump ? &mel : nullptr);
+        if (!mc.empty()) {
+            if (dump) {
+                mel.name = "mel";
+                dump->push_back(mel);
+            }
+            seeds.push_back(mk("mel", band->w_mel, mc));
+        }
     }
     const bool seed_only = band ? band->seed_only : true;
     std::vector<const Variant*> score_v;
@@ -1227,6 +1270,61 @@ int32_t sdsp_oracle_tempogram_estimate(const float* spec, uint64_t frames, uint6
         out3[2] = (float)e.method_agreement;
         return 0;
     });
+}
+
+// Stage export of tempogram_impl under the configuration's BandCfg (tests/test_gpu_tempo_stages.py):
+// the seeded variants in order (full, then the bands and mel that were seeded), kept until the next
+// call.  Returns the number of variants, or -(error code) when tempogram_impl failed after them.
+static std::vector<StageVariant> g_stages;
+static BpmEstimate g_stages_est{0.0f, 0.0f, 0};
+int64_t sdsp_oracle_tempo_stages(const float* spec, uint64_t frames, uint64_t bins, uint32_t sr, uint32_t hop,
+                                 const sdsp_config* c) {
+    g_stages.clear();
+    probe_call([&]() -> int64_t {
+        Spec m;
+        spec_from_rows(spec, frames, bins, nullptr, &m);
+        const BandCfg band = band_cfg_of(*c);
+        g_stages_est = BpmEstimate{0.0f, 0.0f, 0};
+        tempogram_impl(m, sr, hop, c->min_bpm, c->max_bpm, c->bpm_resolution, band_cfg_used(*c) ? &band : nullptr,
+                       &g_stages_est, nullptr, &g_stages);
+        return 0;
+    });
+    return (int64_t)g_stages.size();
+}
+// the estimate of that tempogram_impl call: (bpm, confidence, method agreement); zeros when it failed
+void sdsp_oracle_tempo_stages_estimate(float* out3) {
+    out3[0] = g_stages_est.bpm;
+    out3[1] = g_stages_est.confidence;
+    out3[2] = (float)g_stages_est.method_agreement;
+}
+
+// what: 0 frame energy, 1 frame HFC, 2 raw superflux, 3 normalised superflux, 4 novelty, 5 / 6 FFT
+// tempogram (bpm / power), 7 / 8 ACF tempogram (bpm / strength), 9 mel log-magnitudes (frames x
+// n_mels).  info = {first bin, end bin (mel: n_mels)}; name holds >= 8 bytes.  Returns the length.
+int64_t sdsp_oracle_tempo_stage_get(uint64_t variant, int32_t what, float* out, uint64_t cap, char* name, uint64_t* info) {
+    if (variant >= g_stages.size()) return -1;
+    const StageVariant& v = g_stages[(size_t)variant];
+    if (name) std::snprintf(name, 8, "%s", v.name.c_str());
+    if (info) {
+        info[0] = v.s;
+        info[1] = v.e;
+    }
+    std::vector<float> r;
+    switch (what) {
+        case 0: r = v.energy; break;
+        case 1: r = v.hfc; break;
+        case 2: r = v.sfx_raw; break;
+        case 3: r = v.sf; break;
+        case 4: r = v.nov; break;
+        case 5: for (auto& p : v.fft) r.push_back(p.first); break;
+        case 6: for (auto& p : v.fft) r.push_back(p.second); break;
+        case 7: for (auto& p : v.ac) r.push_back(p.first); break;
+        case 8: for (auto& p : v.ac) r.push_back(p.second); break;
+        case 9: r = v.melf; break;
+        default: return -1;
+    }
+    if (out && r.size() <= cap) std::memcpy(out, r.data(), r.size() * sizeof(float));
+    return (int64_t)r.size();
 }
 
 // multi_resolution_analysis (multi_resolution.rs:76-203): estimate_bpm_tempogram of the same

@@ -72,6 +72,7 @@ void detect_and_trim(const std::vector<float>& x, uint32_t sr, float threshold_d
                      size_t frame_size, size_t* trim_start, size_t* trim_end,
                      std::vector<std::pair<size_t, size_t>>* silence_map = nullptr);
 std::vector<size_t> energy_flux_onsets(const float* s, size_t n, size_t frame, size_t hop, float thr_db);
+std::vector<float> spectral_flux_curve(const Spec& m);  // the flux spectral_flux_onsets thresholds (frames >= 2)
 std::vector<size_t> spectral_flux_onsets(const Spec& m, float pct);
 std::vector<size_t> hfc_onsets(const Spec& m, uint32_t sr, float pct);
 struct OnsetCand {
@@ -105,8 +106,20 @@ struct BandCfg {
     size_t local_mean_window, smooth_window, superflux_k;
 };
 std::vector<float> combined_full_novelty(const Spec& m, uint32_t sr, const BandCfg& c);
+// AnalysisConfig -> the BandCfg analyze passes (src/lib.rs:337-377), and whether it passes one
+BandCfg band_cfg_of(const sdsp_config& c);
+bool band_cfg_used(const sdsp_config& c);
+// Stage export (test probes): what tempogram_impl computed one seeded variant from.  Bands: bins
+// [s, e); mel: e = n_mels, melf = the mel log-magnitudes (frames x n_mels), the curve in nov.
+struct StageVariant {
+    std::string name;
+    size_t s = 0, e = 0;
+    std::vector<float> energy, hfc, sfx_raw, sf, nov, melf;
+    std::vector<std::pair<float, float>> fft, ac;
+};
 void tempogram_impl(const Spec& m, uint32_t sr, uint32_t hop, float min_bpm, float max_bpm, float res,
-                    const BandCfg* band, BpmEstimate* est, std::vector<TempoCand>* cands);
+                    const BandCfg* band, BpmEstimate* est, std::vector<TempoCand>* cands,
+                    std::vector<StageVariant>* dump = nullptr);
 void multi_resolution(const std::vector<float>& samples, uint32_t sr, size_t frame_size, float min_bpm,
                       float max_bpm, float res, size_t top_k, float w512, float w256, float w1024,
                       float structural_discount, float dt512, float margin_threshold, bool human_prior,
@@ -124,6 +137,8 @@ bool generate_beat_grid(float bpm, float conf, const std::vector<float>& onsets_
 
 // ---------- key (chroma/, key/) ----------
 void harmonic_mask_inplace(Spec& s, size_t margin, float power);
+// the key spectrogram conditioning analyze applies (src/lib.rs:1011-1060)
+void key_condition_inplace(Spec& ks, const sdsp_config& c, uint32_t sr, size_t kfft);
 void hpcp_frames(const Spec& s, uint32_t sr, size_t fft_size, float sigma, size_t peaks, size_t harmonics,
                  float decay, float mag_power, std::vector<float>* chroma12, std::vector<float>* energies);
 void smooth_chroma_inplace(std::vector<float>& ch, size_t frames, size_t window);

@@ -336,3 +336,76 @@ def dot_product(a, b):
 
 def compute_key_clarity(scores):
     return oracle.key_clarity([s for _, s in scores]) if scores else 0.0
+
+
+# ---- stage exports (tests/test_oracle_stage_exports.py, tests/test_gpu_tempo_stages.py, test_gpu_key_stages.py) ----
+_STAGE_WHAT = {"energy": 0, "hfc": 1, "sfx_raw": 2, "sf": 3, "nov": 4, "fft_bpm": 5, "fft_val": 6, "acf_bpm": 7,
+               "acf_val": 8, "melf": 9}
+
+
+def tempo_stages(spec, sample_rate=44100, hop=512, config=None):
+    """tempogram_impl's seeded variants under the configuration's BandCfg, in order: {name: dict} with
+    s, e (band bins; mel: e = n_mels), energy, hfc (raw per frame), sfx_raw, sf (superflux before /
+    after normalisation), nov, fft / acf ((n, 2) arrays of (bpm, value), sorted as the tempogram
+    returns them) and, for mel, melf (frames, n_mels)."""
+    L = lib()
+    L.sdsp_oracle_tempo_stages.argtypes = [fp, C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32,
+                                           C.POINTER(oracle.SdspConfig)]
+    L.sdsp_oracle_tempo_stages.restype = C.c_int64
+    L.sdsp_oracle_tempo_stage_get.argtypes = [C.c_uint64, C.c_int32, fp, C.c_uint64, C.c_char_p, u64p]
+    L.sdsp_oracle_tempo_stage_get.restype = C.c_int64
+    cfg = config if config is not None else oracle.default_config()
+    m = np.ascontiguousarray(spec, dtype=np.float32)
+    n = L.sdsp_oracle_tempo_stages(_p(m), m.shape[0], m.shape[1], sample_rate, hop, C.byref(cfg))
+    out = {}
+    for i in range(n):
+        name = C.create_string_buffer(8)
+        info = np.zeros(2, np.uint64)
+
+        def get(what):
+            k = L.sdsp_oracle_tempo_stage_get(i, _STAGE_WHAT[what], None, 0, name, _u64(info))
+            a = np.zeros(max(k, 1), np.float32)
+            L.sdsp_oracle_tempo_stage_get(i, _STAGE_WHAT[what], _p(a), a.size, name, _u64(info))
+            return a[:k]
+
+        d = {k: get(k) for k in ("energy", "hfc", "sfx_raw", "sf", "nov")}
+        d["fft"] = np.stack([get("fft_bpm"), get("fft_val")], axis=1)
+        d["acf"] = np.stack([get("acf_bpm"), get("acf_val")], axis=1)
+        d["s"], d["e"] = int(info[0]), int(info[1])
+        if name.value == b"mel":
+            d["melf"] = get("melf").reshape(m.shape[0], d["e"])
+        out[name.value.decode()] = d
+    return out
+
+
+def tempo_stages_estimate():
+    """(bpm, confidence, method agreement) of the tempogram_impl call the last tempo_stages() made."""
+    out = np.zeros(3, np.float32)
+    lib().sdsp_oracle_tempo_stages_estimate.argtypes = [fp]
+    lib().sdsp_oracle_tempo_stages_estimate(_p(out))
+    return float(out[0]), float(out[1]), int(out[2])
+
+
+def spectral_flux_curve(spec):
+    """The flux detect_spectral_flux_onsets thresholds: frames - 1 values."""
+    L = lib()
+    L.sdsp_oracle_spectral_flux_curve.argtypes = [fp, C.c_uint64, C.c_uint64, fp]
+    L.sdsp_oracle_spectral_flux_curve.restype = C.c_int64
+    m = np.ascontiguousarray(spec, dtype=np.float32)
+    out = np.zeros(max(m.shape[0], 1), np.float32)
+    n = _check(L.sdsp_oracle_spectral_flux_curve(_p(m), m.shape[0], m.shape[1], _p(out)))
+    return out[:n]
+
+
+def key_stages(spec, sample_rate=44100, config=None):
+    """The configuration's key spectrogram conditioning, then hpcp_frames with its peaks, harmonics,
+    decay and mag_power: (conditioned spectrogram, chroma (frames, 12), frame energies)."""
+    L = lib()
+    L.sdsp_oracle_key_stages.argtypes = [fp, C.c_uint64, C.c_uint64, C.c_uint32, C.POINTER(oracle.SdspConfig), fp, fp]
+    L.sdsp_oracle_key_stages.restype = C.c_int32
+    cfg = config if config is not None else oracle.default_config()
+    m = np.array(spec, dtype=np.float32, order="C")
+    ch, en = np.zeros((m.shape[0], 12), np.float32), np.zeros(m.shape[0], np.float32)
+    if L.sdsp_oracle_key_stages(_p(m), m.shape[0], m.shape[1], sample_rate, C.byref(cfg), _p(ch), _p(en)) != 0:
+        raise AnalysisError(1, "key_stages: empty spectrogram")
+    return m, ch, en

@@ -30,6 +30,7 @@
 #include <vector>
 
 #include "../../include/sdsp_fft_spec.h"
+#include "../../include/stratum_hip_debug.h"
 #include "batch_sched.hpp"
 #include "kernels.hpp"
 #include "sdsp_runtime.hpp"
@@ -596,6 +597,20 @@ std::string unsupported(const sdsp_config& c, uint32_t sr) {
     return "";
 }
 
+// What a tempo pass launched with, kept for the stage probe (sdsp_debug_tempo_stages): the
+// parameters the pass built and its tempogram lists, which are locals of tempo_pass otherwise.
+// Device pointers stay valid until the next pass with the same tag.
+struct TempoStageDbg {
+    FeatParams fp{};
+    int present[NVAR] = {0, 0, 0, 0, 0};
+    int NB = 0;
+    std::vector<int> items;          // (track, variant) = track * NVAR + variant, in launch order
+    std::vector<uint64_t> fft_off;   // per item: first entry of its FFT list
+    std::vector<int> fft_k;          // per item: entries of its FFT list
+    const float *acf_bpm = nullptr, *acf_str = nullptr;  // item i at [i * NB, (i + 1) * NB)
+    const float *fft_bpm = nullptr, *fft_pow = nullptr;
+};
+
 // One "tempo pass": STFT (2048, hop) -> features -> novelty -> tempograms -> candidate scoring,
 // for a dense list of tracks.  Used for hop 512 (all tracks) and the escalation hops.
 struct TempoPassIn {
@@ -619,6 +634,7 @@ struct TempoPassIn {
     // also the hop-512 novelty multi_resolution.rs:680-694 gates its folds with (the combined
     // novelty with the configured weights, whatever the band-fusion setting; out.nov_mr)
     bool mr_nov = false;
+    TempoStageDbg* dbg = nullptr;  // the stage probe's record (never set by an analysis call)
 };
 struct TempoPassOut {
     std::vector<uint64_t> fpfx;  // frame prefix over the pass's tracks
@@ -830,7 +846,7 @@ void print_debug(const sdsp_config& c, const TrackDbg& d) {
 class Pipeline {
    public:
     Pipeline(DeviceCtx& d, const sdsp_config& cfg, uint32_t sr, int stages = SDSP_STAGES_FULL, bool exact_energy = false,
-             bool key_only = false, bool nested = false)
+             bool key_only = false, bool nested = false, bool probe = false)
         : c_(d),
           d_(d),
           cfg_(cfg),
@@ -838,15 +854,21 @@ class Pipeline {
           bpm_only_(stages == SDSP_STAGES_BPM_ONLY),
           exact_energy_(exact_energy),
           key_only_(key_only),
-          nested_(nested),
+          nested_(nested || probe),
           fs_((int)std::min<uint64_t>(cfg.frame_size, STFT_GEN_MAX)),
           nb_(fs_ / 2 + 1),
           s2_(base_stride(fs_)),
           kfs_((int)std::min<uint64_t>(key_fft(cfg), STFT_GEN_MAX)),
           khop_((int)std::min<uint64_t>(std::max<uint64_t>(key_hop(cfg), 1), INT32_MAX)),
           ks_(base_stride(kfs_)) {
-        if (nested_) c_.pre = "X.";
+        if (nested_) c_.pre = probe ? "D." : "X.";
     }
+    // Stage probes (include/stratum_hip_debug.h), on a pipeline built with probe = true: its buffers
+    // carry the prefix "D." and everything runs in order on the main stream, like a nested rerun.
+    void debug_tempo_stages(const float* host_mags, const uint64_t* frames, uint64_t n_tracks, int hop,
+                            sdsp_debug_tempo_out* out);
+    void debug_key_stages(const float* host_mags, const uint64_t* frames, uint64_t n_tracks, int mode, float* masked,
+                          float* chroma, float* energy, float* edel, int32_t info[4]);
 
     void run(const float* d_samples, const std::vector<uint64_t>& in_off, const std::vector<uint64_t>& n_raw,
              std::vector<TrackRes>& res);
@@ -870,6 +892,7 @@ class Pipeline {
     // the sub-batch being run is the call's last (its key vote runs alone at the tail)
     bool last_sub_ = false;
     uint64_t reruns_ = 0;
+    uint64_t tail_reruns_ = 0;  // of those, the tracks rerun_tail reran in place (sdsp_debug_last_tail_reruns)
     double rerun_ms_ = 0.0;
     void rerun_near(const float* d_samples, const std::vector<uint64_t>& in_off, const std::vector<uint64_t>& n_raw,
                     const std::vector<size_t>& near, std::vector<TrackRes>& res);
@@ -919,8 +942,35 @@ class Pipeline {
     std::unique_ptr<KeyPending> key_pending_;
     std::unique_ptr<KeyPending> tail_;  // the last sub-batch's pending join, kept for rerun_tail
     int sb_parity_ = 0;
+    // what key_condition launched with
+    struct KeyCond {
+        HpcpParams hp{};
+        bool band = false;  // the band path: k_mask_rp on [pk_lo - 1, pk_hi + 1], k_hpcp_band
+        int st_lo = 0, st_hi = -1;  // the bins launch_mask_band stored (blocked configurations)
+        float *d_part = nullptr, *d_chroma = nullptr, *d_energy = nullptr, *d_edel = nullptr, *d_tune = nullptr;
+        const HarmEntry* d_ht = nullptr;
+    };
+    KeyCond key_condition(const std::string& EP, float* mags8, const std::vector<uint64_t>& kpfx,
+                          const std::vector<uint64_t>& ktile, uint64_t* d_kpfx, uint64_t* d_ktile, int* d_kid,
+                          hipStream_t st2, Timers& kt);
     std::vector<size_t> finish_key(std::vector<TrackRes>& res, bool keep_tail = false);
     void rerun_tail(const std::vector<size_t>& near, std::vector<TrackRes>& res);
+    // the band path's spectrogram, block sums, HPCP parameters and chroma / energy buffers, as
+    // tail_exact reads them
+    void tail_buffers(KeyTail& t, const KeyCond& kc, float* mags8, uint64_t* d_kpfx, uint64_t total8) const {
+        t.mags8 = mags8;
+        t.d_kpfx = d_kpfx;
+        t.d_part = kc.d_part;
+        t.total8 = total8;
+        t.st_lo = kc.st_lo;
+        t.st_hi = kc.st_hi;
+        t.B8 = kc.hp.B;
+        t.hp = kc.hp;
+        t.d_ht = kc.d_ht;
+        t.d_chroma = kc.d_chroma;
+        t.d_energy = kc.d_energy;
+    }
+    void tail_exact(const KeyTail& t, const int* d_sel, int n, const uint64_t* d_tiles, uint64_t n_tiles, hipStream_t st);
     void tempo_pass(const std::string& tag, const TempoPassIn& in, TempoPassOut& out);
     void legacy_select(const TempoPassIn& bin, const uint32_t* d_onsets, const uint64_t* d_on_off, const int* d_on_n,
                        const std::vector<int>& R, const std::vector<int>& idx, std::vector<TrackRes>& res,
@@ -1013,6 +1063,7 @@ void Pipeline::run(const float* d_samples, const std::vector<uint64_t>& in_off, 
     times_.key_reruns = reruns_;  // in-flight reruns (rerun_near), their time inside total_ms
     times_.rerun_ms = rerun_ms_;
     d_.last = times_;
+    if (!exact_energy_ && !nested_) d_.last_tail_reruns = tail_reruns_;
 }
 
 void Pipeline::loudness_prepass(const float* d_samples, const std::vector<uint64_t>& in_off,
@@ -1430,6 +1481,21 @@ void Pipeline::tempo_pass(const std::string& tag, const TempoPassIn& in, TempoPa
         SDSP_HIP_CHECK(hipGetLastError());
     }
     (void)d_fft_off_items;
+    if (in.dbg) {
+        TempoStageDbg& g = *in.dbg;
+        g.fp = fp;
+        for (int v = 0; v < NVAR; v++) g.present[v] = present[v];
+        g.NB = NB;
+        g.items = items;
+        g.fft_off = fft_off;
+        g.fft_k.assign(n_it, 0);
+        for (auto& pc : classes)
+            for (int i : pc.pos) g.fft_k[(size_t)i] = pc.prm.K;
+        g.acf_bpm = acf_bpm;
+        g.acf_str = acf_str;
+        g.fft_bpm = fft_bpm;
+        g.fft_pow = fft_pow;
+    }
     // per (track, variant) offsets for the selector
     std::vector<uint64_t> fo((size_t)P_T * NVAR, 0), ao((size_t)P_T * NVAR, 0);
     for (size_t i = 0; i < n_it; i++) {
@@ -1505,11 +1571,16 @@ std::vector<size_t> Pipeline::finish_key(std::vector<TrackRes>& res, bool keep_t
 // masked spectrogram there (the same masked values the nested rerun's full-bin mask stores), k_hpcp
 // folds each frame's energy in bin order (and rewrites the same chroma), and the vote runs on the
 // exact energies: the nested rerun's results without its front end and 8192-point STFT.
-void Pipeline::rerun_tail(const std::vector<size_t>& near, std::vector<TrackRes>& res) {
+void Pipeline::rerun_tail(const std::vector<size_t>& near_all, std::vector<TrackRes>& res) {
     std::unique_ptr<KeyPending> kp = std::move(tail_);
-    if (near.empty() || !kp || exact_energy_ || nested_) return;
+    if (near_all.empty() || !kp || exact_energy_ || nested_) return;
     const KeyTail& t = kp->tail;
     const auto t0 = std::chrono::steady_clock::now();
+    // a track that already failed keeps its error: its key fields are not reported, nothing to certify
+    std::vector<size_t> near;
+    for (size_t i : near_all)
+        if (res[i].status == SDSP_OK) near.push_back(i);
+    if (near.empty()) return;
     std::vector<int> sel;
     for (size_t i : near)
         for (size_t k = 0; k < kp->at.size(); k++)
@@ -1526,11 +1597,7 @@ void Pipeline::rerun_tail(const std::vector<size_t>& near, std::vector<TrackRes>
     int* d_sel = c_.up("E.tail_sel", sel);
     uint64_t* d_tp = c_.up("E.tail_tile", tp);
     uint64_t* d_sp = c_.up("E.tail_seg", sp);
-    launch_mask_band(t.mags8, ks_, t.B8, t.d_kpfx, d_sel, n, cfg_.key_harmonic_mask_power, t.st_lo, t.st_hi, t.d_part,
-                     t.total8, st, true);
-    SDSP_HIP_CHECK(hipGetLastError());
-    launch_hpcp(t.mags8, t.d_kpfx, d_tp, d_sel, n, tp.back(), t.hp, t.d_ht, t.d_chroma, t.d_energy, st);
-    SDSP_HIP_CHECK(hipGetLastError());
+    tail_exact(t, d_sel, n, d_tp, tp.back(), st);
     KeyParams kx = t.kp;
     kx.near_check = 0;  // the exact energies: nothing left to certify
     // (the vote writes out[track], so the selected tracks' entries of the sub-batch's KeyOut array)
@@ -1544,6 +1611,7 @@ void Pipeline::rerun_tail(const std::vector<size_t>& near, std::vector<TrackRes>
         if (!o.ok) {
             r.status = SDSP_ERR_PROCESSING;
             r.err = "Processing error: key certification rerun failed (no key from the exact energies)";
+            r.key_rerun = true;  // the rerun ran: run_locked does not run it again
             continue;
         }
         r.key_mode = o.mode;
@@ -1553,7 +1621,19 @@ void Pipeline::rerun_tail(const std::vector<size_t>& near, std::vector<TrackRes>
         r.key_rerun = true;
     }
     reruns_ += (uint64_t)n;
+    tail_reruns_ += (uint64_t)n;
     rerun_ms_ += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+}
+
+// The in-place rerun's kernels over the band path's buffers: the mask on the bins outside the
+// stored band, then the sequential-energy HPCP, for the selected key tracks.
+void Pipeline::tail_exact(const KeyTail& t, const int* d_sel, int n, const uint64_t* d_tiles, uint64_t n_tiles,
+                          hipStream_t st) {
+    launch_mask_band(t.mags8, ks_, t.B8, t.d_kpfx, d_sel, n, cfg_.key_harmonic_mask_power, t.st_lo, t.st_hi, t.d_part,
+                     t.total8, st, true);
+    SDSP_HIP_CHECK(hipGetLastError());
+    launch_hpcp(t.mags8, t.d_kpfx, d_tiles, d_sel, n, n_tiles, t.hp, t.d_ht, t.d_chroma, t.d_energy, st);
+    SDSP_HIP_CHECK(hipGetLastError());
 }
 
 // The exact key rerun of near-decision tracks for a finished sub-batch, from inside
@@ -1583,6 +1663,247 @@ void Pipeline::rerun_near(const float* d_samples, const std::vector<uint64_t>& i
     }
     reruns_ += near.size();
     rerun_ms_ += d_.last.total_ms;  // px.run's
+}
+
+// Key spectrogram conditioning and chroma (src/lib.rs:1011-1197) of the key tracks whose frame
+// prefix is kpfx, in place over mags8 on st2: the branch the configuration selects, with the
+// parameters every launch takes.  sub_batch's key path and the key stage probe both run this.
+Pipeline::KeyCond Pipeline::key_condition(const std::string& EP, float* mags8, const std::vector<uint64_t>& kpfx,
+                                          const std::vector<uint64_t>& ktile, uint64_t* d_kpfx, uint64_t* d_ktile,
+                                          int* d_kid, hipStream_t st2, Timers& kt) {
+    const int NK = (int)kpfx.size() - 1;
+    const int KFS = kfs_;
+    const int B8 = KFS / 2 + 1;
+    const float fres8 = (float)sr_ / (float)KFS;
+    const uint64_t total8 = kpfx.back();
+    float* d_tune = nullptr;  // per key track tuning offset (tuning compensation)
+    // key spectrogram conditioning (src/lib.rs:1011-1060): the mask runs in place over HBM
+    // (k_mask_r), then HPCP reads the masked spectrogram (DESIGN.md §4 on the fused variant)
+    const bool use_log = cfg_.enable_key_log_frequency;  // :1062-1095
+    const bool tuned = cfg_.enable_key_tuning_compensation && !use_log;
+    const bool whiten = cfg_.enable_key_hpcp_whitening && cfg_.key_hpcp_whitening_smooth_bins >= 3;
+    // the default key path (harmonic mask, plain HPCP, nothing else reading the masked
+    // spectrogram): the mask stores only HPCP's peak band and folds the frame energies in
+    // 64-bin blocks (k_mask_rp / k_hpcp_band); SDSP_KEY_EXACT_ENERGY builds
+    // keep the reference's one sequential energy sum (k_mask_r / k_hpcp)
+    KeyCond kc;
+    HpcpParams& hp = kc.hp;
+    hp.B = B8;
+    hp.stride = ks_;
+    key_peak_band(cfg_, sr_, &hp.pk_lo, &hp.pk_hi);
+    hp.K = (int)std::max<uint64_t>(cfg_.key_hpcp_peaks_per_frame, 1);
+    hp.hmax = (int)std::max<uint64_t>(cfg_.key_hpcp_num_harmonics, 1);
+    hp.p = sd_clampf(cfg_.key_hpcp_mag_power, 0.05f, 1.0f);
+    // sdsp_debug_key_energy_blocked answers the same; exact_energy_: the rerun of near-decision tracks
+    // exact_energy_ on the same configurations (the rerun): the band path's mask storing every
+    // bin (its masked values are k_mask_r's, bit for bit, at less cost), then k_hpcp's one
+    // sequential energy sum; the block sums it also writes go unused
+    const bool blocked = key_energy_blocked(cfg_, sr_);
+    const bool band = kc.band = blocked && !exact_energy_;
+    float* d_part = kc.d_part = blocked ? c_.dev<float>("E.kpart", total8 * (uint64_t)((B8 + 63) / 64)) : nullptr;
+    if (blocked) {
+        kc.st_lo = band ? hp.pk_lo - 1 : 0;
+        kc.st_hi = band ? hp.pk_hi + 1 : B8 - 1;
+        launch_mask_band(mags8, ks_, B8, d_kpfx, d_kid, NK, cfg_.key_harmonic_mask_power, kc.st_lo, kc.st_hi, d_part,
+                         total8, st2);
+    } else if (cfg_.enable_key_hpss_harmonic) {
+        const KeyHpssParams kh = key_hpss_params(cfg_, sr_, B8, fres8, ks_);
+        if (kh.nb > 0) {  // an empty band returns the spectrogram unchanged (extractor.rs:1408-1410)
+            std::vector<uint64_t> moff(1, 0), mt(1, 0), at(1, 0);
+            for (int k = 0; k < NK; k++) {
+                const uint64_t F8 = kpfx[(size_t)k + 1] - kpfx[(size_t)k];
+                const uint64_t nds = (F8 + (uint64_t)kh.step - 1) / (uint64_t)kh.step;
+                moff.push_back(moff.back() + nds * (uint64_t)kh.nb);
+                mt.push_back(mt.back() + ((nds + KH_TILE_FRAMES - 1) / KH_TILE_FRAMES) *
+                                             (((uint64_t)kh.nb + KH_TILE_BINS - 1) / KH_TILE_BINS));
+                at.push_back(at.back() + (F8 + KH_APPLY_FRAMES - 1) / KH_APPLY_FRAMES);
+            }
+            uint64_t* d_moff = c_.up(EP + "kh_off", moff);
+            uint64_t* d_mt = c_.up(EP + "kh_mt", mt);
+            uint64_t* d_at = c_.up(EP + "kh_at", at);
+            float* d_kmask = c_.dev<float>("E.kh_mask", std::max<uint64_t>(moff.back(), 1));
+            // the uploads are on the main stream
+            kt.mark(9);
+            SDSP_HIP_CHECK(hipStreamWaitEvent(st2, kt.ev[9], 0));
+            launch_key_hpss(mags8, d_kpfx, d_mt, mt.back(), d_at, at.back(), d_moff, d_kid, NK, kh, d_kmask, st2);
+        }
+    } else if (cfg_.enable_key_harmonic_mask)
+        launch_mask(mags8, ks_, B8, d_kpfx, d_kid, NK, (int)cfg_.key_spectrogram_smooth_margin,
+                    cfg_.key_harmonic_mask_power, st2);
+    else if (cfg_.enable_key_spectrogram_time_smoothing)
+        launch_mask(mags8, ks_, B8, d_kpfx, d_kid, NK, (int)cfg_.key_spectrogram_smooth_margin,
+                    cfg_.key_harmonic_mask_power, st2, true);
+    // tuning offset per track (:1097-1119)
+    if (tuned) {
+        TuningParams tp = tuning_params(cfg_, sr_, B8, fres8, ks_);
+        d_tune = kc.d_tune = c_.dev<float>("E.tune", (size_t)NK);
+        launch_tuning(mags8, d_kpfx, d_kid, NK, tp, d_tune, st2);
+        SDSP_HIP_CHECK(hipGetLastError());
+    }
+    float* d_chroma = kc.d_chroma = c_.dev<float>("E.chroma", total8 * 12);
+    float* d_energy = kc.d_energy = c_.dev<float>("E.energy", total8);
+    float* d_edel = nullptr;  // the band path's per-frame energy bounds (the vote's certificate)
+    // the previous sub-batch's key vote (stream3) reads E.chroma / E.energy: the producers
+    // below wait for it (an event never recorded counts as complete)
+    // (a nested rerun has its own "X." buffers and runs in order on the main stream)
+    if (!nested_) SDSP_HIP_CHECK(hipStreamWaitEvent(st2, d_.vote_done, 0));
+    if (use_log) {  // :1120-1131
+        const ChromaParams cp = chroma_params(cfg_, sr_, 1, B8, fres8, ks_);
+        launch_chroma(1, mags8, d_kpfx, d_ktile, d_kid, NK, ktile.back(), cp, nullptr, d_chroma, d_energy, st2);
+    } else if (cfg_.enable_key_hpcp && (d_tune || whiten || cfg_.enable_key_hpcp_bass_blend)) {  // :1133-1168
+        const HpcpXParams hx = hpcp_x_params(cfg_, sr_, B8, fres8, whiten, ks_);
+        launch_hpcp_x(mags8, d_kpfx, d_ktile, d_kid, NK, ktile.back(), hx, d_tune, d_chroma, d_energy, st2);
+    } else if (cfg_.enable_key_hpcp) {
+        std::vector<HarmEntry> ht =
+            harm_table(B8, sr_, KFS, cfg_.soft_mapping_sigma, hp.hmax, cfg_.key_hpcp_harmonic_decay);
+        HarmEntry* d_ht = c_.up(EP + "harm", ht);
+        kc.d_ht = d_ht;
+        // the table upload is queued on the main stream: order the key stream after it
+        kt.mark(10);
+        SDSP_HIP_CHECK(hipStreamWaitEvent(st2, kt.ev[10], 0));
+        if (band) {
+            d_edel = kc.d_edel = c_.dev<float>("E.edel", total8);
+            launch_hpcp_band(mags8, d_kpfx, d_ktile, d_kid, NK, ktile.back(), hp, d_ht, d_part, total8, d_chroma,
+                             d_energy, d_edel, st2);
+        }
+        else
+            launch_hpcp(mags8, d_kpfx, d_ktile, d_kid, NK, ktile.back(), hp, d_ht, d_chroma, d_energy, st2);
+    } else {  // :1169-1197 (the tuned variant only when |offset| > 1e-6)
+        const ChromaParams cp = chroma_params(cfg_, sr_, 0, B8, fres8, ks_);
+        launch_chroma(0, mags8, d_kpfx, d_ktile, d_kid, NK, ktile.back(), cp, d_tune, d_chroma, d_energy, st2);
+    }
+    SDSP_HIP_CHECK(hipGetLastError());
+    return kc;
+}
+
+// sdsp_debug_tempo_stages: tempo_pass through its mags_in / fmax_in path (the percussive
+// fallback's), then the stage buffers and the tempogram lists back to the host.
+void Pipeline::debug_tempo_stages(const float* host_mags, const uint64_t* frames, uint64_t n_tracks, int hop,
+                                  sdsp_debug_tempo_out* out) {
+    std::string why = unsupported(cfg_, sr_);
+    if (why.empty()) why = unsupported_sr(cfg_, sr_);
+    if (!why.empty()) throw HipError(why);
+    TempoPassIn in;
+    in.hop = hop;
+    in.samples = nullptr;
+    uint64_t total = 0;
+    for (uint64_t t = 0; t < n_tracks; t++) {
+        in.src_off.push_back(0);
+        in.gain_h.push_back(1.0f);
+        in.n_trim.push_back((uint64_t)fs_ + (frames[t] - 1) * (uint64_t)hop);  // frames[t] frames exactly
+        total += frames[t];
+    }
+    in.want_onsets = true;
+    in.top_n = 10;
+    in.cand_cap = 10;
+    in.gate = 0;
+    std::vector<float> fmax((size_t)total);
+    for (uint64_t r = 0; r < total; r++) {  // the exact row maximum
+        float m = 0.0f;
+        for (int b = 0; b < nb_; b++) m = std::max(m, host_mags[r * (uint64_t)nb_ + (uint64_t)b]);
+        fmax[(size_t)r] = m;
+    }
+    float* d_mags = c_.dev<float>("P.in", total * (uint64_t)s2_);
+    SDSP_HIP_CHECK(hipMemsetAsync(d_mags, 0, total * (uint64_t)s2_ * sizeof(float), d_.stream));
+    SDSP_HIP_CHECK(hipMemcpy2DAsync(d_mags, (size_t)s2_ * sizeof(float), host_mags, (size_t)nb_ * sizeof(float),
+                                    (size_t)nb_ * sizeof(float), total, hipMemcpyHostToDevice, d_.stream));
+    in.mags_in = d_mags;
+    in.fmax_in = c_.up("P.inmax", fmax);
+    TempoStageDbg g;
+    in.dbg = &g;
+    TempoPassOut po;
+    tempo_pass("B.", in, po);
+    out->n_mels = g.fp.n_mels;
+    out->NB = g.NB;
+    for (int v = 0; v < 4; v++) {
+        out->bs[v] = g.fp.bs[v];
+        out->be[v] = g.fp.be[v];
+        out->band_on[v] = g.fp.band_on[v];
+    }
+    for (int v = 0; v < NVAR; v++) out->present[v] = g.present[v];
+    if ((uint32_t)g.fp.n_mels > out->mel_cap || (uint32_t)g.NB > out->acf_cap) throw std::invalid_argument("capacity");
+    for (int k : g.fft_k)
+        if ((uint32_t)k > out->fft_cap) throw std::invalid_argument("capacity");
+    auto get = [&](const float* d, float* h, size_t n) {
+        if (n) SDSP_HIP_CHECK(hipMemcpyAsync(h, d, n * sizeof(float), hipMemcpyDeviceToHost, d_.stream));
+    };
+    get(po.E, out->E, 4 * (size_t)total);
+    get(po.H, out->H, 4 * (size_t)total);
+    get(po.SFX, out->SFX, 4 * (size_t)total);
+    get(po.SFO, out->SFO, (size_t)total);
+    get(po.MEL, out->MEL, (size_t)g.fp.n_mels * (size_t)total);
+    get(po.nov, out->nov, NVAR * (size_t)total);
+    get(po.nov_sum, out->nov_sum, NVAR * (size_t)n_tracks);
+    const size_t n_it = g.items.size();
+    uint64_t n_fft = 0;
+    for (size_t i = 0; i < n_it; i++) n_fft = std::max(n_fft, g.fft_off[i] + (uint64_t)g.fft_k[i]);
+    const std::vector<float> ab = c_.down(g.acf_bpm, n_it * (size_t)g.NB), as = c_.down(g.acf_str, n_it * (size_t)g.NB);
+    const std::vector<float> fb = c_.down(g.fft_bpm, (size_t)n_fft), fw = c_.down(g.fft_pow, (size_t)n_fft);
+    for (uint64_t k = 0; k < n_tracks * NVAR; k++) out->acf_n[k] = out->fft_n[k] = 0;
+    for (size_t i = 0; i < n_it; i++) {
+        const size_t slot = (size_t)g.items[i];
+        float* a = out->acf + slot * out->acf_cap * 2;
+        float* f = out->fft + slot * out->fft_cap * 2;
+        for (int j = 0; j < g.NB; j++) {
+            a[2 * j] = ab[i * (size_t)g.NB + (size_t)j];
+            a[2 * j + 1] = as[i * (size_t)g.NB + (size_t)j];
+        }
+        for (int j = 0; j < g.fft_k[i]; j++) {
+            f[2 * j] = fb[(size_t)g.fft_off[i] + (size_t)j];
+            f[2 * j + 1] = fw[(size_t)g.fft_off[i] + (size_t)j];
+        }
+        out->acf_n[slot] = g.NB;
+        out->fft_n[slot] = g.fft_k[i];
+    }
+}
+
+// sdsp_debug_key_stages: key_condition (and, for mode 1, tail_exact) over uploaded key spectrograms.
+// exact_energy_ selects mode 2's sequence, as it does for the nested rerun.
+void Pipeline::debug_key_stages(const float* host_mags, const uint64_t* frames, uint64_t n_tracks, int mode,
+                                float* masked, float* chroma, float* energy, float* edel, int32_t info[4]) {
+    std::string why = unsupported(cfg_, sr_);
+    if (why.empty()) why = unsupported_sr(cfg_, sr_);
+    if (!why.empty()) throw HipError(why);
+    if ((mode == 2) != exact_energy_) throw HipError("debug_key_stages: mode 2 runs on an exact-energy pipeline");
+    if (mode != 0 && !key_energy_blocked(cfg_, sr_)) throw std::invalid_argument("modes 1 and 2 need the band path");
+    const int NK = (int)n_tracks, B8 = kfs_ / 2 + 1;
+    std::vector<uint64_t> kpfx(1, 0), ktile(1, 0);
+    std::vector<int> kid((size_t)NK);
+    for (int k = 0; k < NK; k++) {
+        kpfx.push_back(kpfx.back() + frames[k]);
+        ktile.push_back(ktile.back() + (frames[k] + HP_FRAMES - 1) / HP_FRAMES);
+        kid[(size_t)k] = k;
+    }
+    const uint64_t total8 = kpfx.back();
+    const std::string EP = "E0.";
+    hipStream_t st = d_.stream;
+    uint64_t* d_kpfx = c_.up(EP + "kpfx", kpfx);
+    uint64_t* d_ktile = c_.up(EP + "ktile", ktile);
+    int* d_kid = c_.up(EP + "kid", kid);
+    float* mags8 = c_.dev<float>("E.mags8", total8 * (uint64_t)ks_);
+    SDSP_HIP_CHECK(hipMemsetAsync(mags8, 0, total8 * (uint64_t)ks_ * sizeof(float), st));
+    SDSP_HIP_CHECK(hipMemcpy2DAsync(mags8, (size_t)ks_ * sizeof(float), host_mags, (size_t)B8 * sizeof(float),
+                                    (size_t)B8 * sizeof(float), total8, hipMemcpyHostToDevice, st));
+    Timers kt;
+    kt.init(d_);
+    const KeyCond kc = key_condition(EP, mags8, kpfx, ktile, d_kpfx, d_ktile, d_kid, st, kt);
+    if (mode == 1) {
+        if (!kc.band || !kc.d_ht) throw HipError("debug_key_stages: mode 1 without the band path");
+        KeyTail t;
+        tail_buffers(t, kc, mags8, d_kpfx, total8);
+        tail_exact(t, d_kid, NK, d_ktile, ktile.back(), st);
+    }
+    info[0] = kc.st_lo;
+    info[1] = kc.st_hi;
+    info[2] = kc.band ? 1 : 0;
+    info[3] = B8;
+    SDSP_HIP_CHECK(hipMemcpy2DAsync(masked, (size_t)B8 * sizeof(float), mags8, (size_t)ks_ * sizeof(float),
+                                    (size_t)B8 * sizeof(float), total8, hipMemcpyDeviceToHost, st));
+    SDSP_HIP_CHECK(hipMemcpyAsync(chroma, kc.d_chroma, total8 * 12 * sizeof(float), hipMemcpyDeviceToHost, st));
+    SDSP_HIP_CHECK(hipMemcpyAsync(energy, kc.d_energy, total8 * sizeof(float), hipMemcpyDeviceToHost, st));
+    if (edel && kc.d_edel && mode == 0)
+        SDSP_HIP_CHECK(hipMemcpyAsync(edel, kc.d_edel, total8 * sizeof(float), hipMemcpyDeviceToHost, st));
+    c_.sync();
 }
 
 struct HostTrace {
@@ -1801,99 +2122,12 @@ void Pipeline::sub_batch(const float* d_samples, const std::vector<uint64_t>& in
                     c_.dev<uint32_t>("E.redo", total8 + 1));
         SDSP_HIP_CHECK(hipGetLastError());
         kt.mark(1, st2);
-        // key spectrogram conditioning (src/lib.rs:1011-1060): the mask runs in place over HBM
-        // (k_mask_r), then HPCP reads the masked spectrogram (DESIGN.md §4 on the fused variant)
-        const bool use_log = cfg_.enable_key_log_frequency;  // :1062-1095
-        const bool tuned = cfg_.enable_key_tuning_compensation && !use_log;
-        const bool whiten = cfg_.enable_key_hpcp_whitening && cfg_.key_hpcp_whitening_smooth_bins >= 3;
-        // the default key path (harmonic mask, plain HPCP, nothing else reading the masked
-        // spectrogram): the mask stores only HPCP's peak band and folds the frame energies in
-        // 64-bin blocks (k_mask_rp / k_hpcp_band); SDSP_KEY_EXACT_ENERGY builds
-        // keep the reference's one sequential energy sum (k_mask_r / k_hpcp)
-        HpcpParams hp{};
-        hp.B = B8;
-        hp.stride = ks_;
-        key_peak_band(cfg_, sr_, &hp.pk_lo, &hp.pk_hi);
-        hp.K = (int)std::max<uint64_t>(cfg_.key_hpcp_peaks_per_frame, 1);
-        hp.hmax = (int)std::max<uint64_t>(cfg_.key_hpcp_num_harmonics, 1);
-        hp.p = sd_clampf(cfg_.key_hpcp_mag_power, 0.05f, 1.0f);
-        // sdsp_debug_key_energy_blocked answers the same; exact_energy_: the rerun of near-decision tracks
-        // exact_energy_ on the same configurations (the rerun): the band path's mask storing every
-        // bin (its masked values are k_mask_r's, bit for bit, at less cost), then k_hpcp's one
-        // sequential energy sum; the block sums it also writes go unused
-        const bool blocked = key_energy_blocked(cfg_, sr_);
-        const bool band = blocked && !exact_energy_;
-        float* d_part = blocked ? c_.dev<float>("E.kpart", total8 * (uint64_t)((B8 + 63) / 64)) : nullptr;
-        if (blocked) {
-            launch_mask_band(mags8, ks_, B8, d_kpfx, d_kid, NK, cfg_.key_harmonic_mask_power, band ? hp.pk_lo - 1 : 0,
-                             band ? hp.pk_hi + 1 : B8 - 1, d_part, total8, st2);
-        } else if (cfg_.enable_key_hpss_harmonic) {
-            const KeyHpssParams kh = key_hpss_params(cfg_, sr_, B8, fres8, ks_);
-            if (kh.nb > 0) {  // an empty band returns the spectrogram unchanged (extractor.rs:1408-1410)
-                std::vector<uint64_t> moff(1, 0), mt(1, 0), at(1, 0);
-                for (int k = 0; k < NK; k++) {
-                    const uint64_t F8 = kpfx[(size_t)k + 1] - kpfx[(size_t)k];
-                    const uint64_t nds = (F8 + (uint64_t)kh.step - 1) / (uint64_t)kh.step;
-                    moff.push_back(moff.back() + nds * (uint64_t)kh.nb);
-                    mt.push_back(mt.back() + ((nds + KH_TILE_FRAMES - 1) / KH_TILE_FRAMES) *
-                                                 (((uint64_t)kh.nb + KH_TILE_BINS - 1) / KH_TILE_BINS));
-                    at.push_back(at.back() + (F8 + KH_APPLY_FRAMES - 1) / KH_APPLY_FRAMES);
-                }
-                uint64_t* d_moff = c_.up(EP + "kh_off", moff);
-                uint64_t* d_mt = c_.up(EP + "kh_mt", mt);
-                uint64_t* d_at = c_.up(EP + "kh_at", at);
-                float* d_kmask = c_.dev<float>("E.kh_mask", std::max<uint64_t>(moff.back(), 1));
-                // the uploads are on the main stream
-                kt.mark(9);
-                SDSP_HIP_CHECK(hipStreamWaitEvent(st2, kt.ev[9], 0));
-                launch_key_hpss(mags8, d_kpfx, d_mt, mt.back(), d_at, at.back(), d_moff, d_kid, NK, kh, d_kmask, st2);
-            }
-        } else if (cfg_.enable_key_harmonic_mask)
-            launch_mask(mags8, ks_, B8, d_kpfx, d_kid, NK, (int)cfg_.key_spectrogram_smooth_margin,
-                        cfg_.key_harmonic_mask_power, st2);
-        else if (cfg_.enable_key_spectrogram_time_smoothing)
-            launch_mask(mags8, ks_, B8, d_kpfx, d_kid, NK, (int)cfg_.key_spectrogram_smooth_margin,
-                        cfg_.key_harmonic_mask_power, st2, true);
-        // tuning offset per track (:1097-1119)
-        if (tuned) {
-            TuningParams tp = tuning_params(cfg_, sr_, B8, fres8, ks_);
-            d_tune = c_.dev<float>("E.tune", (size_t)NK);
-            launch_tuning(mags8, d_kpfx, d_kid, NK, tp, d_tune, st2);
-            SDSP_HIP_CHECK(hipGetLastError());
-        }
-        float* d_chroma = c_.dev<float>("E.chroma", total8 * 12);
-        float* d_energy = c_.dev<float>("E.energy", total8);
-        float* d_edel = nullptr;  // the band path's per-frame energy bounds (the vote's certificate)
-        // the previous sub-batch's key vote (stream3) reads E.chroma / E.energy: the producers
-        // below wait for it (an event never recorded counts as complete)
-        // (a nested rerun has its own "X." buffers and runs in order on the main stream)
-        if (!nested_) SDSP_HIP_CHECK(hipStreamWaitEvent(st2, d_.vote_done, 0));
-        if (use_log) {  // :1120-1131
-            const ChromaParams cp = chroma_params(cfg_, sr_, 1, B8, fres8, ks_);
-            launch_chroma(1, mags8, d_kpfx, d_ktile, d_kid, NK, ktile.back(), cp, nullptr, d_chroma, d_energy, st2);
-        } else if (cfg_.enable_key_hpcp && (d_tune || whiten || cfg_.enable_key_hpcp_bass_blend)) {  // :1133-1168
-            const HpcpXParams hx = hpcp_x_params(cfg_, sr_, B8, fres8, whiten, ks_);
-            launch_hpcp_x(mags8, d_kpfx, d_ktile, d_kid, NK, ktile.back(), hx, d_tune, d_chroma, d_energy, st2);
-        } else if (cfg_.enable_key_hpcp) {
-            std::vector<HarmEntry> ht =
-                harm_table(B8, sr_, KFS, cfg_.soft_mapping_sigma, hp.hmax, cfg_.key_hpcp_harmonic_decay);
-            HarmEntry* d_ht = c_.up(EP + "harm", ht);
-            ktail.d_ht = d_ht;
-            // the table upload is queued on the main stream: order the key stream after it
-            kt.mark(10);
-            SDSP_HIP_CHECK(hipStreamWaitEvent(st2, kt.ev[10], 0));
-            if (band) {
-                d_edel = c_.dev<float>("E.edel", total8);
-                launch_hpcp_band(mags8, d_kpfx, d_ktile, d_kid, NK, ktile.back(), hp, d_ht, d_part, total8, d_chroma,
-                                 d_energy, d_edel, st2);
-            }
-            else
-                launch_hpcp(mags8, d_kpfx, d_ktile, d_kid, NK, ktile.back(), hp, d_ht, d_chroma, d_energy, st2);
-        } else {  // :1169-1197 (the tuned variant only when |offset| > 1e-6)
-            const ChromaParams cp = chroma_params(cfg_, sr_, 0, B8, fres8, ks_);
-            launch_chroma(0, mags8, d_kpfx, d_ktile, d_kid, NK, ktile.back(), cp, d_tune, d_chroma, d_energy, st2);
-        }
-        SDSP_HIP_CHECK(hipGetLastError());
+        const KeyCond kc = key_condition(EP, mags8, kpfx, ktile, d_kpfx, d_ktile, d_kid, st2, kt);
+        const bool band = kc.band;
+        float* const d_chroma = kc.d_chroma;
+        float* const d_energy = kc.d_energy;
+        float* const d_edel = kc.d_edel;
+        d_tune = kc.d_tune;
         std::vector<float> tpl(576);
         key_templates(tpl.data());
         d_tpl = c_.up(EP + "tpl", tpl);
@@ -1931,20 +2165,11 @@ void Pipeline::sub_batch(const float* d_samples, const std::vector<uint64_t>& in
         float* d_w = c_.dev<float>("E.weights", total8);
         float* d_sscr = c_.dev<float>("E.segscr", std::max<uint64_t>(kseg.back(), 1));
         d_kout = c_.dev<KeyOut>(EP + "kout", (size_t)NK);
-        if (band && ktail.d_ht) {
+        if (band && kc.d_ht) {
             ktail.ok = true;
-            ktail.mags8 = mags8;
-            ktail.d_kpfx = d_kpfx;
+            tail_buffers(ktail, kc, mags8, d_kpfx, total8);
             ktail.kpfx = kpfx;
             ktail.kseg = kseg;
-            ktail.d_part = d_part;
-            ktail.total8 = total8;
-            ktail.st_lo = hp.pk_lo - 1;
-            ktail.st_hi = hp.pk_hi + 1;
-            ktail.B8 = B8;
-            ktail.hp = hp;
-            ktail.d_chroma = d_chroma;
-            ktail.d_energy = d_energy;
             ktail.d_cs = d_cs;
             ktail.d_w = d_w;
             ktail.d_sscr = d_sscr;
@@ -2776,6 +3001,38 @@ std::vector<int> device_list_override(int ndev) {
 }  // namespace
 }  // namespace sdsp
 
+// Stage probes (include/stratum_hip_debug.h): a probe pipeline on the device context, whose "D."
+// buffers are released again, so an analysis call finds the context as it left it.
+namespace sdsp {
+namespace {
+template <class F>
+int32_t run_stage_probe(const char* name, int32_t device, F f) {
+    try {
+        DeviceCtx& d = device_ctx(device);
+        std::lock_guard<std::mutex> lk(d.mu);
+        SDSP_HIP_CHECK(hipSetDevice(device));
+        int32_t rc = SDSP_OK;
+        try {
+            f(d);
+        } catch (const std::invalid_argument& e) {
+            std::fprintf(stderr, "%s: %s\n", name, e.what());
+            rc = SDSP_ERR_INVALID_INPUT;
+        } catch (const std::exception& e) {
+            std::fprintf(stderr, "%s: %s\n", name, e.what());
+            rc = SDSP_ERR_PROCESSING;
+        }
+        for (hipStream_t s : d.own) (void)hipStreamSynchronize(s);
+        for (auto it = d.bufs.begin(); it != d.bufs.end();)
+            it = it->first.compare(0, 2, "D.") == 0 ? d.bufs.erase(it) : std::next(it);
+        return rc;
+    } catch (const std::exception& e) {
+        std::fprintf(stderr, "%s: %s\n", name, e.what());
+        return SDSP_ERR_PROCESSING;
+    }
+}
+}  // namespace
+}  // namespace sdsp
+
 
 extern "C" {
 
@@ -2821,6 +3078,46 @@ int32_t sdsp_debug_last_key_near(int32_t device, uint8_t* out, uint64_t n) {
     } catch (const std::exception&) {
         return SDSP_ERR_PROCESSING;
     }
+}
+
+// Tracks the last call on `device` reran in place (Pipeline::rerun_tail).
+int32_t sdsp_debug_last_tail_reruns(int32_t device, uint64_t* n_tracks) {
+    try {
+        if (!n_tracks) return SDSP_ERR_INVALID_INPUT;
+        DeviceCtx& d = device_ctx(device);
+        std::lock_guard<std::mutex> lk(d.mu);
+        *n_tracks = d.last_tail_reruns;
+        return SDSP_OK;
+    } catch (const std::exception&) {
+        return SDSP_ERR_PROCESSING;
+    }
+}
+
+int32_t sdsp_debug_tempo_stages(const float* host_mags, const uint64_t* frames, uint64_t n_tracks, uint32_t sample_rate,
+                                uint32_t hop, const sdsp_config* cfg, sdsp_debug_tempo_out* out, int32_t device) {
+    if (!host_mags || !frames || !cfg || !out || n_tracks == 0 || n_tracks > (1u << 20) || sample_rate == 0 || hop == 0 ||
+        hop > 8192)
+        return SDSP_ERR_INVALID_INPUT;
+    for (uint64_t t = 0; t < n_tracks; t++)
+        if (frames[t] == 0 || frames[t] > (1u << 24)) return SDSP_ERR_INVALID_INPUT;
+    return run_stage_probe("sdsp_debug_tempo_stages", device, [&](DeviceCtx& d) {
+        Pipeline p(d, *cfg, sample_rate, SDSP_STAGES_FULL, false, false, false, true);
+        p.debug_tempo_stages(host_mags, frames, n_tracks, (int)hop, out);
+    });
+}
+
+int32_t sdsp_debug_key_stages(const float* host_mags, const uint64_t* frames, uint64_t n_tracks, uint32_t sample_rate,
+                              const sdsp_config* cfg, int32_t mode, float* masked, float* chroma, float* energy,
+                              float* edel, int32_t info[4], int32_t device) {
+    if (!host_mags || !frames || !cfg || !masked || !chroma || !energy || !info || n_tracks == 0 ||
+        n_tracks > (1u << 20) || sample_rate == 0 || mode < 0 || mode > 2)
+        return SDSP_ERR_INVALID_INPUT;
+    for (uint64_t t = 0; t < n_tracks; t++)
+        if (frames[t] == 0 || frames[t] > (1u << 24)) return SDSP_ERR_INVALID_INPUT;
+    return run_stage_probe("sdsp_debug_key_stages", device, [&](DeviceCtx& d) {
+        Pipeline p(d, *cfg, sample_rate, SDSP_STAGES_FULL, mode == 2, false, false, true);
+        p.debug_key_stages(host_mags, frames, n_tracks, mode, masked, chroma, energy, edel, info);
+    });
 }
 
 // Host buffers: chunks of whole tracks (up to SDSP_BATCH_CHUNK_TRACKS tracks, default

@@ -87,6 +87,7 @@ struct DeviceCtx {
     std::map<std::string, std::unique_ptr<DevBuf>> bufs;
     sdsp_stage_times last{};
     std::vector<uint8_t> last_near;  // per track of the last call: its key vote was near a decision (rerun)
+    uint64_t last_tail_reruns = 0;   // tracks the last call reran in place (Pipeline::rerun_tail)
     DevBuf& buf(const std::string& name) {
         auto& b = bufs[name];
         if (!b) {

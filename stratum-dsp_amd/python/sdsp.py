@@ -545,3 +545,121 @@ def debug_stft(x, nfft, hop, gain=1.0, device=0):
     if st != 0:
         raise AnalysisError(st, "debug_stft failed")
     return out, fmax
+
+
+class SdspDebugTempoOut(C.Structure):
+    """sdsp_debug_tempo_out (include/stratum_hip_debug.h)."""
+    _fields_ = ([(n, C.POINTER(C.c_float)) for n in ("E", "H", "SFX", "SFO", "MEL", "nov", "nov_sum", "acf", "fft")] +
+                [("acf_n", C.POINTER(C.c_int32)), ("fft_n", C.POINTER(C.c_int32)),
+                 ("mel_cap", C.c_uint32), ("acf_cap", C.c_uint32), ("fft_cap", C.c_uint32),
+                 ("n_mels", C.c_int32), ("NB", C.c_int32),
+                 ("bs", C.c_int32 * 4), ("be", C.c_int32 * 4), ("band_on", C.c_int32 * 4), ("present", C.c_int32 * 5)])
+
+
+def _packed_specs(specs, bins=None):
+    arrs = [np.ascontiguousarray(s, dtype=np.float32) for s in specs]
+    if not arrs or any(a.ndim != 2 or a.shape[0] < 1 or a.shape[1] != arrs[0].shape[1] for a in arrs):
+        raise ValueError("tracks are (frames >= 1, bins) arrays of one width")
+    if bins is not None and arrs[0].shape[1] != bins:
+        raise ValueError(f"rows of {bins} bins expected")
+    frames = np.array([a.shape[0] for a in arrs], np.uint64)
+    return np.ascontiguousarray(np.concatenate(arrs, axis=0)), frames
+
+
+VARIANTS = ("full", "low", "mid", "high", "mel")
+
+
+def debug_tempo_stages(specs, sample_rate=44100, hop=512, config=None, device=0):
+    """The tempo pass's stages over host magnitude spectrograms (sdsp_debug_tempo_stages): a list of
+    tracks, each (frames, frame_size / 2 + 1).  Returns (meta, tracks): meta holds bs, be, band_on,
+    present, n_mels, NB; tracks[t] holds E, H (4, F), SFX (4, F - 1), SFO (F - 1), MEL (n_mels, F),
+    nov {variant: F - 1 values}, nov_sum {variant: value}, acf / fft {variant: (n, 2) array of
+    (bpm, value) in the kernels' order} for the present variants."""
+    cfg = config if config is not None else default_config()
+    x, frames = _packed_specs(specs, int(cfg.frame_size) // 2 + 1)
+    T, total = len(frames), int(frames.sum())
+    mel_cap, acf_cap = 48, 512
+    fft_cap = max(1 << max(int(f) - 2, 0).bit_length() for f in frames) // 2 + 1
+    f32 = lambda *shape: np.zeros(shape, np.float32)
+    buf = dict(E=f32(4, total), H=f32(4, total), SFX=f32(4, total), SFO=f32(total), MEL=f32(mel_cap, total),
+               nov=f32(5, total), nov_sum=f32(5, T), acf=f32(T, 5, acf_cap, 2), fft=f32(T, 5, fft_cap, 2))
+    acf_n, fft_n = np.zeros((T, 5), np.int32), np.zeros((T, 5), np.int32)
+    o = SdspDebugTempoOut(mel_cap=mel_cap, acf_cap=acf_cap, fft_cap=fft_cap)
+    for k, v in buf.items():
+        setattr(o, k, _fp(v))
+    i32p = C.POINTER(C.c_int32)
+    o.acf_n, o.fft_n = acf_n.ctypes.data_as(i32p), fft_n.ctypes.data_as(i32p)
+    f = lib().sdsp_debug_tempo_stages
+    f.argtypes = [C.POINTER(C.c_float), C.POINTER(C.c_uint64), C.c_uint64, C.c_uint32, C.c_uint32, C.POINTER(SdspConfig),
+                  C.POINTER(SdspDebugTempoOut), C.c_int32]
+    f.restype = C.c_int32
+    st = f(_fp(x), frames.ctypes.data_as(C.POINTER(C.c_uint64)), T, sample_rate, hop, C.byref(cfg), C.byref(o), device)
+    if st != 0:
+        raise AnalysisError(st, "debug_tempo_stages failed")
+    meta = dict(bs=list(o.bs), be=list(o.be), band_on=list(o.band_on), present=list(o.present), n_mels=o.n_mels,
+                NB=o.NB)
+    tracks, g0 = [], 0
+    for t in range(T):
+        F = int(frames[t])
+        sl, pr = slice(g0, g0 + F), slice(g0, g0 + F - 1)
+        on = [v for v in range(5) if o.present[v] and F >= 2]
+        tracks.append(dict(
+            E=buf["E"][:, sl].copy(), H=buf["H"][:, sl].copy(), SFX=buf["SFX"][:, pr].copy(), SFO=buf["SFO"][pr].copy(),
+            MEL=buf["MEL"][:o.n_mels, sl].copy(),
+            nov={VARIANTS[v]: buf["nov"][v, pr].copy() for v in on},
+            nov_sum={VARIANTS[v]: buf["nov_sum"][v, t] for v in on},
+            acf={VARIANTS[v]: buf["acf"][t, v, :acf_n[t, v]].copy() for v in on},
+            fft={VARIANTS[v]: buf["fft"][t, v, :fft_n[t, v]].copy() for v in on}))
+        g0 += F
+    return meta, tracks
+
+
+def debug_key_stages(specs, sample_rate=44100, config=None, mode=0, device=0):
+    """The key path's conditioning and chroma over host key spectrograms (sdsp_debug_key_stages;
+    mode 0 the configured path, 1 the in-place rerun's sequence, 2 the nested rerun's).  Returns
+    (info, tracks): info holds st_lo, st_hi, band, bins; tracks[t] holds masked (F, bins), chroma
+    (F, 12), energy (F) and, on mode 0's band path, edel (F)."""
+    cfg = config if config is not None else default_config()
+    x, frames = _packed_specs(specs)
+    T, total, bins = len(frames), int(frames.sum()), x.shape[1]
+    masked, chroma = np.zeros((total, bins), np.float32), np.zeros((total, 12), np.float32)
+    energy, edel = np.zeros(total, np.float32), np.full(total, np.nan, np.float32)
+    info = (C.c_int32 * 4)()
+    f = lib().sdsp_debug_key_stages
+    fp = C.POINTER(C.c_float)
+    f.argtypes = [fp, C.POINTER(C.c_uint64), C.c_uint64, C.c_uint32, C.POINTER(SdspConfig), C.c_int32, fp, fp, fp, fp,
+                  C.POINTER(C.c_int32), C.c_int32]
+    f.restype = C.c_int32
+    if key_fft_bins(cfg) != bins:
+        raise ValueError(f"rows of {key_fft_bins(cfg)} bins expected")
+    st = f(_fp(x), frames.ctypes.data_as(C.POINTER(C.c_uint64)), T, sample_rate, C.byref(cfg), mode, _fp(masked),
+           _fp(chroma), _fp(energy), _fp(edel), info, device)
+    if st != 0:
+        raise AnalysisError(st, "debug_key_stages failed")
+    meta = dict(st_lo=info[0], st_hi=info[1], band=bool(info[2]), bins=info[3])
+    tracks, g0 = [], 0
+    for t in range(T):
+        sl = slice(g0, g0 + int(frames[t]))
+        d = dict(masked=masked[sl].copy(), chroma=chroma[sl].copy(), energy=energy[sl].copy())
+        if meta["band"] and mode == 0:
+            d["edel"] = edel[sl].copy()
+        tracks.append(d)
+        g0 += int(frames[t])
+    return meta, tracks
+
+
+def key_fft_bins(cfg):
+    """Bins per row of the key spectrogram: the override's frame size (>= 256), else frame_size."""
+    n = max(int(cfg.key_stft_frame_size), 256) if cfg.enable_key_stft_override else int(cfg.frame_size)
+    return n // 2 + 1
+
+
+def last_tail_reruns(device=0):
+    """Tracks the last analysis call reran in place (sdsp_debug_last_tail_reruns)."""
+    f = lib().sdsp_debug_last_tail_reruns
+    f.argtypes = [C.c_int32, C.POINTER(C.c_uint64)]
+    f.restype = C.c_int32
+    n = C.c_uint64()
+    if f(device, C.byref(n)) != 0:
+        raise RuntimeError("sdsp_debug_last_tail_reruns failed")
+    return int(n.value)

@@ -114,7 +114,10 @@ def test_tail_rerun_in_place_equals_nested(monkeypatch):
     """The last sub-batch's near-decision tracks are rerun in place (Pipeline::rerun_tail: the
     mask completed outside HPCP's band, the exact energy fold, the vote) instead of by a nested
     pipeline from the samples.  With the late key join off (SDSP_NO_KEY_DEFER) the same tracks take
-    the nested rerun; every result field must be identical, and so must the rerun count."""
+    the nested rerun; every result field must be identical, and so must the rerun count.  That the
+    in-place rerun ran, rather than returning early and leaving the tracks to the nested pipeline
+    (which gives the same results), is read from sdsp_debug_last_tail_reruns: the whole batch is one
+    sub-batch, so every near track is rerun in place in the default run and none without the late join."""
     n, L = 48, 180 * 44100
     buf = sdsp.DeviceBuffer(n * L)
     sdsp.generate_synthetic(buf.ptr, n, L, 44100, seed0=3000)
@@ -123,9 +126,13 @@ def test_tail_rerun_in_place_equals_nested(monkeypatch):
     got = sdsp.analyze_batch_device(buf.ptr, offs, lens, 44100)
     st = sdsp.stage_times()
     near = sdsp.last_key_near(n).copy()
+    tail = sdsp.last_tail_reruns()
     monkeypatch.setenv("SDSP_NO_KEY_DEFER", "1")
     ref = sdsp.analyze_batch_device(buf.ptr, offs, lens, 44100)
     st_ref = sdsp.stage_times()
+    tail_ref = sdsp.last_tail_reruns()
     assert (near != 0).sum() > 0 and st["key_reruns"] == st_ref["key_reruns"] == int((near != 0).sum())
+    assert tail > 0 and tail == int((near != 0).sum()), (tail, near)
+    assert tail_ref == 0, tail_ref
     for i in range(n):
         assert parity.result_digest(got[i]) == parity.result_digest(ref[i]), i

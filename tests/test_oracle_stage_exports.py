@@ -1,0 +1,119 @@
+"""The oracle's stage exports (oracle/units.py: tempo_stages, spectral_flux_curve, key_stages) pinned
+against exports that are already pinned.  The stage tests on the GPU (test_gpu_tempo_stages.py,
+test_gpu_key_stages.py) compare kernels with these exports, so the exports themselves must be the
+arithmetic the whole-track oracle runs: they are taken from inside tempogram_impl and from the key
+conditioning analyze calls, not restated.
+"""
+import numpy as np
+import pytest
+
+import oracle
+import synth
+import units
+
+
+def _spec(seed, frames, bins):
+    rng = np.random.default_rng(seed)
+    return (rng.random((frames, bins)) ** 4 * 50).astype(np.float32)
+
+
+def _bits(a):
+    return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
+
+
+def _same(a, b):
+    a, b = np.asarray(a, np.float32), np.asarray(b, np.float32)
+    return a.shape == b.shape and np.array_equal(_bits(a), _bits(b))
+
+
+@pytest.mark.parametrize("frames", [2, 3, 17, 65, 130])
+def test_full_variant_is_novelty_full(frames):
+    m = _spec(11 + frames, frames, 1025)
+    st = units.tempo_stages(m)
+    assert list(st) == ["full", "low", "mid", "high", "mel"]
+    assert _same(st["full"]["nov"], oracle.novelty_full(m))
+    assert (st["full"]["s"], st["full"]["e"]) == (0, 1025)
+    assert st["mel"]["melf"].shape == (frames, 40) and len(st["mel"]["nov"]) == frames - 1
+
+
+@pytest.mark.parametrize("frames", [2, 17, 65])
+def test_pieces_are_the_unit_novelties(frames):
+    """The full band's pieces are the unit exports: the normalised superflux, and the raw energies
+    and HFC whose normalised positive differences are energy_flux_novelty / hfc_novelty; the raw
+    superflux divided by its maximum is the normalised one."""
+    m = _spec(23 + frames, frames, 1025)
+    f = units.tempo_stages(m)["full"]
+    assert _same(f["sf"], units.superflux_novelty(m, 4))
+
+    def flux_norm(x):
+        d = np.maximum(x[1:] - x[:-1], np.float32(0))
+        mx = d.max() if d.size else np.float32(0)
+        return d / mx if mx > np.float32(1e-10) else d
+
+    assert _same(flux_norm(f["energy"]), units.energy_flux_novelty(m))
+    assert _same(flux_norm(f["hfc"]), units.hfc_novelty(m, 44100))
+    mx = f["sfx_raw"].max()
+    assert _same(f["sfx_raw"] / mx if mx > np.float32(1e-10) else f["sfx_raw"], f["sf"])
+    # the band variants' energies are the same fold over their own bins
+    st = units.tempo_stages(m)
+    for name in ("low", "mid", "high"):
+        s, e = st[name]["s"], st[name]["e"]
+        acc = np.zeros(frames, np.float32)
+        for b in range(s, e):
+            acc = acc + m[:, b] * m[:, b]
+        assert _same(acc, st[name]["energy"]), name
+
+
+def test_spectral_flux_curve_is_the_unit_novelty_before_normalisation():
+    m = _spec(5, 33, 1025)
+    c = units.spectral_flux_curve(m)
+    assert c.shape == (32,) and _same(c / c.max(), units.spectral_flux_novelty(m))
+    assert units.spectral_flux_curve(m[:1]).size == 0
+
+
+@pytest.mark.parametrize("opts", [{}, {"key_spectrogram_smooth_margin": 8}, {"key_harmonic_mask_power": 1.0},
+                                  {"enable_key_harmonic_mask": 0, "enable_key_spectrogram_time_smoothing": 1},
+                                  {"key_hpcp_peaks_per_frame": 8}])
+def test_key_stage_energies_are_the_sequential_fold(opts):
+    """The returned energies are the f32 sequential sum of squares of the returned masked rows
+    (extractor.rs:1133), and the default configuration's chroma is the pinned HPCP export's."""
+    cfg = oracle.default_config()
+    for k, v in opts.items():
+        setattr(cfg, k, v)
+    x = _spec(77, 30, 4097)
+    x[7] = 0.0
+    masked, chroma, energy = units.key_stages(x, 44100, cfg)
+    if not opts:
+        assert not np.array_equal(masked, x)
+    sq = masked * masked
+    ref = np.cumsum(sq, axis=1, dtype=np.float32)[:, -1]  # cumsum folds in order, one f32 rounding per step
+    assert _same(energy, ref)
+    if cfg.enable_key_harmonic_mask:  # a mask scales the row; time smoothing fills it from its neighbours
+        assert energy[7] == 0.0 and not chroma[7].any()
+    if not opts:
+        ch, en = oracle.chroma("hpcp", masked, 44100, 8192)
+        assert _same(ch, chroma) and _same(en, energy)
+
+
+@pytest.mark.parametrize("seed,bpm", [(7, 120.0), (8101, 126.0)])
+def test_chained_exports_reproduce_the_base_estimate(seed, bpm):
+    """The whole-track oracle's spectrogram (peak normalisation, trim, STFT) through the export:
+    every variant's novelty through units._tempogram gives the export's own tempogram lists, and the
+    estimate tempogram_impl made from them is the analysis trace's base estimate."""
+    x = synth.make_track(seed, seconds=20.0, bpm=bpm)[0]
+    rc, _, tr = oracle.analyze(x, 44100, trace=True)
+    assert rc == 0 and tr["has_tempogram"]
+    st_n, xn = oracle.normalize(x, 0)
+    assert st_n == 0
+    m = oracle.stft(xn[tr["trim_start"]:tr["trim_end"]], 2048, 512)
+    cfg = oracle.default_config()
+    st = units.tempo_stages(m, 44100, 512, cfg)
+    est = units.tempo_stages_estimate()
+    assert list(st) == ["full", "low", "mid", "high", "mel"]
+    for name, v in st.items():
+        fft = units._tempogram(0, v["nov"], 44100, 512, cfg.min_bpm, cfg.max_bpm, cfg.bpm_resolution)
+        acf = units._tempogram(1, v["nov"], 44100, 512, cfg.min_bpm, cfg.max_bpm, cfg.bpm_resolution)
+        assert _same(np.array(fft, np.float32).reshape(-1, 2), v["fft"]), name
+        assert _same(np.array(acf, np.float32).reshape(-1, 2), v["acf"]), name
+    base = tr["base"]
+    assert est[0] > 0 and _same(est[:2], base[:2]) and est[2] == base[2], (est, base)
