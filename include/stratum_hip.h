@@ -378,6 +378,45 @@ int32_t sdsp_decode_flac_batch_device(const uint8_t* const* files, const uint64_
 /* Counters and phase times (HIP events; total_ms is the call's wall time) of the last call on `device`. */
 int32_t sdsp_last_flac_decode_stats(int32_t device, sdsp_flac_decode_stats* out);
 
+/*
+ * Batched lossless decode on the device: one entry for every lossless family the front-end reads.
+ * Arguments, ownership and per-file results are those of sdsp_decode_flac_batch_device: n_files
+ * files held in memory are decoded into one caller-owned device buffer of concatenated mono f32
+ * tracks (sdsp_device_free), track i bit-identical to sdsp_decode_audio_file on the same bytes,
+ * status[i] and errs + 256 * i the host's; a failed file has lens[i] = 0 and the others still
+ * decode; the call returns after the buffer is complete.  Each file is dispatched by content, as
+ * the front-end probes it:
+ *   native FLAC                          the FLAC kernels (scan, frames, chain, gather)
+ *   ALAC in ISO MP4 / M4A and in CAF     the ALAC kernels: one lane per packet (the container's
+ *                                        sample table gives every packet), offsets, gather
+ *   RIFF/WAVE and AIFF / AIFF-C with     the PCM kernel: conversion and channel mix
+ *   linear PCM (u8 / s16 / s24 / s32 / f32 / f64, either byte order, up to 8 channels)
+ * Everything else is decoded by the host decoder, uploaded into the same buffer and counted in
+ * host_fallback_files: G.711, ADPCM, CAF lpcm, Ogg, Matroska, every unsupported codec (which gets
+ * the host's error text), an ALAC frame length above 16384, PCM wider than 8 channels, a file of
+ * 2 GiB or more, files past the call's HBM budget.  A container the host plan refuses (a missing
+ * cookie or sample table, AAC in MP4, a packet outside the file) is that file's error, not a
+ * fallback.  With no HIP device: SDSP_ERR_PROCESSING and "Processing error: no HIP device" in every
+ * errs slot.
+ */
+typedef struct sdsp_decode_stats {
+    uint64_t files, device_files, host_fallback_files, error_files;
+    uint64_t flac_files, alac_files, pcm_files; /* device files per family */
+    uint64_t alac_packets, alac_packets_decoded, alac_packets_skipped;
+    uint64_t bytes_in, samples_out;
+    double upload_ms, flac_ms, alac_ms, pcm_ms, gather_ms; /* HIP events */
+    double total_ms;                                       /* the call's wall time */
+} sdsp_decode_stats;
+
+int32_t sdsp_decode_batch_device(const uint8_t* const* files, const uint64_t* sizes, uint64_t n_files,
+                                 int32_t device, void* stream,
+                                 float** d_samples, /* out: free with sdsp_device_free */
+                                 uint64_t* offsets, uint64_t* lens, uint32_t* sample_rates,
+                                 int32_t* status, char* errs /* n_files x 256 */);
+/* Counters and phase times of the last sdsp_decode_batch_device call on `device`
+ * (sdsp_last_flac_decode_stats keeps reporting calls made through the FLAC entry). */
+int32_t sdsp_last_decode_stats(int32_t device, sdsp_decode_stats* out);
+
 /* Library identification: "stratum-hip <abi> gfx950" */
 const char* sdsp_version(void);
 

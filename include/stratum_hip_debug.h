@@ -163,6 +163,30 @@ int32_t sdsp_probe_stft(int32_t device, uint64_t nfft, uint64_t hop, uint64_t n_
 int32_t sdsp_debug_flac_decode_phased(const uint8_t* data, uint64_t n, float** samples, uint64_t* n_samples,
                                       uint32_t* sample_rate, uint64_t counts[3], char* err, uint64_t errlen);
 
+/*
+ * The device ALAC decoder's phases on the CPU, through the same packet-level code
+ * (csrc/alac_core.hpp): the host plan (cookie and packet table of the CAF or ISO MP4 container), a
+ * decode of every packet into its own slot with its sample count, the walk of the counts into
+ * offsets, the gather of the decoded slots.  Status, text and samples equal
+ * sdsp_decode_audio_file's for the same bytes in a file; *samples is malloc'ed
+ * (sdsp_free_samples).  counts (NULL allowed) receives packets, decoded and skipped packets.
+ * SDSP_ERR_NOT_IMPLEMENTED ("not planned: ...") for bytes that are no ALAC container.  No device
+ * is touched.
+ */
+int32_t sdsp_debug_alac_decode_phased(const uint8_t* data, uint64_t n, float** samples, uint64_t* n_samples,
+                                      uint32_t* sample_rate, uint64_t counts[3], char* err, uint64_t errlen);
+
+/*
+ * The device PCM path's steps on the CPU: the host plan of a RIFF/WAVE or AIFF / AIFF-C file, then
+ * csrc/pcm_core.hpp over the planned frames.  info (NULL allowed) receives the plan: sample kind
+ * (0 u8, 1 s16, 2 s24, 3 s32, 4 f32, 5 f64) | big-endian << 8, channels, data offset, frames.
+ * SDSP_ERR_NOT_IMPLEMENTED ("not planned: ...") for a file that is not linear PCM (G.711, ADPCM,
+ * another container: the batch decoder's host fallback); SDSP_ERR_DECODING with the host decoder's
+ * text for a file it refuses.  No device is touched.
+ */
+int32_t sdsp_debug_pcm_decode_planned(const uint8_t* data, uint64_t n, float** samples, uint64_t* n_samples,
+                                      uint32_t* sample_rate, uint64_t info[4], char* err, uint64_t errlen);
+
 #ifdef __cplusplus
 }
 #endif

@@ -6,13 +6,13 @@
 // summary on stderr.
 //
 //
-// --gpu-decode (opt-in; the output is the same): the workers only read the files' bytes; native FLAC
-// files ("fLaC", or an ID3v2 tag then "fLaC") are grouped by STREAMINFO rate, cut into chunks under
-// a device-memory bound, and each chunk is decoded on a GPU (sdsp_decode_flac_batch_device) and
-// analysed from the device buffer (sdsp_analyze_batch_device): no host PCM exists for them and host
-// memory holds their compressed bytes only.  Chunks go round-robin over the devices of --devices,
-// one host thread per device.  Every other format (Ogg FLAC and Matroska included) takes the path
-// above.
+// --gpu-decode (opt-in; the output is the same): the workers only read the files' bytes.  The files
+// are cut into chunks under a device-memory bound, and each chunk is decoded on a GPU by
+// sdsp_decode_batch_device (native FLAC, ALAC in M4A / CAF, WAV and AIFF PCM by HIP kernels; every
+// other format by the host decoder inside that call) and analysed from the device buffer
+// (sdsp_analyze_batch_device), one call per sample rate the decoder returned: no host PCM exists
+// and host memory holds the files' bytes only.  Chunks go round-robin over the devices of
+// --devices, one host thread per device.
 //
 //   analyze_batch [--jobs N] [--devices MASK] [--json] [--gpu-decode] <file1> <file2> ...
 #include <algorithm>
@@ -30,9 +30,9 @@ namespace {
 struct Item {
     std::string path;
     std::vector<float> samples;
-    std::vector<uint8_t> bytes;  // --gpu-decode: a native FLAC file's compressed bytes
+    std::vector<uint8_t> bytes;  // --gpu-decode: the file's bytes
     uint64_t need = 0;           // --gpu-decode: device bytes the file's decode is expected to take
-    bool flac = false;
+    bool device = false;         // --gpu-decode: the file goes through sdsp_decode_batch_device
     uint32_t sr = 0;
     bool decoded = false;
     std::string error;
@@ -88,8 +88,25 @@ void flac_streaminfo(const std::vector<uint8_t>& b, uint32_t* rate, uint64_t* to
     }
 }
 
+// Device bytes a file's decode is expected to take, from the container's declared length: FLAC by
+// STREAMINFO's sample count; RIFF/WAVE and AIFF hold at most one frame per byte (bytes + 4-byte
+// samples); a compressed or unknown container a generous multiple of its bytes, as a FLAC file of
+// unknown length.  The decoder checks its own budget again.
+uint64_t expected_need(const std::vector<uint8_t>& b) {
+    const uint64_t n = b.size();
+    if (native_flac(b)) {
+        uint32_t rate = 0;
+        uint64_t total = 0;
+        flac_streaminfo(b, &rate, &total);
+        return 3 * n + 8 * (total ? total : 16 * n);
+    }
+    const bool riff = n >= 12 && std::memcmp(b.data(), "RIFF", 4) == 0;
+    const bool form = n >= 12 && std::memcmp(b.data(), "FORM", 4) == 0;
+    if (riff || form) return 5 * n;
+    return 3 * n + 8 * 16 * n;
+}
+
 struct Chunk {
-    uint32_t rate;
     std::vector<size_t> idx;
 };
 
@@ -124,7 +141,7 @@ int main(int argc, char** argv) {
                          "--jobs N        Decode workers (default: CPU-1)\n"
                          "--devices MASK  GPU bitmask (default: all visible GPUs)\n"
                          "--json          Emit one JSON object per line (JSONL)\n"
-                         "--gpu-decode    Decode native FLAC files on the GPUs (same output)\n");
+                         "--gpu-decode    Decode on the GPUs: FLAC, ALAC (M4A / CAF), WAV and AIFF by kernels (same output)\n");
             return 0;
         } else {
             paths.push_back(s);
@@ -151,22 +168,19 @@ int main(int argc, char** argv) {
         for (size_t i; (i = next++) < items.size();) {
             Item& it = items[i];
             it.path = paths[i];
-            if (gpu_decode) {  // read the bytes; only a native FLAC file keeps them
-                if (FILE* fp = std::fopen(it.path.c_str(), "rb")) {
-                    uint8_t chunk[1 << 16];
-                    size_t got;
-                    while ((got = std::fread(chunk, 1, sizeof chunk, fp)) > 0) it.bytes.insert(it.bytes.end(), chunk, chunk + got);
-                    std::fclose(fp);
-                }
-                if (native_flac(it.bytes)) {
-                    uint64_t total = 0;
-                    flac_streaminfo(it.bytes, &it.sr, &total);
-                    if (it.sr == 0) it.sr = 44100;
-                    it.need = 3 * (uint64_t)it.bytes.size() + 8 * (total ? total : 16 * (uint64_t)it.bytes.size());
-                    it.flac = true;
+            if (gpu_decode) {  // read the bytes; the decode happens on the device threads below
+                FILE* fp = std::fopen(it.path.c_str(), "rb");
+                if (!fp) {
+                    it.error = "decode failed: cannot open " + it.path;
                     continue;
                 }
-                std::vector<uint8_t>().swap(it.bytes);
+                uint8_t chunk[1 << 16];
+                size_t got;
+                while ((got = std::fread(chunk, 1, sizeof chunk, fp)) > 0) it.bytes.insert(it.bytes.end(), chunk, chunk + got);
+                std::fclose(fp);
+                it.need = expected_need(it.bytes);
+                it.device = true;
+                continue;
             }
             float* p = nullptr;
             uint64_t n = 0;
@@ -206,23 +220,18 @@ int main(int argc, char** argv) {
     };
 
     if (gpu_decode) {
-        // chunks of one STREAMINFO rate, at most 8 GiB of expected device memory and 512 files each
-        // (the decoder checks its own budget again and sends what does not fit to the host decoder)
-        std::map<uint32_t, std::vector<size_t>> flac_by_sr;
-        for (size_t i = 0; i < items.size(); i++)
-            if (items[i].flac) flac_by_sr[items[i].sr].push_back(i);
+        // chunks of at most 8 GiB of expected device memory and 512 files each (the decoder checks
+        // its own budget again and sends what does not fit to the host decoder)
         std::vector<Chunk> chunks;
-        for (auto& kv : flac_by_sr) {
-            uint64_t acc = 0;
-            for (size_t i : kv.second) {
-                if (chunks.empty() || chunks.back().rate != kv.first || chunks.back().idx.size() >= 512 ||
-                    (acc && acc + items[i].need > (8ull << 30))) {
-                    chunks.push_back(Chunk{kv.first, {}});
-                    acc = 0;
-                }
-                chunks.back().idx.push_back(i);
-                acc += items[i].need;
+        uint64_t acc = 0;
+        for (size_t i = 0; i < items.size(); i++) {
+            if (!items[i].device) continue;
+            if (chunks.empty() || chunks.back().idx.size() >= 512 || (acc && acc + items[i].need > (8ull << 30))) {
+                chunks.push_back(Chunk{});
+                acc = 0;
             }
+            chunks.back().idx.push_back(i);
+            acc += items[i].need;
         }
         std::vector<int> devs;
         for (int d = 0; d < 32; d++)
@@ -239,10 +248,9 @@ int main(int argc, char** argv) {
                 sizes[k] = items[ch.idx[k]].bytes.size();
             }
             float* d_samples = nullptr;
-            const int32_t rc = sdsp_decode_flac_batch_device(ptrs.data(), sizes.data(), n, dev, nullptr, &d_samples, offs.data(),
-                                                             lens.data(), rates.data(), status.data(), errs.data());
-            std::vector<size_t> okk;
-            std::vector<uint64_t> o2, l2;
+            const int32_t rc = sdsp_decode_batch_device(ptrs.data(), sizes.data(), n, dev, nullptr, &d_samples, offs.data(),
+                                                        lens.data(), rates.data(), status.data(), errs.data());
+            std::map<uint32_t, std::vector<size_t>> by_rate;  // the decoded files, by the rate the decoder returned
             for (size_t k = 0; k < n; k++) {
                 Item& it = items[ch.idx[k]];
                 std::vector<uint8_t>().swap(it.bytes);
@@ -251,13 +259,18 @@ int main(int argc, char** argv) {
                     continue;
                 }
                 it.decoded = true;
-                okk.push_back(k);
-                o2.push_back(offs[k]);
-                l2.push_back(lens[k]);
+                it.sr = rates[k];
+                by_rate[rates[k]].push_back(k);
             }
-            if (!okk.empty()) {
+            for (auto& kv : by_rate) {
+                const std::vector<size_t>& okk = kv.second;
+                std::vector<uint64_t> o2, l2;
+                for (size_t k : okk) {
+                    o2.push_back(offs[k]);
+                    l2.push_back(lens[k]);
+                }
                 std::vector<sdsp_result> outs(okk.size());
-                (void)sdsp_analyze_batch_device(d_samples, o2.data(), l2.data(), okk.size(), ch.rate, &cfg, dev, nullptr,
+                (void)sdsp_analyze_batch_device(d_samples, o2.data(), l2.data(), okk.size(), kv.first, &cfg, dev, nullptr,
                                                 outs.data());
                 for (size_t j = 0; j < okk.size(); j++) {
                     take(items[ch.idx[okk[j]]], outs[j]);
@@ -276,7 +289,7 @@ int main(int argc, char** argv) {
 
     std::map<uint32_t, std::vector<size_t>> by_sr;
     for (size_t i = 0; i < items.size(); i++)
-        if (items[i].decoded && !items[i].flac) by_sr[items[i].sr].push_back(i);
+        if (items[i].decoded && !items[i].device) by_sr[items[i].sr].push_back(i);
     for (auto& kv : by_sr) {
         const std::vector<size_t>& idx = kv.second;
         std::vector<const float*> ptrs;

@@ -11,11 +11,21 @@
 // same f32 values for these depths), 32 -> s / 2^31.  One and two channels (SCE, CPE) are
 // decoded; other channel layouts are a decoding error.  Parity with symphonia itself is
 // unpinned: tests/alac_enc.py writes the test streams from the same format description.
+//
+// The packet-level decode is alac_core.hpp, the code the device kernel (k_alac.hip) runs; this file
+// holds the container parsing.  A container parse yields a plan (the cookie and the packet table,
+// lossless_host.hpp) without decoding: the host decoder decodes the plan's packets one after the
+// other, the batch decoder sends the plan to the device.
 #include <cstring>
 #include <string>
 #include <vector>
 
+#include "lossless_host.hpp"
+
 namespace {
+
+namespace ac = alac_core;
+using AlacConfig = ac::Config;
 
 uint16_t be16(const uint8_t* p) { return (uint16_t)((p[0] << 8) | p[1]); }
 uint32_t be32(const uint8_t* p) { return ((uint32_t)p[0] << 24) | ((uint32_t)p[1] << 16) | ((uint32_t)p[2] << 8) | p[3]; }
@@ -25,12 +35,6 @@ bool fail(std::string* err, const std::string& m) {
     *err = m;
     return false;
 }
-
-struct AlacConfig {
-    uint32_t frame_length = 4096;
-    int bit_depth = 16, pb = 40, mb = 10, kb = 14, channels = 2, max_run = 255;
-    uint32_t sample_rate = 44100;
-};
 
 // ALACSpecificConfig (24 bytes), possibly behind 'frma' / 'alac' atom headers (CAF 'kuki')
 bool parse_cookie(const uint8_t* p, size_t n, AlacConfig* c, std::string* err) {
@@ -53,321 +57,18 @@ bool parse_cookie(const uint8_t* p, size_t n, AlacConfig* c, std::string* err) {
     return true;
 }
 
-// MSB-first bit reader over one packet; reads past the end return zeros and set `over`
-struct Bits {
-    const uint8_t* p;
-    size_t n;
-    uint64_t pos = 0;
-    bool over = false;
-    Bits(const uint8_t* d, size_t len) : p(d), n(len) {}
-    uint32_t peek32() const {  // the 32 bits at pos (zeros past the end)
-        uint64_t w = 0;
-        for (int i = 0; i < 5; i++) {
-            const size_t b = (size_t)(pos >> 3) + (size_t)i;
-            w = (w << 8) | (b < n ? p[b] : 0);
-        }
-        return (uint32_t)(w >> (8 - (pos & 7)));
-    }
-    uint32_t read(int k) {  // k <= 32
-        if (k == 0) return 0;
-        const uint32_t v = k == 32 ? peek32() : peek32() >> (32 - k);
-        pos += (uint64_t)k;
-        if (pos > 8 * (uint64_t)n) over = true;
-        return v;
-    }
-    void skip(uint64_t k) {
-        pos += k;
-        if (pos > 8 * (uint64_t)n) over = true;
-    }
-};
-
-inline int clz32(uint32_t x) { return x ? __builtin_clz(x) : 32; }
-
-// adaptive Golomb parameters (Apple's ag_dec: QBSHIFT 9, MMULSHIFT 2, MDENSHIFT 6, MOFF 16,
-// BITOFF 24, escape after a 9-bit prefix, zero runs of up to 65535)
-constexpr int QBSHIFT = 9, QB = 1 << QBSHIFT, MMULSHIFT = 2, MDENSHIFT = QBSHIFT - MMULSHIFT - 1,
-              MOFF = 1 << (MDENSHIFT - 2), BITOFF = 24, MAX_PREFIX = 9, MAX_DATATYPE_BITS_16 = 16;
-
-// one Golomb value: a unary prefix of ones (escape at 9), then k bits; values v < 2 give pre * m
-// and return the k-th bit to the stream
-uint32_t ag_get(Bits& b, uint32_t m, int k, int escape_bits) {
-    const uint32_t s = b.peek32();
-    const int pre = clz32(~s);
-    if (pre >= MAX_PREFIX) {
-        b.skip(MAX_PREFIX);
-        return b.read(escape_bits);
-    }
-    b.skip((uint64_t)pre + 1);
-    if (k == 1) return (uint32_t)pre;
-    const uint32_t v = b.read(k);
-    if (v >= 2) return (uint32_t)pre * m + v - 1;
-    b.pos -= 1;
-    return (uint32_t)pre * m;
+// the text of a packet's error code (the examples skip such a packet, so nothing prints it; the
+// tools do)
+std::string frame_error(int32_t code, int32_t detail) {
+    std::string m = ac::err_text(code);
+    if (code == ac::UNSUPPORTED_ELEMENT || code == ac::PREDICTION_MODE) m += std::to_string(detail);
+    return m;
 }
 
-// dyn_decomp: numSamples signed residuals into pc
-bool ag_decode(Bits& b, const AlacConfig& c, int pb_factor, int n, int chan_bits, std::vector<int32_t>& pc) {
-    const uint32_t pb = (uint32_t)(c.pb * pb_factor) / 4;
-    const uint32_t wb = (1u << c.kb) - 1;
-    uint32_t mb = (uint32_t)c.mb;
-    uint32_t zmode = 0;
-    int i = 0;
-    while (i < n) {
-        const uint32_t m0 = mb >> QBSHIFT;
-        int k = 31 - clz32(m0 + 3);  // lg3a
-        if (k > c.kb) k = c.kb;
-        const uint32_t m = (1u << k) - 1;
-        const uint32_t v = ag_get(b, m, k, chan_bits);
-        const uint32_t nd = v + zmode;
-        const int32_t mag = (int32_t)((nd + 1) >> 1);
-        pc[(size_t)i++] = (nd & 1) ? -mag : mag;
-        mb = pb * (v + zmode) + mb - ((pb * mb) >> QBSHIFT);
-        if (v > 0xffff) mb = 0xffff;
-        zmode = 0;
-        if (((mb << MMULSHIFT) < (uint32_t)QB) && i < n) {
-            zmode = 1;
-            const int kz = clz32(mb) - BITOFF + (int)((mb + MOFF) >> MDENSHIFT);
-            const uint32_t mz = ((1u << kz) - 1) & wb;
-            const uint32_t run = ag_get(b, mz, kz, MAX_DATATYPE_BITS_16);
-            if ((uint64_t)i + run > (uint64_t)n) return false;
-            for (uint32_t j = 0; j < run; j++) pc[(size_t)i++] = 0;
-            if (run >= 65535) zmode = 0;
-            mb = 0;
-        }
-        if (b.over) return false;
-    }
-    return true;
-}
-
-inline int32_t sext(int32_t v, int chan_bits) {
-    const int sh = 32 - chan_bits;
-    return (int32_t)((uint32_t)v << sh) >> sh;
-}
-inline int32_t sign_of(int32_t v) { return (v > 0) - (v < 0); }
-
-// unpc_block: the sign-adaptive predictor (numactive 31: first-order difference)
-void unpredict(const std::vector<int32_t>& pc, std::vector<int32_t>& out, int n, int16_t* coefs, int na, int chan_bits,
-               int den_shift) {
-    if (n <= 0) return;
-    out[0] = pc[0];
-    if (na == 0) {
-        for (int j = 1; j < n; j++) out[(size_t)j] = pc[(size_t)j];
-        return;
-    }
-    if (na == 31) {
-        int32_t prev = out[0];
-        for (int j = 1; j < n; j++) {
-            prev = sext((int32_t)((uint32_t)pc[(size_t)j] + (uint32_t)prev), chan_bits);
-            out[(size_t)j] = prev;
-        }
-        return;
-    }
-    for (int j = 1; j <= na && j < n; j++)
-        out[(size_t)j] = sext((int32_t)((uint32_t)pc[(size_t)j] + (uint32_t)out[(size_t)j - 1]), chan_bits);
-    const int32_t den_half = den_shift > 0 ? 1 << (den_shift - 1) : 0;
-    const int lim = na + 1;
-    for (int j = lim; j < n; j++) {
-        const int32_t* pout = out.data() + j - 1;
-        const int32_t top = out[(size_t)(j - lim)];
-        // 32-bit wrap-around arithmetic, as the reference implementation's int32 sums
-        uint32_t sum = 0;
-        for (int k = 0; k < na; k++) sum += (uint32_t)((int64_t)coefs[k] * ((int64_t)pout[-k] - (int64_t)top));
-        const int32_t del = pc[(size_t)j];
-        int32_t del0 = del;
-        const int32_t sg = sign_of(del);
-        const int32_t pred = (int32_t)(sum + (uint32_t)den_half) >> den_shift;
-        out[(size_t)j] = sext((int32_t)((uint32_t)del + (uint32_t)top + (uint32_t)pred), chan_bits);
-        if (sg > 0) {
-            for (int k = na - 1; k >= 0; k--) {
-                const int32_t dd = (int32_t)((uint32_t)top - (uint32_t)pout[-k]);
-                const int32_t sgn = sign_of(dd);
-                coefs[k] = (int16_t)(coefs[k] - sgn);
-                del0 -= (na - k) * (int32_t)((int64_t)sgn * dd >> den_shift);
-                if (del0 <= 0) break;
-            }
-        } else if (sg < 0) {
-            for (int k = na - 1; k >= 0; k--) {
-                const int32_t dd = (int32_t)((uint32_t)top - (uint32_t)pout[-k]);
-                const int32_t sgn = sign_of(dd);
-                coefs[k] = (int16_t)(coefs[k] + sgn);
-                del0 -= (na - k) * (int32_t)((int64_t)-sgn * dd >> den_shift);
-                if (del0 >= 0) break;
-            }
-        }
-    }
-}
-
-// one ALAC frame (packet) -> interleaved integer samples appended to pcm
-bool decode_frame(const uint8_t* d, size_t len, const AlacConfig& c, std::vector<int32_t>* pcm, std::string* err) {
-    Bits b(d, len);
-    const int nch_total = c.channels;
-    int ch_done = 0;
-    std::vector<int32_t> frame_out;
-    int frame_n = -1;
-    while (true) {
-        const uint32_t tag = b.read(3);
-        if (b.over) return fail(err, "truncated ALAC frame");
-        if (tag == 7) break;  // ID_END
-        if (tag == 6) {       // ID_FIL: count + bytes
-            uint32_t cnt = b.read(4);
-            if (cnt == 15) cnt += b.read(8) - 1;
-            b.skip(8ull * cnt);
-            continue;
-        }
-        if (tag == 4) {  // ID_DSE: tag, align flag, count, (align), bytes
-            b.read(4);
-            const uint32_t align = b.read(1);
-            uint32_t cnt = b.read(8);
-            if (cnt == 255) cnt += b.read(8);
-            if (align) b.skip((8 - (b.pos & 7)) & 7);
-            b.skip(8ull * cnt);
-            continue;
-        }
-        if (tag != 0 && tag != 1 && tag != 3) return fail(err, "unsupported ALAC element " + std::to_string(tag));
-        const int ech = tag == 1 ? 2 : 1;
-        if (ch_done + ech > nch_total) return fail(err, "ALAC element exceeds the channel count");
-        b.read(4);  // element instance tag
-        if (b.read(12) != 0) return fail(err, "malformed ALAC element header");
-        const uint32_t hb = b.read(4);
-        const bool partial = hb & 8;
-        const int bytes_shifted = (int)((hb >> 1) & 3);
-        const bool escape = hb & 1;
-        if (bytes_shifted == 3) return fail(err, "malformed ALAC element header");
-        int n = (int)c.frame_length;
-        if (partial) {
-            uint32_t v = b.read(16) << 16;
-            v |= b.read(16);
-            if (v == 0 || v > c.frame_length) return fail(err, "malformed ALAC sample count");
-            n = (int)v;
-        }
-        if (frame_n < 0) {
-            frame_n = n;
-            frame_out.assign((size_t)n * (size_t)nch_total, 0);
-        } else if (n != frame_n) {
-            return fail(err, "ALAC elements disagree on the sample count");
-        }
-        const int shift = escape ? 0 : bytes_shifted * 8;  // raw elements carry the full samples
-        std::vector<int32_t> u((size_t)n), v(ech == 2 ? (size_t)n : 0), sh((size_t)n * (size_t)ech, 0);
-        int mix_bits = 0, mix_res = 0;
-        if (!escape) {
-            const int chan_bits = c.bit_depth - shift + (ech == 2 ? 1 : 0);
-            if (chan_bits < 1 || chan_bits > 32) return fail(err, "malformed ALAC element");
-            if (ech == 2) {
-                mix_bits = (int)b.read(8);
-                mix_res = (int8_t)b.read(8);
-                if (mix_bits > 31) return fail(err, "malformed ALAC element");
-            }
-            int mode[2], den[2], pbf[2], na[2];
-            int16_t coefs[2][32];
-            for (int e = 0; e < ech; e++) {
-                const uint32_t h1 = b.read(8), h2 = b.read(8);
-                mode[e] = (int)(h1 >> 4);
-                den[e] = (int)(h1 & 15);
-                pbf[e] = (int)(h2 >> 5);
-                na[e] = (int)(h2 & 31);
-                for (int k = 0; k < na[e]; k++) coefs[e][k] = (int16_t)b.read(16);
-            }
-            uint64_t shift_pos = 0;
-            if (shift) {
-                shift_pos = b.pos;
-                b.skip((uint64_t)shift * (uint64_t)ech * (uint64_t)n);
-            }
-            std::vector<int32_t> pc((size_t)n);
-            for (int e = 0; e < ech; e++) {
-                if (!ag_decode(b, c, pbf[e], n, chan_bits, pc)) return fail(err, "corrupt ALAC residuals");
-                std::vector<int32_t>& dst = e == 0 ? u : v;
-                if (mode[e] == 0) {
-                    unpredict(pc, dst, n, coefs[e], na[e], chan_bits, den[e]);
-                } else if (mode[e] == 15) {  // a first-order pass, then the FIR predictor
-                    std::vector<int32_t> tmp((size_t)n);
-                    unpredict(pc, tmp, n, nullptr, 31, chan_bits, 0);
-                    unpredict(tmp, dst, n, coefs[e], na[e], chan_bits, den[e]);
-                } else {
-                    return fail(err, "unsupported ALAC prediction mode " + std::to_string(mode[e]));
-                }
-            }
-            if (shift) {
-                const uint64_t end = b.pos;
-                b.pos = shift_pos;
-                for (int i = 0; i < n; i++)
-                    for (int e = 0; e < ech; e++) sh[(size_t)i * ech + e] = (int32_t)b.read(shift);
-                b.pos = end;
-            }
-        } else {
-            // escaped: raw samples of the full bit depth, channels interleaved per sample
-            const int bits = c.bit_depth;
-            for (int i = 0; i < n; i++) {
-                for (int e = 0; e < ech; e++) {
-                    int32_t val;
-                    if (bits <= 16) {
-                        val = sext((int32_t)b.read(bits), bits);
-                    } else {
-                        const int32_t hi = sext((int32_t)b.read(16), 16);
-                        val = (int32_t)((uint32_t)hi << (bits - 16)) | (int32_t)b.read(bits - 16);
-                    }
-                    (e == 0 ? u : v)[(size_t)i] = val;
-                }
-            }
-        }
-        if (b.over) return fail(err, "truncated ALAC frame");
-        // un-mix (stereo) and restore the shifted low bytes
-        for (int i = 0; i < n; i++) {
-            int32_t l, r = 0;
-            if (ech == 2) {
-                if (mix_res != 0) {
-                    l = (int32_t)((uint32_t)u[(size_t)i] + (uint32_t)v[(size_t)i] -
-                                  (uint32_t)((int32_t)((uint32_t)mix_res * (uint32_t)v[(size_t)i]) >> mix_bits));
-                    r = (int32_t)((uint32_t)l - (uint32_t)v[(size_t)i]);
-                } else {
-                    l = u[(size_t)i];
-                    r = v[(size_t)i];
-                }
-            } else {
-                l = u[(size_t)i];
-            }
-            if (shift) {
-                l = (int32_t)((uint32_t)l << shift) | sh[(size_t)i * ech];
-                if (ech == 2) r = (int32_t)((uint32_t)r << shift) | sh[(size_t)i * ech + 1];
-            }
-            frame_out[(size_t)i * nch_total + ch_done] = l;
-            if (ech == 2) frame_out[(size_t)i * nch_total + ch_done + 1] = r;
-        }
-        ch_done += ech;
-    }
-    if (ch_done != nch_total) return fail(err, "ALAC frame is missing channels");
-    pcm->insert(pcm->end(), frame_out.begin(), frame_out.end());
-    return true;
-}
-
-// interleaved integers of the stream's depth -> mono f32 (the examples' conversion)
-void to_mono(const AlacConfig& c, const std::vector<int32_t>& pcm, std::vector<float>* out) {
-    const int ch = c.channels;
-    const float scale = c.bit_depth == 16 ? 32768.0f : c.bit_depth == 32 ? 2147483648.0f : (float)(1u << (c.bit_depth - 1));
-    const size_t frames = pcm.size() / (size_t)ch;
-    out->resize(frames);
-    for (size_t i = 0; i < frames; i++) {
-        if (ch == 1) {
-            (*out)[i] = (float)pcm[i] / scale;
-        } else {
-            float s = -0.0f;
-            for (int k = 0; k < ch; k++) s = s + (float)pcm[i * ch + (size_t)k] / scale;
-            (*out)[i] = s / (float)ch;
-        }
-    }
-}
-
-// packets -> mono; a packet that fails to decode is skipped (the examples skip DecodeError)
-bool decode_packets(const AlacConfig& c, const uint8_t* base, size_t size, const std::vector<std::pair<uint64_t, uint64_t>>& pk,
-                    std::vector<float>* out, uint32_t* sr, std::string* err) {
-    std::vector<int32_t> pcm;
-    for (const auto& p : pk) {
+// every packet of the table lies inside the file
+bool check_packets(size_t size, const std::vector<std::pair<uint64_t, uint64_t>>& pk, std::string* err) {
+    for (const auto& p : pk)
         if (p.first > size || p.second > size - p.first) return fail(err, "ALAC packet outside the file");
-        std::string why;
-        std::vector<int32_t> one;
-        if (decode_frame(base + p.first, (size_t)p.second, c, &one, &why)) pcm.insert(pcm.end(), one.begin(), one.end());
-    }
-    to_mono(c, pcm, out);
-    *sr = c.sample_rate ? c.sample_rate : 44100u;
     return true;
 }
 
@@ -385,19 +86,47 @@ bool caf_vlq(const uint8_t* p, size_t n, size_t* pos, uint64_t* v) {
 
 }  // namespace
 
+// one packet through the core with host buffers; the error text where it fails
+bool sdsp_alac_decode_packet(const ac::Config& c, const uint8_t* d, size_t len, std::vector<int32_t>* work,
+                             std::vector<float>* slot, uint32_t* n_out, std::string* err) {
+    work->resize((size_t)c.channels * c.frame_length);
+    slot->resize(c.frame_length);
+    int16_t coefs[64];
+    int32_t detail = 0;
+    const ac::Work w{work->data(), 1, work->size(), c.frame_length};
+    const int32_t e = ac::decode_frame(d, len, c, w, ac::Coefs{coefs, 1}, slot->data(), 1, n_out, &detail);
+    if (e != ac::OK && err) *err = frame_error(e, detail);
+    return e == ac::OK;
+}
+
+// packets -> mono; a packet that fails to decode is skipped (the examples skip DecodeError)
+void sdsp_alac_decode_plan(const uint8_t* f, const sdsp_alac_plan& plan, std::vector<float>* out, uint32_t* sr) {
+    std::vector<int32_t> work;
+    std::vector<float> slot;
+    out->clear();
+    for (const auto& p : plan.packets) {
+        uint32_t n = 0;
+        std::string why;
+        if (sdsp_alac_decode_packet(plan.cfg, f + p.first, (size_t)p.second, &work, &slot, &n, &why))
+            out->insert(out->end(), slot.begin(), slot.begin() + n);
+    }
+    *sr = plan.cfg.sample_rate ? plan.cfg.sample_rate : 44100u;
+}
+
 // CAF with format 'alac': desc, kuki (the magic cookie), pakt (packet sizes), data
-bool sdsp_decode_caf_alac(const std::vector<uint8_t>& f, std::vector<float>* out, uint32_t* sr, std::string* err) {
-    AlacConfig c;
+bool sdsp_alac_plan_caf(const uint8_t* f, size_t fsize, sdsp_alac_plan* plan, std::string* err) {
+    AlacConfig& c = plan->cfg;
+    plan->packets.clear();
     bool have_cookie = false;
     const uint8_t* pakt = nullptr;
     uint64_t pakt_len = 0;
     uint64_t data_off = 0, data_len = 0;
     bool have_data = false;
     size_t pos = 8;
-    while (pos + 12 <= f.size()) {
-        const uint8_t* ck = f.data() + pos;
+    while (pos + 12 <= fsize) {
+        const uint8_t* ck = f + pos;
         const int64_t slen = (int64_t)be64(ck + 4);
-        const uint64_t avail = f.size() - (pos + 12);
+        const uint64_t avail = fsize - (pos + 12);
         const uint64_t body = (slen < 0 || (uint64_t)slen > avail) ? avail : (uint64_t)slen;
         if (std::memcmp(ck, "kuki", 4) == 0) {
             if (!parse_cookie(ck + 12, (size_t)body, &c, err)) return false;
@@ -418,7 +147,7 @@ bool sdsp_decode_caf_alac(const std::vector<uint8_t>& f, std::vector<float>* out
     if (!have_data) return fail(err, "missing data chunk");
     if (!pakt || pakt_len < 24) return fail(err, "missing packet table");
     const uint64_t npk = be64(pakt);
-    std::vector<std::pair<uint64_t, uint64_t>> pk;
+    std::vector<std::pair<uint64_t, uint64_t>>& pk = plan->packets;
     size_t q = 24;
     uint64_t off = data_off;
     for (uint64_t i = 0; i < npk; i++) {
@@ -428,7 +157,14 @@ bool sdsp_decode_caf_alac(const std::vector<uint8_t>& f, std::vector<float>* out
         pk.push_back({off, sz});
         off += sz;
     }
-    return decode_packets(c, f.data(), f.size(), pk, out, sr, err);
+    return check_packets(fsize, pk, err);
+}
+
+bool sdsp_decode_caf_alac(const std::vector<uint8_t>& f, std::vector<float>* out, uint32_t* sr, std::string* err) {
+    sdsp_alac_plan plan;
+    if (!sdsp_alac_plan_caf(f.data(), f.size(), &plan, err)) return false;
+    sdsp_alac_decode_plan(f.data(), plan, out, sr);
+    return true;
 }
 
 namespace {
@@ -455,17 +191,18 @@ bool boxes(const uint8_t* p, uint64_t n, Fn fn) {
 }  // namespace
 
 // ISO MP4 / M4A: the first audio track's sample table (stsd 'alac', stsz, stsc, stco / co64)
-bool sdsp_decode_mp4(const std::vector<uint8_t>& f, std::vector<float>* out, uint32_t* sr, std::string* err) {
+bool sdsp_alac_plan_mp4(const uint8_t* fdata, size_t fsize, sdsp_alac_plan* plan, std::string* err) {
+    plan->packets.clear();
     const uint8_t* moov = nullptr;
     uint64_t moov_n = 0;
-    boxes(f.data(), f.size(), [&](const uint8_t* t, const uint8_t* b, uint64_t n) {
+    boxes(fdata, fsize, [&](const uint8_t* t, const uint8_t* b, uint64_t n) {
         if (std::memcmp(t, "moov", 4) == 0) moov = b, moov_n = n;
         return true;
     });
     if (!moov) return fail(err, "malformed ISO MP4 file: missing moov box");
     std::string codec;
     bool found = false;
-    AlacConfig c;
+    AlacConfig& c = plan->cfg;
     std::vector<uint32_t> sizes;
     std::vector<uint64_t> chunk_off;
     std::vector<uint32_t> stsc;  // triples: first chunk, samples per chunk, description index
@@ -533,7 +270,7 @@ bool sdsp_decode_mp4(const std::vector<uint8_t>& f, std::vector<float>* out, uin
     if (codec != "alac") return fail(err, "unsupported codec: ISO MP4 '" + codec + "'");
     if (stsc.empty() || chunk_off.empty()) return fail(err, "malformed sample table");
     // sample -> (offset, size) through the sample-to-chunk runs
-    std::vector<std::pair<uint64_t, uint64_t>> pk;
+    std::vector<std::pair<uint64_t, uint64_t>>& pk = plan->packets;
     size_t s = 0;
     const size_t runs = stsc.size() / 3;
     for (size_t r = 0; r < runs && s < sizes.size(); r++) {
@@ -548,19 +285,26 @@ bool sdsp_decode_mp4(const std::vector<uint8_t>& f, std::vector<float>* out, uin
             }
         }
     }
-    return decode_packets(c, f.data(), f.size(), pk, out, sr, err);
+    return check_packets(fsize, pk, err);
+}
+
+bool sdsp_decode_mp4(const std::vector<uint8_t>& f, std::vector<float>* out, uint32_t* sr, std::string* err) {
+    sdsp_alac_plan plan;
+    if (!sdsp_alac_plan_mp4(f.data(), f.size(), &plan, err)) return false;
+    sdsp_alac_decode_plan(f.data(), plan, out, sr);
+    return true;
 }
 
 // ALAC from a magic cookie and a list of packets (the Matroska A_ALAC track, host_mkv.hip)
 bool sdsp_decode_alac_packets(const std::vector<uint8_t>& cookie, const std::vector<std::vector<uint8_t>>& packets,
                               std::vector<float>* out, uint32_t* sr, std::string* err) {
-    AlacConfig c;
-    if (!parse_cookie(cookie.data(), cookie.size(), &c, err)) return false;
+    sdsp_alac_plan plan;
+    if (!parse_cookie(cookie.data(), cookie.size(), &plan.cfg, err)) return false;
     std::vector<uint8_t> flat;
-    std::vector<std::pair<uint64_t, uint64_t>> pk;
     for (const auto& p : packets) {
-        pk.push_back({flat.size(), p.size()});
+        plan.packets.push_back({flat.size(), p.size()});
         flat.insert(flat.end(), p.begin(), p.end());
     }
-    return decode_packets(c, flat.data(), flat.size(), pk, out, sr, err);
+    sdsp_alac_decode_plan(flat.data(), plan, out, sr);
+    return true;
 }

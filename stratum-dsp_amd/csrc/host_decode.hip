@@ -23,6 +23,7 @@
 #include "../../include/stratum_hip.h"
 
 #include "flac_host.hpp"
+#include "lossless_host.hpp"
 
 bool sdsp_decode_aiff(const std::vector<uint8_t>& f, std::vector<float>* out, uint32_t* sr, std::string* err);
 bool sdsp_decode_caf(const std::vector<uint8_t>& f, std::vector<float>* out, uint32_t* sr, std::string* err);
@@ -63,31 +64,18 @@ int16_t ulaw_to_s16(uint8_t u) {
 
 enum class Kind { U8, S16, S24, S32, F32, F64, ALAW, ULAW };
 
-// one channel sample -> f32, the reference's per-type conversion
+inline int core_kind(Kind k) {
+    return k == Kind::U8 ? pcm_core::U8 : k == Kind::S16 ? pcm_core::S16 : k == Kind::S24 ? pcm_core::S24
+           : k == Kind::S32 ? pcm_core::S32 : k == Kind::F32 ? pcm_core::F32 : pcm_core::F64;
+}
+
+// one channel sample -> f32, the reference's per-type conversion: the linear kinds through
+// pcm_core.hpp (the code the device kernel runs), G.711 here
 inline float conv(Kind k, const uint8_t* p) {
-    switch (k) {
-        case Kind::U8: return ((float)p[0] - 128.0f) / 128.0f;
-        case Kind::S16: return (float)(int16_t)rd16(p) / 32768.0f;
-        case Kind::S24: {
-            int32_t v = (int32_t)((uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16));
-            if (v & 0x800000) v -= 0x1000000;
-            return (float)v / 8388608.0f;
-        }
-        case Kind::S32: return (float)(int32_t)rd32(p) / 2147483648.0f;
-        case Kind::F32: {
-            float f;
-            std::memcpy(&f, p, 4);
-            return f;
-        }
-        case Kind::F64: {
-            double d;
-            std::memcpy(&d, p, 8);
-            return (float)d;
-        }
-        case Kind::ALAW: return (float)alaw_to_s16(p[0]) / 32768.0f;
-        case Kind::ULAW: return (float)ulaw_to_s16(p[0]) / 32768.0f;
-    }
-    return 0.0f;
+    if (k == Kind::ALAW) return (float)alaw_to_s16(p[0]) / 32768.0f;
+    if (k == Kind::ULAW) return (float)ulaw_to_s16(p[0]) / 32768.0f;
+    const int ck = core_kind(k);
+    return pcm_core::conv(ck, false, pcm_core::load(p, pcm_core::width_of(ck)));
 }
 
 bool fail(char* err, uint64_t errlen, const std::string& m) {
@@ -202,10 +190,18 @@ bool msadpcm_decode(const uint8_t* d, uint64_t n, int ch, int ba, const std::vec
     return true;
 }
 
-bool decode_wav(const std::vector<uint8_t>& f, std::vector<float>* out, uint32_t* sr, char* err, uint64_t errlen) {
+// the chunk walk: the fmt chunk and the data chunk's bytes (clipped to the file)
+bool wav_parse(const uint8_t* fdata, size_t fsize, Fmt* fmt_out, const uint8_t** data_out, uint64_t* data_len_out, char* err,
+               uint64_t errlen) {
+    struct {
+        const uint8_t* d;
+        size_t n;
+        size_t size() const { return n; }
+        const uint8_t* data() const { return d; }
+    } f{fdata, fsize};
+    Fmt& fmt = *fmt_out;
     if (f.size() < 12 || std::memcmp(f.data(), "RIFF", 4) != 0 || std::memcmp(f.data() + 8, "WAVE", 4) != 0)
         return fail(err, errlen, "unsupported format: not a RIFF/WAVE file");
-    Fmt fmt;
     bool have_fmt = false;
     const uint8_t* data = nullptr;
     uint64_t data_len = 0;
@@ -241,6 +237,12 @@ bool decode_wav(const std::vector<uint8_t>& f, std::vector<float>* out, uint32_t
     if (!have_fmt) return fail(err, errlen, "missing fmt chunk");
     if (!data) return fail(err, errlen, "missing data chunk");
     if (fmt.channels == 0) return fail(err, errlen, "zero channels");
+    *data_out = data, *data_len_out = data_len;
+    return true;
+}
+
+// the linear-PCM layouts (tags 1 and 3): 1 with kind and width, 0 another tag, -1 an error
+int wav_linear(const Fmt& fmt, Kind* k_out, int* width_out, char* err, uint64_t errlen) {
     Kind k;
     int width;
     if (fmt.tag == 1) {
@@ -253,15 +255,52 @@ bool decode_wav(const std::vector<uint8_t>& f, std::vector<float>* out, uint32_t
         else if (fmt.bits == 32)
             k = Kind::S32, width = 4;
         else
-            return fail(err, errlen, "unsupported PCM bits per sample " + std::to_string(fmt.bits));
+            return fail(err, errlen, "unsupported PCM bits per sample " + std::to_string(fmt.bits)) - 1;
     } else if (fmt.tag == 3) {
         if (fmt.bits == 32)
             k = Kind::F32, width = 4;
         else if (fmt.bits == 64)
             k = Kind::F64, width = 8;
         else
-            return fail(err, errlen, "unsupported float bits per sample " + std::to_string(fmt.bits));
-    } else if (fmt.tag == 6 && fmt.bits == 8) {
+            return fail(err, errlen, "unsupported float bits per sample " + std::to_string(fmt.bits)) - 1;
+    } else {
+        return 0;
+    }
+    *k_out = k, *width_out = width;
+    return 1;
+}
+
+// linear PCM: layout, rate, data offset, whole frames; 1 planned, 0 another tag, -1 an error
+int wav_plan(const uint8_t* fdata, size_t fsize, const Fmt& fmt, const uint8_t* data, uint64_t data_len, sdsp_pcm_plan* plan,
+             char* err, uint64_t errlen) {
+    Kind k;
+    int width;
+    const int r = wav_linear(fmt, &k, &width, err, errlen);
+    if (r != 1) return r;
+    const uint64_t stride = (uint64_t)width * fmt.channels;
+    if (fmt.block_align != 0 && fmt.block_align != stride) return fail(err, errlen, "unsupported block alignment") - 1;
+    plan->lay.kind = core_kind(k), plan->lay.big = 0, plan->lay.width = width, plan->lay.channels = fmt.channels;
+    plan->rate = fmt.rate ? fmt.rate : 44100u;  // codec_params.sample_rate.unwrap_or(44100)
+    plan->data_off = (uint64_t)(data - fdata);
+    plan->frames = data_len / stride;
+    return 1;
+}
+
+bool decode_wav(const std::vector<uint8_t>& f, std::vector<float>* out, uint32_t* sr, char* err, uint64_t errlen) {
+    Fmt fmt;
+    const uint8_t* data = nullptr;
+    uint64_t data_len = 0;
+    if (!wav_parse(f.data(), f.size(), &fmt, &data, &data_len, err, errlen)) return false;
+    if (fmt.tag == 1 || fmt.tag == 3) {  // linear PCM: the plan, then pcm_core over its frames
+        sdsp_pcm_plan plan;
+        if (wav_plan(f.data(), f.size(), fmt, data, data_len, &plan, err, errlen) != 1) return false;
+        sdsp_pcm_convert_plan(f.data(), plan, out);
+        *sr = plan.rate;
+        return true;
+    }
+    Kind k;
+    int width;
+    if (fmt.tag == 6 && fmt.bits == 8) {
         k = Kind::ALAW, width = 1;
     } else if (fmt.tag == 7 && fmt.bits == 8) {
         k = Kind::ULAW, width = 1;
@@ -309,6 +348,17 @@ bool decode_wav(const std::vector<uint8_t>& f, std::vector<float>* out, uint32_t
 
 }  // namespace
 
+int sdsp_pcm_plan_wav(const uint8_t* f, size_t n, sdsp_pcm_plan* plan, std::string* err) {
+    char why[256] = {0};
+    Fmt fmt;
+    const uint8_t* data = nullptr;
+    uint64_t data_len = 0;
+    int r = -1;
+    if (wav_parse(f, n, &fmt, &data, &data_len, why, sizeof why)) r = wav_plan(f, n, fmt, data, data_len, plan, why, sizeof why);
+    if (r < 0) *err = why;
+    return r;
+}
+
 namespace {
 size_t id3_skip(const uint8_t* d, size_t n) {
     // an ID3v2 tag (10-byte header, syncsafe size) may precede FLAC or MP3 data
@@ -328,32 +378,39 @@ bool sdsp_is_native_flac(const uint8_t* d, size_t n) {
     return magic_at(d, n, 0, "fLaC") || (id3 && magic_at(d, n, id3, "fLaC"));
 }
 
+SdspFormat sdsp_probe_format(const uint8_t* d, size_t n) {
+    auto magic = [&](size_t off, const char* m) { return magic_at(d, n, off, m); };
+    const size_t id3 = id3_skip(d, n);
+    if (sdsp_is_native_flac(d, n)) return SdspFormat::FLAC;
+    if (magic(0, "FORM") && (magic(8, "AIFF") || magic(8, "AIFC"))) return SdspFormat::AIFF;
+    if (magic(0, "caff")) return SdspFormat::CAF;
+    if (magic(0, "OggS")) return SdspFormat::OGG;
+    if (n >= 4 && d[0] == 0x1A && d[1] == 0x45 && d[2] == 0xDF && d[3] == 0xA3) return SdspFormat::MKV;
+    if (magic(4, "ftyp")) return SdspFormat::MP4;
+    if (id3 || (n >= 2 && d[0] == 0xFF && (d[1] & 0xE0) == 0xE0)) return SdspFormat::MPEG;
+    return SdspFormat::WAV;
+}
+
 // The front-end on bytes in memory, by magic number; false with the reason in err.
 bool sdsp_decode_audio_bytes(const std::vector<uint8_t>& buf, std::vector<float>* mono_out, uint32_t* sr_out, char* err,
                              uint64_t errlen) {
     std::vector<float>& mono = *mono_out;
     uint32_t& sr = *sr_out;
-    auto magic = [&](size_t off, const char* m) { return magic_at(buf.data(), buf.size(), off, m); };
     const size_t id3 = id3_skip(buf.data(), buf.size());
     std::string why;
     bool ok;
-    if (sdsp_is_native_flac(buf.data(), buf.size())) {
-        ok = sdsp_decode_flac(buf, &mono, &sr, &why);
-    } else if (magic(0, "FORM") && (magic(8, "AIFF") || magic(8, "AIFC"))) {
-        ok = sdsp_decode_aiff(buf, &mono, &sr, &why);
-    } else if (magic(0, "caff")) {
-        ok = sdsp_decode_caf(buf, &mono, &sr, &why);
-    } else if (magic(0, "OggS")) {
-        ok = sdsp_decode_ogg(buf, &mono, &sr, &why);
-    } else if (buf.size() >= 4 && buf[0] == 0x1A && buf[1] == 0x45 && buf[2] == 0xDF && buf[3] == 0xA3) {
-        ok = sdsp_decode_mkv(buf, &mono, &sr, &why);
-    } else if (magic(4, "ftyp")) {
-        ok = sdsp_decode_mp4(buf, &mono, &sr, &why);
-    } else if (id3 || (buf.size() >= 2 && buf[0] == 0xFF && (buf[1] & 0xE0) == 0xE0)) {
-        ok = false, why = (buf.size() >= 2 && !id3 && (buf[1] & 0xF6) == 0xF0) ? "unsupported codec: AAC (ADTS)"
-                                                                             : "unsupported codec: MPEG audio (MP1/MP2/MP3)";
-    } else {
-        return decode_wav(buf, &mono, &sr, err, errlen);
+    switch (sdsp_probe_format(buf.data(), buf.size())) {
+        case SdspFormat::FLAC: ok = sdsp_decode_flac(buf, &mono, &sr, &why); break;
+        case SdspFormat::AIFF: ok = sdsp_decode_aiff(buf, &mono, &sr, &why); break;
+        case SdspFormat::CAF: ok = sdsp_decode_caf(buf, &mono, &sr, &why); break;
+        case SdspFormat::OGG: ok = sdsp_decode_ogg(buf, &mono, &sr, &why); break;
+        case SdspFormat::MKV: ok = sdsp_decode_mkv(buf, &mono, &sr, &why); break;
+        case SdspFormat::MP4: ok = sdsp_decode_mp4(buf, &mono, &sr, &why); break;
+        case SdspFormat::MPEG:
+            ok = false, why = (buf.size() >= 2 && !id3 && (buf[1] & 0xF6) == 0xF0) ? "unsupported codec: AAC (ADTS)"
+                                                                                 : "unsupported codec: MPEG audio (MP1/MP2/MP3)";
+            break;
+        default: return decode_wav(buf, &mono, &sr, err, errlen);
     }
     if (!ok) fail(err, errlen, why);
     return ok;

@@ -24,6 +24,8 @@
 #include <string>
 #include <vector>
 
+#include "lossless_host.hpp"
+
 bool sdsp_decode_flac(const std::vector<uint8_t>& f, std::vector<float>* out, uint32_t* sr, std::string* err);
 bool sdsp_decode_caf_alac(const std::vector<uint8_t>& f, std::vector<float>* out, uint32_t* sr, std::string* err);
 bool sdsp_decode_vorbis(const std::vector<std::vector<uint8_t>>& packets, int64_t last_granule, std::vector<float>* out,
@@ -57,37 +59,26 @@ int16_t ulaw16(uint8_t u) {
     return (int16_t)((u & 0x80) ? (0x84 - t) : (t - 0x84));
 }
 
-// One PCM sample layout; conv() gives the reference's f32 value of one channel sample.
+// One PCM sample layout; conv() gives the reference's f32 value of one channel sample: the linear
+// kinds through pcm_core.hpp (the code the device kernel runs), G.711 here.
 struct Pcm {
     enum Kind { S16, S24, S32, F32, F64, ALAW, ULAW } kind = S16;
     bool big = true;
     int width = 2;
+    bool linear() const { return kind != ALAW && kind != ULAW; }
+    int core_kind() const {
+        return kind == S16 ? pcm_core::S16 : kind == S24 ? pcm_core::S24 : kind == S32 ? pcm_core::S32
+               : kind == F32 ? pcm_core::F32 : pcm_core::F64;
+    }
+    pcm_core::Layout layout(int ch) const {
+        pcm_core::Layout l;
+        l.kind = core_kind(), l.big = big ? 1 : 0, l.width = width, l.channels = ch;
+        return l;
+    }
     float conv(const uint8_t* p) const {
-        switch (kind) {
-            case S16: return (float)(int16_t)(big ? be16(p) : (uint16_t)(p[0] | (p[1] << 8))) / 32768.0f;
-            case S24: {
-                int32_t v = big ? (int32_t)(((uint32_t)p[0] << 16) | ((uint32_t)p[1] << 8) | p[2])
-                                : (int32_t)(((uint32_t)p[2] << 16) | ((uint32_t)p[1] << 8) | p[0]);
-                if (v & 0x800000) v -= 0x1000000;
-                return (float)v / 8388608.0f;
-            }
-            case S32: return (float)(int32_t)(big ? be32(p) : le32(p)) / 2147483648.0f;
-            case F32: {
-                const uint32_t u = big ? be32(p) : le32(p);
-                float f;
-                std::memcpy(&f, &u, 4);
-                return f;
-            }
-            case F64: {
-                const uint64_t u = big ? be64(p) : le64(p);
-                double d;
-                std::memcpy(&d, &u, 8);
-                return (float)d;
-            }
-            case ALAW: return (float)alaw16(p[0]) / 32768.0f;
-            case ULAW: return (float)ulaw16(p[0]) / 32768.0f;
-        }
-        return 0.0f;
+        if (kind == ALAW) return (float)alaw16(p[0]) / 32768.0f;
+        if (kind == ULAW) return (float)ulaw16(p[0]) / 32768.0f;
+        return pcm_core::conv(core_kind(), big, pcm_core::load(p, width));
     }
 };
 
@@ -95,6 +86,11 @@ struct Pcm {
 void to_mono(const Pcm& pcm, int ch, const uint8_t* data, uint64_t frames, std::vector<float>* out) {
     out->resize(frames);
     const uint64_t stride = (uint64_t)pcm.width * (uint64_t)ch;
+    if (pcm.linear()) {
+        const pcm_core::Layout l = pcm.layout(ch);
+        for (uint64_t i = 0; i < frames; i++) (*out)[i] = pcm_core::frame_mono_bytes(l, data + i * stride);
+        return;
+    }
     for (uint64_t i = 0; i < frames; i++) {
         const uint8_t* p = data + i * stride;
         if (ch == 1) {
@@ -142,7 +138,16 @@ uint32_t ext80(const uint8_t* p) {
 }  // namespace
 
 // AIFF / AIFF-C: FORM container, COMM (channels, frames, sample size, rate[, compression]), SSND
-bool sdsp_decode_aiff(const std::vector<uint8_t>& f, std::vector<float>* out, uint32_t* sr, std::string* err) {
+namespace {
+// the parse: the sample layout, channel count, rate and the sample bytes (clipped to the file)
+bool aiff_parse(const uint8_t* fdata, size_t fsize, Pcm* pcm_out, int* ch_out, uint32_t* rate_out, const uint8_t** data_out,
+                uint64_t* data_len_out, std::string* err) {
+    struct {
+        const uint8_t* d;
+        size_t n;
+        size_t size() const { return n; }
+        const uint8_t* data() const { return d; }
+    } f{fdata, fsize};
     if (f.size() < 12) return fail(err, "malformed AIFF file");
     const bool aifc = std::memcmp(f.data() + 8, "AIFC", 4) == 0;
     int ch = 0, bits = 0;
@@ -164,7 +169,7 @@ bool sdsp_decode_aiff(const std::vector<uint8_t>& f, std::vector<float>* out, ui
             if (aifc) std::memcpy(comp, c + 26, 4);
             have_comm = true;
         } else if (std::memcmp(c, "SSND", 4) == 0) {
-            if (len < 8) return fail(err, "malformed SSND chunk");
+            if (len < 8 || avail < 8) return fail(err, "malformed SSND chunk");  // the offset field lies in the file
             const uint64_t off = be32(c + 8);
             const uint64_t body = (len <= avail ? len : avail);
             if (body < 8 + off) return fail(err, "malformed SSND chunk");
@@ -193,50 +198,102 @@ bool sdsp_decode_aiff(const std::vector<uint8_t>& f, std::vector<float>* out, ui
     } else {
         return fail(err, "unsupported AIFF-C compression type '" + cs + "'");
     }
-    to_mono(pcm, ch, data, data_len / ((uint64_t)pcm.width * (uint64_t)ch), out);
-    *sr = rate ? rate : 44100u;
+    *pcm_out = pcm, *ch_out = ch, *rate_out = rate ? rate : 44100u, *data_out = data, *data_len_out = data_len;
     return true;
+}
+}  // namespace
+
+bool sdsp_decode_aiff(const std::vector<uint8_t>& f, std::vector<float>* out, uint32_t* sr, std::string* err) {
+    Pcm pcm;
+    int ch = 0;
+    const uint8_t* data = nullptr;
+    uint64_t data_len = 0;
+    if (!aiff_parse(f.data(), f.size(), &pcm, &ch, sr, &data, &data_len, err)) return false;
+    to_mono(pcm, ch, data, data_len / ((uint64_t)pcm.width * (uint64_t)ch), out);
+    return true;
+}
+
+// the parse-only form: 1 planned, 0 G.711 (the host decoder's), -1 an error with its text
+int sdsp_pcm_plan_aiff(const uint8_t* f, size_t n, sdsp_pcm_plan* plan, std::string* err) {
+    Pcm pcm;
+    int ch = 0;
+    const uint8_t* data = nullptr;
+    uint64_t data_len = 0;
+    if (!aiff_parse(f, n, &pcm, &ch, &plan->rate, &data, &data_len, err)) return -1;
+    if (!pcm.linear()) return 0;
+    plan->lay = pcm.layout(ch);
+    plan->data_off = (uint64_t)(data - f);
+    plan->frames = data_len / ((uint64_t)pcm.width * (uint64_t)ch);
+    return 1;
+}
+
+void sdsp_pcm_convert_plan(const uint8_t* f, const sdsp_pcm_plan& plan, std::vector<float>* out) {
+    out->resize(plan.frames);
+    const uint64_t stride = (uint64_t)plan.lay.width * (uint64_t)plan.lay.channels;
+    for (uint64_t i = 0; i < plan.frames; i++) (*out)[i] = pcm_core::frame_mono_bytes(plan.lay, f + plan.data_off + i * stride);
 }
 
 // CAF: 'caff' header, 'desc' (rate f64, format id, flags, bytes / packet, frames / packet,
 // channels, bits), 'data' (edit count + audio; size -1 = to the end of the file)
-bool sdsp_decode_caf(const std::vector<uint8_t>& f, std::vector<float>* out, uint32_t* sr, std::string* err) {
-    if (f.size() < 8 || be16(f.data() + 4) != 1) return fail(err, "malformed CAF file");
-    bool have_desc = false;
+namespace {
+struct CafDesc {
     double rate = 0.0;
     char fmt[4] = {0, 0, 0, 0};
     uint32_t flags = 0, bpp = 0, fpp = 0, ch = 0, bits = 0;
     const uint8_t* data = nullptr;
     uint64_t data_len = 0;
+};
+// the checks that come before the format is looked at
+bool caf_parse(const uint8_t* fdata, size_t fsize, CafDesc* d, std::string* err) {
+    if (fsize < 8 || be16(fdata + 4) != 1) return fail(err, "malformed CAF file");
+    bool have_desc = false;
     size_t pos = 8;
-    while (pos + 12 <= f.size()) {
-        const uint8_t* c = f.data() + pos;
+    while (pos + 12 <= fsize) {
+        const uint8_t* c = fdata + pos;
         const int64_t slen = (int64_t)be64(c + 4);
-        const uint64_t avail = f.size() - (pos + 12);
+        const uint64_t avail = fsize - (pos + 12);
         if (std::memcmp(c, "desc", 4) == 0) {
             if (slen < 32 || (uint64_t)slen > avail) return fail(err, "malformed desc chunk");
             const uint64_t rb = be64(c + 12);
-            std::memcpy(&rate, &rb, 8);
-            std::memcpy(fmt, c + 20, 4);
-            flags = be32(c + 24);
-            bpp = be32(c + 28);
-            fpp = be32(c + 32);
-            ch = be32(c + 36);
-            bits = be32(c + 40);
+            std::memcpy(&d->rate, &rb, 8);
+            std::memcpy(d->fmt, c + 20, 4);
+            d->flags = be32(c + 24);
+            d->bpp = be32(c + 28);
+            d->fpp = be32(c + 32);
+            d->ch = be32(c + 36);
+            d->bits = be32(c + 40);
             have_desc = true;
         } else if (std::memcmp(c, "data", 4) == 0) {
             const uint64_t body = (slen < 0 || (uint64_t)slen > avail) ? avail : (uint64_t)slen;
             if (body < 4) return fail(err, "malformed data chunk");
-            data = c + 16;
-            data_len = body - 4;
+            d->data = c + 16;
+            d->data_len = body - 4;
             if (slen < 0) break;  // the data chunk runs to the end of the file
         }
         if (slen < 0) break;
         pos += 12 + (uint64_t)slen;
     }
     if (!have_desc) return fail(err, "missing desc chunk");
-    if (!data) return fail(err, "missing data chunk");
-    if (ch == 0 || ch > 64) return fail(err, "unsupported channel count");
+    if (!d->data) return fail(err, "missing data chunk");
+    if (d->ch == 0 || d->ch > 64) return fail(err, "unsupported channel count");
+    return true;
+}
+}  // namespace
+
+bool sdsp_caf_is_alac(const uint8_t* f, size_t n) {
+    CafDesc d;
+    std::string why;
+    return caf_parse(f, n, &d, &why) && std::memcmp(d.fmt, "alac", 4) == 0;
+}
+
+bool sdsp_decode_caf(const std::vector<uint8_t>& f, std::vector<float>* out, uint32_t* sr, std::string* err) {
+    CafDesc d;
+    if (!caf_parse(f.data(), f.size(), &d, err)) return false;
+    const double rate = d.rate;
+    const char* fmt = d.fmt;
+    const uint32_t flags = d.flags, bpp = d.bpp, fpp = d.fpp, ch = d.ch, bits = d.bits;
+    const uint8_t* data = d.data;
+    const uint64_t data_len = d.data_len;
     const std::string fs(fmt, 4);
     Pcm pcm;
     if (fs == "lpcm") {

@@ -17,6 +17,10 @@
 //           candidates in this order; a frame's decode depends on nothing but the file's bytes, so
 //           `ok`, `end` and the samples computed ahead of time are the ones the host would compute.
 //   gather  k_flac_gather: the accepted slots, copied to the file's contiguous output.
+// On the host the phases are FlacStage's steps (decode_stages.hpp): plan, run (scan, frames, chain:
+// the files' lengths), place, write (gather at a given base of the call's one output buffer).  Both
+// batch entries use them: sdsp_decode_flac_batch_device here, sdsp_decode_batch_device in
+// decode_batch.hip.
 #include <algorithm>
 #include <chrono>
 #include <cstdio>
@@ -30,23 +34,15 @@
 #include "../../include/stratum_hip_debug.h"
 #include "flac_core.hpp"
 #include "flac_host.hpp"
+#include "decode_stages.hpp"
 #include "flac_phased.hpp"
 #include "sdsp_runtime.hpp"
 
 namespace {
 
 using namespace sdsp;
+using namespace sdsp_dec;
 namespace fc = flac_core;
-
-// one file of the device path
-struct FlacFile {
-    uint64_t base;       // first byte in the bytes buffer (16-byte aligned)
-    uint64_t cand_base;  // first slot of the file's range in the scan's candidate list
-    uint32_t size;       // bytes (< 2^31)
-    uint32_t start;      // first byte of the frame region
-    uint32_t cand_cap;   // slots in that range
-    int32_t si_bps;      // STREAMINFO's bits per sample
-};
 
 constexpr uint32_t SCAN_BYTES = 16384;  // byte offsets per scan block
 constexpr uint32_t PACK_BS = 0xFFFFu;   // candidate word: (bs - 1) | bps << 16 | channel code << 22 | header bytes << 26
@@ -145,157 +141,65 @@ __global__ __launch_bounds__(256) void k_flac_gather(const float* __restrict__ s
 std::mutex g_stats_mu;
 std::map<int, sdsp_flac_decode_stats> g_stats;
 
-// pinned staging for the compressed bytes, grow-only, per device (used under the device's lock)
-struct Pinned {
-    uint8_t* p = nullptr;
-    size_t bytes = 0;
-    void ensure(size_t n) {
-        if (n <= bytes) return;
-        if (p) SDSP_HIP_CHECK(hipHostFree(p));
-        p = nullptr;
-        bytes = 0;
-        const size_t want = n + n / 8 + 4096;
-        SDSP_HIP_CHECK(hipHostMalloc((void**)&p, want, hipHostMallocDefault));
-        note_alloc(want);
-        bytes = want;
+}  // namespace
+
+namespace sdsp_dec {
+
+// stream-level parse; the file goes to the device, to the host decoder (past the budget) or fails
+void FlacStage::plan(Call& k, uint64_t i) {
+    sdsp_flac_stream si;
+    size_t start = 0;
+    std::string why;
+    if (!sdsp_flac_parse_stream(k.files[i], k.sizes[i], &si, &start, &why)) {
+        k.set_err(i, why);
+        return;
     }
-};
-std::map<int, Pinned> g_pinned;
-
-void set_err(char* errs, uint64_t i, const std::string& m) { std::snprintf(errs + 256 * i, 256, "%s", m.c_str()); }
-
-template <class T>
-void upload(DevBuf& b, const std::vector<T>& v, hipStream_t st) {
-    b.ensure(std::max<size_t>(v.size(), 1) * sizeof(T));
-    if (!v.empty()) SDSP_HIP_CHECK(hipMemcpyAsync(b.p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice, st));
+    k.rates[i] = si.rate ? si.rate : 44100u;
+    // bytes + candidate slots + sorted candidate arrays, then scratch and output by STREAMINFO's
+    // sample count (unknown: a generous multiple of the bytes); the scan's real figure is
+    // checked again in run()
+    const double est =
+        3.0 * (double)k.sizes[i] + 8.0 * (si.total_samples ? (double)si.total_samples : 16.0 * (double)k.sizes[i]);
+    if (k.need + est > k.budget) {
+        k.fallback.push_back(i);
+        return;
+    }
+    k.need += est;
+    est_sum += est;
+    FlacFile f{};
+    f.base = k.reserve_bytes(i);
+    f.cand_base = cand_total;
+    f.size = (uint32_t)k.sizes[i];
+    f.start = (uint32_t)start;
+    f.cand_cap = (uint32_t)(k.sizes[i] / 8 + 16);
+    f.si_bps = si.bps;
+    cand_total += f.cand_cap;
+    ft.push_back(f);
+    dev_idx.push_back(i);
 }
 
-struct HostTrack {  // a file decoded by the host decoder (fallback)
-    uint64_t file;
-    std::vector<float> mono;
-};
-
-double hbm_budget() {
-    double budget = 16e9;
-    size_t fr = 0, tot = 0;
-    if (hipMemGetInfo(&fr, &tot) == hipSuccess) budget = std::max(1e9, (double)fr * 0.80 / 1.125);
-    if (const double gb = test_hooks().hbm_budget_gb.load(); gb > 0.0) budget = std::max(1.0, gb) * 1e9;
-    return budget;
-}
-
-int32_t decode_batch(const uint8_t* const* files, const uint64_t* sizes, uint64_t n_files, int32_t device, void* stream,
-                     float** d_samples, uint64_t* offsets, uint64_t* lens, uint32_t* rates, int32_t* status, char* errs) {
-    const auto t_begin = std::chrono::steady_clock::now();
-    sdsp_flac_decode_stats stt{};
-    stt.files = n_files;
-    DeviceCtx& c = device_ctx(device);
-    std::lock_guard<std::mutex> lk(c.mu);
-    SDSP_HIP_CHECK(hipSetDevice(device));
-    hipStream_t st = stream ? (hipStream_t)stream : c.stream;
-
-    // ---- host setup: stream-level parse, which files the device takes ----
-    const double budget = hbm_budget();
-    // a wave's work range is at most 64 lanes x 8 channels x 65536 samples x 8 bytes = 256 MiB
-    const double work_budget = std::max(320e6, std::min(budget / 2, 24e9));
-    std::vector<FlacFile> ft;       // device files
-    std::vector<uint64_t> dev_idx;  // their indices in the call
-    std::vector<uint64_t> fallback; // files for the host decoder
-    uint64_t bytes_total = 0, cand_total = 0;
-    double need = work_budget;
-    for (uint64_t i = 0; i < n_files; i++) {
-        status[i] = SDSP_OK;
-        errs[256 * i] = 0;
-        offsets[i] = lens[i] = 0;
-        rates[i] = 0;
-        stt.bytes_in += sizes[i];
-        if (!files[i] || !sdsp_is_native_flac(files[i], sizes[i]) || sizes[i] >= (1ull << 31)) {
-            fallback.push_back(i);
-            continue;
-        }
-        sdsp_flac_stream si;
-        size_t start = 0;
-        std::string why;
-        if (!sdsp_flac_parse_stream(files[i], sizes[i], &si, &start, &why)) {
-            status[i] = SDSP_ERR_DECODING;
-            set_err(errs, i, why);
-            continue;
-        }
-        rates[i] = si.rate ? si.rate : 44100u;
-        // bytes + candidate slots + sorted candidate arrays, then scratch and output by STREAMINFO's
-        // sample count (unknown: a generous multiple of the bytes); the scan's real figure is
-        // checked again below
-        const double est = 3.0 * (double)sizes[i] + 8.0 * (si.total_samples ? (double)si.total_samples : 16.0 * (double)sizes[i]);
-        if (need + est > budget) {
-            fallback.push_back(i);
-            continue;
-        }
-        need += est;
-        FlacFile f{};
-        f.base = bytes_total;
-        f.cand_base = cand_total;
-        f.size = (uint32_t)sizes[i];
-        f.start = (uint32_t)start;
-        f.cand_cap = (uint32_t)(sizes[i] / 8 + 16);
-        f.si_bps = si.bps;
-        bytes_total += ((uint64_t)f.size + 15) / 16 * 16 + 16;
-        cand_total += f.cand_cap;
-        ft.push_back(f);
-        dev_idx.push_back(i);
-    }
-
-    hipEvent_t ev[6];
-    for (auto& e : ev) SDSP_HIP_CHECK(hipEventCreate(&e));
-    struct EvGuard {
-        hipEvent_t* e;
-        ~EvGuard() {
-            for (int i = 0; i < 6; i++) (void)hipEventDestroy(e[i]);
-        }
-    } evg{ev};
-
+void FlacStage::run(Call& k, DevBuf& b_bytes, hipEvent_t ev_scan, hipEvent_t ev_frames, hipEvent_t ev_chain) {
+    DeviceCtx& c = k.c;
+    hipStream_t st = k.st;
     const size_t nd = ft.size();
-    std::vector<uint64_t> f_len(nd, 0);
-    std::vector<uint32_t> f_acc(nd, 0), f_rej(nd, 0);
-    std::vector<uint8_t> on_device(nd, 1);
+    f_len.assign(nd, 0);
+    f_outoff.assign(nd, 0);
+    f_acc.assign(nd, 0);
+    f_rej.assign(nd, 0);
+    on_device.assign(nd, 1);
     // sorted candidates of the device files
     std::vector<uint32_t> c_file, c_off, c_pack, c_bs;
     std::vector<uint64_t> c_slot, f_first(nd, 0);
     std::vector<uint32_t> f_ncand(nd, 0);
     uint64_t scratch_total = 0;
-    DevBuf& b_bytes = c.buf("flac.bytes");
     DevBuf& b_files = c.buf("flac.files");
-    SDSP_HIP_CHECK(hipEventRecord(ev[0], st));
     if (nd) {
-        // ---- upload from pinned memory ----
-        Pinned* pinp;
-        {  // other devices' threads may add their entry at the same time; the reference stays valid
-            std::lock_guard<std::mutex> pl(g_stats_mu);
-            pinp = &g_pinned[device];
-        }
-        Pinned& pin = *pinp;
-        pin.ensure(bytes_total);
-        {  // the copy into the staging buffer is memory-bound on one core: a few threads for large batches
-            std::atomic<size_t> next{0};
-            auto copy = [&]() {
-                for (size_t k; (k = next++) < nd;) {
-                    std::memcpy(pin.p + ft[k].base, files[dev_idx[k]], ft[k].size);
-                    const uint64_t padded = ((uint64_t)ft[k].size + 15) / 16 * 16 + 16;
-                    std::memset(pin.p + ft[k].base + ft[k].size, 0, padded - ft[k].size);
-                }
-            };
-            const size_t nt = bytes_total > (64u << 20) ? std::min<size_t>(8, nd) : 1;
-            std::vector<std::thread> pool;
-            for (size_t t = 1; t < nt; t++) pool.emplace_back(copy);
-            copy();
-            for (auto& t : pool) t.join();
-        }
-        b_bytes.ensure(bytes_total);
-        SDSP_HIP_CHECK(hipMemcpyAsync(b_bytes.p, pin.p, bytes_total, hipMemcpyHostToDevice, st));
         upload(b_files, ft, st);
 
         // ---- scan ----
         std::vector<uint2> blocks;
-        for (size_t k = 0; k < nd; k++)
-            for (uint64_t o = ft[k].start & ~3u; o < ft[k].size; o += SCAN_BYTES) blocks.push_back(make_uint2((uint32_t)k, (uint32_t)o));
+        for (size_t q = 0; q < nd; q++)
+            for (uint64_t o = ft[q].start & ~3u; o < ft[q].size; o += SCAN_BYTES) blocks.push_back(make_uint2((uint32_t)q, (uint32_t)o));
         DevBuf& b_blocks = c.buf("flac.blocks");
         DevBuf& b_cnt = c.buf("flac.cnt");
         DevBuf& b_cand = c.buf("flac.cand");
@@ -307,55 +211,56 @@ int32_t decode_batch(const uint8_t* const* files, const uint64_t* sizes, uint64_
             hipLaunchKernelGGL(k_flac_scan, dim3((unsigned)blocks.size()), dim3(256), 0, st, b_bytes.as<uint8_t>(),
                                b_files.as<FlacFile>(), b_blocks.as<uint2>(), b_cnt.as<uint32_t>(), b_cand.as<uint2>());
         SDSP_HIP_CHECK(hipGetLastError());
-        SDSP_HIP_CHECK(hipEventRecord(ev[1], st));
+        SDSP_HIP_CHECK(hipEventRecord(ev_scan, st));
         std::vector<uint32_t> cnt(nd);
         SDSP_HIP_CHECK(hipMemcpyAsync(cnt.data(), b_cnt.p, nd * 4, hipMemcpyDeviceToHost, st));
         SDSP_HIP_CHECK(hipStreamSynchronize(st));
 
         // ---- candidates to the host: sort per file, lay out scratch; files past a bound fall back ----
         std::vector<std::vector<uint2>> fc_list(nd);
-        for (size_t k = 0; k < nd; k++) {
-            if (cnt[k] > ft[k].cand_cap) {  // denser than one per 8 bytes: the list lost entries
-                on_device[k] = 0;
+        for (size_t q = 0; q < nd; q++) {
+            if (cnt[q] > ft[q].cand_cap) {  // denser than one per 8 bytes: the list lost entries
+                on_device[q] = 0;
                 continue;
             }
-            fc_list[k].resize(cnt[k]);
-            if (cnt[k])
-                SDSP_HIP_CHECK(hipMemcpyAsync(fc_list[k].data(), b_cand.as<uint2>() + ft[k].cand_base, (size_t)cnt[k] * 8,
+            fc_list[q].resize(cnt[q]);
+            if (cnt[q])
+                SDSP_HIP_CHECK(hipMemcpyAsync(fc_list[q].data(), b_cand.as<uint2>() + ft[q].cand_base, (size_t)cnt[q] * 8,
                                               hipMemcpyDeviceToHost, st));
         }
         SDSP_HIP_CHECK(hipStreamSynchronize(st));
-        double used = work_budget;
-        for (size_t k = 0; k < nd; k++) {
-            if (!on_device[k]) continue;
-            std::vector<uint2>& l = fc_list[k];
+        // what plan() committed for these files is given back and the scan's real figure taken
+        double used = k.need - est_sum;
+        for (size_t q = 0; q < nd; q++) {
+            if (!on_device[q]) continue;
+            std::vector<uint2>& l = fc_list[q];
             std::sort(l.begin(), l.end(), [](const uint2& a, const uint2& b) { return a.x < b.x; });
             uint64_t sum_bs = 0;
-            for (const uint2& q : l) sum_bs += (q.y & PACK_BS) + 1;
-            const double real = 3.0 * (double)ft[k].size + 8.0 * (double)sum_bs + 40.0 * (double)l.size();
-            if (used + real > budget) {  // the candidates' samples need more than STREAMINFO promised
-                on_device[k] = 0;
+            for (const uint2& e : l) sum_bs += (e.y & PACK_BS) + 1;
+            const double real = 3.0 * (double)ft[q].size + 8.0 * (double)sum_bs + 40.0 * (double)l.size();
+            if (used + real > k.budget) {  // the candidates' samples need more than STREAMINFO promised
+                on_device[q] = 0;
                 continue;
             }
             used += real;
-            f_first[k] = c_off.size();
-            f_ncand[k] = (uint32_t)l.size();
-            for (const uint2& q : l) {
-                c_file.push_back((uint32_t)k);
-                c_off.push_back(q.x);
-                c_pack.push_back(q.y);
-                c_bs.push_back((q.y & PACK_BS) + 1);
+            f_first[q] = c_off.size();
+            f_ncand[q] = (uint32_t)l.size();
+            for (const uint2& e : l) {
+                c_file.push_back((uint32_t)q);
+                c_off.push_back(e.x);
+                c_pack.push_back(e.y);
+                c_bs.push_back((e.y & PACK_BS) + 1);
                 c_slot.push_back(scratch_total);
-                scratch_total += (q.y & PACK_BS) + 1;
+                scratch_total += (e.y & PACK_BS) + 1;
             }
         }
-        for (size_t k = 0; k < nd; k++)
-            if (!on_device[k]) fallback.push_back(dev_idx[k]);
+        k.need = used;
+        for (size_t q = 0; q < nd; q++)
+            if (!on_device[q]) k.fallback.push_back(dev_idx[q]);
     } else {
-        SDSP_HIP_CHECK(hipEventRecord(ev[1], st));
+        SDSP_HIP_CHECK(hipEventRecord(ev_scan, st));
     }
-    const uint64_t nc = c_off.size();
-    stt.candidates = nc;
+    nc = c_off.size();
 
     DevBuf& b_cfile = c.buf("flac.c_file");
     DevBuf& b_coff = c.buf("flac.c_off");
@@ -377,7 +282,7 @@ int32_t decode_batch(const uint8_t* const* files, const uint64_t* sizes, uint64_
             uint32_t cap = 0;
             for (uint64_t i = w * 64; i < std::min(nc, w * 64 + 64); i++)
                 cap = std::max(cap, (uint32_t)fc::channels_of((int)((c_pack[i] >> 22) & 15u)) * c_bs[i]);
-            if (acc && (double)(acc + 64ull * cap) * 8.0 > work_budget) {
+            if (acc && (double)(acc + 64ull * cap) * 8.0 > k.work_budget) {
                 passes.emplace_back(pass0, w);
                 pass0 = w;
                 acc = 0;
@@ -412,7 +317,7 @@ int32_t decode_batch(const uint8_t* const* files, const uint64_t* sizes, uint64_
             SDSP_HIP_CHECK(hipGetLastError());
         }
     }
-    SDSP_HIP_CHECK(hipEventRecord(ev[2], st));
+    SDSP_HIP_CHECK(hipEventRecord(ev_frames, st));
 
     // ---- chain ----
     DevBuf& b_ffirst = c.buf("flac.f_first");
@@ -442,69 +347,97 @@ int32_t decode_batch(const uint8_t* const* files, const uint64_t* sizes, uint64_
         SDSP_HIP_CHECK(hipMemcpyAsync(f_acc.data(), b_facc.p, nd * 4, hipMemcpyDeviceToHost, st));
         SDSP_HIP_CHECK(hipMemcpyAsync(f_rej.data(), b_frej.p, nd * 4, hipMemcpyDeviceToHost, st));
     }
-    SDSP_HIP_CHECK(hipEventRecord(ev[3], st));
+    SDSP_HIP_CHECK(hipEventRecord(ev_chain, st));
+}
+
+// the files' places in the one output buffer, from `total` on; returns the new total
+uint64_t FlacStage::place(Call& k, uint64_t total) {
+    for (size_t q = 0; q < ft.size(); q++) {
+        if (!on_device[q]) continue;
+        f_outoff[q] = total;
+        k.offsets[dev_idx[q]] = total;
+        k.lens[dev_idx[q]] = f_len[q];
+        total += f_len[q];
+        device_files++;
+        frames_accepted += f_acc[q];
+        frames_rejected += f_rej[q];
+    }
+    return total;
+}
+
+void FlacStage::write(Call& k, float* out) {
+    if (!nc) return;
+    DeviceCtx& c = k.c;
+    DevBuf& b_foutoff = c.buf("flac.f_outoff");
+    upload(b_foutoff, f_outoff, k.st);
+    hipLaunchKernelGGL(k_flac_gather, dim3((unsigned)nc), dim3(256), 0, k.st, c.buf("flac.scratch").as<float>(),
+                       c.buf("flac.c_slot").as<uint64_t>(), c.buf("flac.c_bs").as<uint32_t>(), c.buf("flac.c_out").as<uint64_t>(),
+                       c.buf("flac.c_file").as<uint32_t>(), b_foutoff.as<uint64_t>(), out);
+    SDSP_HIP_CHECK(hipGetLastError());
+}
+
+}  // namespace sdsp_dec
+
+namespace {
+
+int32_t decode_batch(const uint8_t* const* files, const uint64_t* sizes, uint64_t n_files, int32_t device, void* stream,
+                     float** d_samples, uint64_t* offsets, uint64_t* lens, uint32_t* rates, int32_t* status, char* errs) {
+    const auto t_begin = std::chrono::steady_clock::now();
+    sdsp_flac_decode_stats stt{};
+    stt.files = n_files;
+    DeviceCtx& c = device_ctx(device);
+    std::lock_guard<std::mutex> lk(c.mu);
+    SDSP_HIP_CHECK(hipSetDevice(device));
+    Call k(c, stream ? (hipStream_t)stream : c.stream, device);
+    k.files = files, k.sizes = sizes, k.n_files = n_files;
+    k.offsets = offsets, k.lens = lens, k.rates = rates, k.status = status, k.errs = errs;
+    hipStream_t st = k.st;
+
+    // ---- host setup: stream-level parse, which files the device takes ----
+    k.init_budget();
+    k.reset_outputs();
+    FlacStage flac;
+    for (uint64_t i = 0; i < n_files; i++) {
+        stt.bytes_in += sizes[i];
+        if (!files[i] || !sdsp_is_native_flac(files[i], sizes[i]) || sizes[i] >= (1ull << 31))
+            k.fallback.push_back(i);
+        else
+            flac.plan(k, i);
+    }
+
+    hipEvent_t ev[6];
+    for (auto& e : ev) SDSP_HIP_CHECK(hipEventCreate(&e));
+    struct EvGuard {
+        hipEvent_t* e;
+        ~EvGuard() {
+            for (int i = 0; i < 6; i++) (void)hipEventDestroy(e[i]);
+        }
+    } evg{ev};
+
+    SDSP_HIP_CHECK(hipEventRecord(ev[0], st));
+    DevBuf& b_bytes = k.upload_bytes();
+    flac.run(k, b_bytes, ev[1], ev[2], ev[3]);
+    stt.candidates = flac.nc;
 
     // ---- the files the device path did not take: the host decoder (overlaps the kernels) ----
-    std::vector<HostTrack> host_tracks;
-    for (uint64_t i : fallback) {
-        std::vector<uint8_t> buf;
-        if (files[i]) buf.assign(files[i], files[i] + sizes[i]);
-        HostTrack t;
-        t.file = i;
-        char why[256] = {0};
-        uint32_t sr = 0;
-        bool ok = false;
-        try {
-            ok = sdsp_decode_audio_bytes(buf, &t.mono, &sr, why, sizeof why);
-        } catch (const std::exception& e) {  // sizes a damaged header declares can make an allocation fail
-            std::snprintf(why, sizeof why, "decoding failed: %s", e.what());
-        }
-        if (!ok) {
-            status[i] = SDSP_ERR_DECODING;
-            set_err(errs, i, why);
-            rates[i] = 0;
-            continue;
-        }
-        rates[i] = sr;
-        host_tracks.push_back(std::move(t));
-    }
+    k.decode_fallbacks();
     SDSP_HIP_CHECK(hipStreamSynchronize(st));
 
     // ---- output layout, gather, fallback upload ----
-    uint64_t total = 0;
-    std::vector<uint64_t> f_outoff(nd, 0);
-    for (size_t k = 0; k < nd; k++) {
-        if (!on_device[k]) continue;
-        f_outoff[k] = total;
-        offsets[dev_idx[k]] = total;
-        lens[dev_idx[k]] = f_len[k];
-        total += f_len[k];
-        stt.device_files++;
-        stt.frames_accepted += f_acc[k];
-        stt.frames_rejected += f_rej[k];
-    }
-    for (HostTrack& t : host_tracks) {
-        offsets[t.file] = total;
-        lens[t.file] = t.mono.size();
-        total += t.mono.size();
-        stt.host_fallback_files++;
-    }
+    uint64_t total = flac.place(k, 0);
+    total = k.place_fallbacks(total);
+    stt.device_files = flac.device_files;
+    stt.frames_accepted = flac.frames_accepted;
+    stt.frames_rejected = flac.frames_rejected;
+    stt.host_fallback_files = k.host_tracks.size();
     for (uint64_t i = 0; i < n_files; i++) stt.error_files += status[i] != SDSP_OK;
     stt.samples_out = total;
     float* out = nullptr;  // the caller's: not one of the engine's grow-only buffers
     SDSP_HIP_CHECK(hipMalloc((void**)&out, std::max<uint64_t>(total, 1) * 4));
     try {
-        if (nc) {
-            DevBuf& b_foutoff = c.buf("flac.f_outoff");
-            upload(b_foutoff, f_outoff, st);
-            hipLaunchKernelGGL(k_flac_gather, dim3((unsigned)nc), dim3(256), 0, st, b_scratch.as<float>(), b_cslot.as<uint64_t>(),
-                               b_cbs.as<uint32_t>(), b_cout.as<uint64_t>(), b_cfile.as<uint32_t>(), b_foutoff.as<uint64_t>(), out);
-            SDSP_HIP_CHECK(hipGetLastError());
-        }
+        flac.write(k, out);
         SDSP_HIP_CHECK(hipEventRecord(ev[4], st));
-        for (HostTrack& t : host_tracks)
-            if (!t.mono.empty())
-                SDSP_HIP_CHECK(hipMemcpyAsync(out + offsets[t.file], t.mono.data(), t.mono.size() * 4, hipMemcpyHostToDevice, st));
+        k.upload_fallbacks(out);
         SDSP_HIP_CHECK(hipStreamSynchronize(st));
     } catch (...) {
         (void)hipFree(out);

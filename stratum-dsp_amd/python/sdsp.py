@@ -14,7 +14,7 @@ import subprocess
 
 import numpy as np
 
-from sdsp_abi import (ERROR_NAMES, FLAG_NAMES, SdspConfidence, SdspConfig, SdspFlacDecodeStats, SdspResult,
+from sdsp_abi import (ERROR_NAMES, FLAG_NAMES, SdspConfidence, SdspConfig, SdspDecodeStats, SdspFlacDecodeStats, SdspResult,
                       SdspStageTimes, result_to_dict)
 
 PKG = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -102,6 +102,13 @@ def _load(path):
         L.sdsp_debug_flac_decode_phased.argtypes = [C.c_char_p, C.c_uint64, C.POINTER(fp), u64p, u32p, u64p, C.c_char_p,
                                                     C.c_uint64]
         L.sdsp_debug_flac_decode_phased.restype = C.c_int32
+        L.sdsp_decode_batch_device.argtypes = L.sdsp_decode_flac_batch_device.argtypes
+        L.sdsp_decode_batch_device.restype = C.c_int32
+        L.sdsp_last_decode_stats.argtypes = [C.c_int32, C.POINTER(SdspDecodeStats)]
+        L.sdsp_last_decode_stats.restype = C.c_int32
+        for f in ("sdsp_debug_alac_decode_phased", "sdsp_debug_pcm_decode_planned"):
+            getattr(L, f).argtypes = L.sdsp_debug_flac_decode_phased.argtypes
+            getattr(L, f).restype = C.c_int32
         L.sdsp_free_samples.restype = None
         for f in ("sdsp_device_malloc", "sdsp_device_free", "sdsp_memcpy_h2d", "sdsp_memcpy_d2h",
                   "sdsp_device_synchronize", "sdsp_compute_confidence", "sdsp_key_name", "sdsp_decode_audio_file"):
@@ -328,12 +335,7 @@ def flac_decode_stats(device=0):
     return {k: getattr(t, k) for k, _ in SdspFlacDecodeStats._fields_}
 
 
-def decode_flac_batch_device(blobs, device=0, stream=None):
-    """sdsp_decode_flac_batch_device: the FLAC files in `blobs` (bytes objects) decoded on `device`.
-    Returns (DeviceBuffer of the concatenated mono f32 tracks, offsets, lens, rates, errors, stats):
-    track i is buffer[offsets[i] : offsets[i] + lens[i]] at rates[i]; errors[i] is None or the
-    AnalysisError sdsp.decode_audio_file raises for the same bytes (then lens[i] == 0).  Raises
-    AnalysisError when the call itself cannot run (no HIP device)."""
+def _decode_batch(entry, stats, what, blobs, device, stream):
     blobs = [bytes(b) for b in blobs]
     n = len(blobs)
     ptrs = (C.c_char_p * max(n, 1))(*blobs)
@@ -343,18 +345,42 @@ def decode_flac_batch_device(blobs, device=0, stream=None):
     errs = C.create_string_buffer(256 * max(n, 1))
     d = C.c_void_p()
     u64p = C.POINTER(C.c_uint64)
-    st = lib().sdsp_decode_flac_batch_device(ptrs, sizes.ctypes.data_as(u64p), n, device, C.c_void_p(stream or 0),
-                                             C.byref(d), offs.ctypes.data_as(u64p), lens.ctypes.data_as(u64p),
-                                             rates.ctypes.data_as(C.POINTER(C.c_uint32)),
-                                             status.ctypes.data_as(C.POINTER(C.c_int32)), errs)
+    st = entry(ptrs, sizes.ctypes.data_as(u64p), n, device, C.c_void_p(stream or 0),
+               C.byref(d), offs.ctypes.data_as(u64p), lens.ctypes.data_as(u64p),
+               rates.ctypes.data_as(C.POINTER(C.c_uint32)),
+               status.ctypes.data_as(C.POINTER(C.c_int32)), errs)
     text = [errs.raw[256 * i:256 * (i + 1)].split(b"\0", 1)[0].decode(errors="replace") for i in range(n)]
     if st != 0:
-        raise AnalysisError(st, text[0] if n and text[0] else "device FLAC decode failed")
+        raise AnalysisError(st, text[0] if n and text[0] else what + " failed")
     buf = DeviceBuffer.__new__(DeviceBuffer)
     buf.device, buf.ptr = device, d.value
     buf.n = int((offs[:n] + lens[:n]).max()) if n else 0
     errors = [AnalysisError(int(status[i]), "Decoding error: " + text[i]) if status[i] != 0 else None for i in range(n)]
-    return buf, offs[:n].copy(), lens[:n].copy(), rates[:n].copy(), errors, flac_decode_stats(device)
+    return buf, offs[:n].copy(), lens[:n].copy(), rates[:n].copy(), errors, stats(device)
+
+
+def decode_flac_batch_device(blobs, device=0, stream=None):
+    """sdsp_decode_flac_batch_device: the FLAC files in `blobs` (bytes objects) decoded on `device`.
+    Returns (DeviceBuffer of the concatenated mono f32 tracks, offsets, lens, rates, errors, stats):
+    track i is buffer[offsets[i] : offsets[i] + lens[i]] at rates[i]; errors[i] is None or the
+    AnalysisError sdsp.decode_audio_file raises for the same bytes (then lens[i] == 0).  Raises
+    AnalysisError when the call itself cannot run (no HIP device)."""
+    return _decode_batch(lib().sdsp_decode_flac_batch_device, flac_decode_stats, "device FLAC decode", blobs, device, stream)
+
+
+def decode_stats(device=0):
+    """sdsp_last_decode_stats: counters and phase times of the last sdsp_decode_batch_device call on `device`."""
+    t = SdspDecodeStats()
+    if lib().sdsp_last_decode_stats(device, C.byref(t)) != 0:
+        raise RuntimeError("sdsp_last_decode_stats failed")
+    return {k: getattr(t, k) for k, _ in SdspDecodeStats._fields_}
+
+
+def decode_batch_device(blobs, device=0, stream=None):
+    """sdsp_decode_batch_device: the files in `blobs` (bytes objects: FLAC, ALAC in M4A / CAF, WAV, AIFF
+    on the device; anything else the front-end reads through the host decoder) decoded into one
+    device buffer.  Returns the same tuple as decode_flac_batch_device, with the decode_stats dict."""
+    return _decode_batch(lib().sdsp_decode_batch_device, decode_stats, "device decode", blobs, device, stream)
 
 
 def debug_flac_decode_phased(data):
@@ -375,6 +401,39 @@ def debug_flac_decode_phased(data):
     finally:
         lib().sdsp_free_samples(p)
     return x, sr.value, tuple(int(v) for v in counts)
+
+
+def _debug_decode(entry, data, n_info):
+    data = bytes(data)
+    p = C.POINTER(C.c_float)()
+    n = C.c_uint64()
+    sr = C.c_uint32()
+    info = (C.c_uint64 * n_info)()
+    err = C.create_string_buffer(512)
+    st = entry(data, len(data), C.byref(p), C.byref(n), C.byref(sr), info, err, 512)
+    if st != 0:
+        text = err.value.decode(errors="replace")
+        raise AnalysisError(st, ("Decoding error: " if st == 2 else "Not implemented: ") + text)
+    try:
+        x = np.ctypeslib.as_array(p, shape=(n.value,)).copy() if n.value else np.zeros(0, np.float32)
+    finally:
+        lib().sdsp_free_samples(p)
+    return x, sr.value, tuple(int(v) for v in info)
+
+
+def debug_alac_decode_phased(data):
+    """sdsp_debug_alac_decode_phased: the device ALAC decoder's phases on the CPU.  Returns (mono
+    float32 array, sample_rate, (packets, decoded, skipped)); raises AnalysisError as decode_audio_file
+    does, or AnalysisError(NotImplemented, "... not planned ...") for bytes that are no ALAC container."""
+    return _debug_decode(lib().sdsp_debug_alac_decode_phased, data, 3)
+
+
+def debug_pcm_decode_planned(data):
+    """sdsp_debug_pcm_decode_planned: the host plan, then pcm_core over the planned frames.  Returns
+    (mono float32 array, sample_rate, (kind | big << 8, channels, data offset, frames)); raises
+    AnalysisError as decode_audio_file does, or AnalysisError(NotImplemented, "... not planned ...")
+    for a file that is not linear PCM in RIFF/WAVE or AIFF."""
+    return _debug_decode(lib().sdsp_debug_pcm_decode_planned, data, 4)
 
 
 class ResultBatch:

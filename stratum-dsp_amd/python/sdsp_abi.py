@@ -227,6 +227,31 @@ class SdspFlacDecodeStats(C.Structure):
     ]
 
 
+class SdspDecodeStats(C.Structure):
+    """sdsp_decode_stats: counters and phase times of the last sdsp_decode_batch_device call."""
+
+    _fields_ = [
+        ("files", u64),
+        ("device_files", u64),
+        ("host_fallback_files", u64),
+        ("error_files", u64),
+        ("flac_files", u64),
+        ("alac_files", u64),
+        ("pcm_files", u64),
+        ("alac_packets", u64),
+        ("alac_packets_decoded", u64),
+        ("alac_packets_skipped", u64),
+        ("bytes_in", u64),
+        ("samples_out", u64),
+        ("upload_ms", C.c_double),
+        ("flac_ms", C.c_double),
+        ("alac_ms", C.c_double),
+        ("pcm_ms", C.c_double),
+        ("gather_ms", C.c_double),
+        ("total_ms", C.c_double),
+    ]
+
+
 class SdspConfidence(C.Structure):
     _fields_ = [
         ("bpm_confidence", f32),
