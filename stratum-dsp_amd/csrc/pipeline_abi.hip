@@ -1,0 +1,549 @@
+// pipeline_abi.hip — the C ABI entry points over the pipeline (sdsp_analyze_audio / _batch /
+// _batch_device, the stage probes, synthetic tracks): result assembly, the certified key rerun of
+// the last sub-batch's near-decision tracks, the per-device staging pool of sdsp_analyze_batch.
+#include <atomic>
+#include <condition_variable>
+#include <mutex>
+#include <thread>
+
+#include "batch_sched.hpp"
+#include "pipeline.hpp"
+
+namespace sdsp {
+namespace {
+
+std::string fmt2(float v) {
+    char b[64];
+    std::snprintf(b, sizeof b, "%.2f", (double)v);
+    return b;
+}
+
+char* dup_str(const std::string& s) {
+    char* p = (char*)std::malloc(s.size() + 1);
+    std::memcpy(p, s.c_str(), s.size() + 1);
+    return p;
+}
+float* dup_f(const std::vector<float>& v) {
+    if (v.empty()) return nullptr;
+    float* p = (float*)std::malloc(v.size() * sizeof(float));
+    std::memcpy(p, v.data(), v.size() * sizeof(float));
+    return p;
+}
+
+// result assembly + warnings (src/lib.rs:1561-1619)
+void fill_result(const TrackRes& r, uint32_t sr, float ms, sdsp_result* o) {
+    std::memset(o, 0, sizeof(*o));
+    o->status = r.status;
+    o->tempogram_multi_res_triggered = o->tempogram_multi_res_used = -1;
+    o->tempogram_percussive_triggered = o->tempogram_percussive_used = -1;
+    if (r.status != SDSP_OK) {
+        std::snprintf(o->error_message, sizeof o->error_message, "%s", r.err.c_str());
+        return;
+    }
+    o->bpm = r.bpm;
+    o->bpm_confidence = r.bpm_conf;
+    o->key_mode = r.key_mode;
+    o->key_tonic = (uint32_t)r.key_tonic;
+    o->key_confidence = r.key_conf;
+    o->key_clarity = r.key_clarity;
+    o->beats = dup_f(r.beats);
+    o->n_beats = r.beats.size();
+    o->downbeats = dup_f(r.downs);
+    o->n_downbeats = r.downs.size();
+    o->bars = dup_f(r.downs);
+    o->n_bars = r.downs.size();
+    o->grid_stability = r.stability;
+    o->duration_seconds = r.duration;
+    o->sample_rate = sr;
+    o->processing_time_ms = ms;
+    std::snprintf(o->algorithm_version, sizeof o->algorithm_version, "0.1.0-alpha");
+    o->onset_method_consensus = r.onset_consensus;
+    o->methods_used = 7;
+    std::vector<std::string> w;
+    if (r.bpm == 0.0f) w.push_back("BPM detection failed: insufficient onsets or estimation error");
+    if (r.stability < 0.5f) w.push_back("Low beat grid stability: " + fmt2(r.stability) + " (may indicate tempo variation)");
+    if (r.key_conf < 0.3f)
+        w.push_back("Low key detection confidence: " + fmt2(r.key_conf) + " (may indicate ambiguous or atonal music)");
+    if (r.key_clarity < 0.2f) {
+        w.push_back("Low key clarity: " + fmt2(r.key_clarity) + " (track may be atonal or have weak tonality)");
+        o->flags |= SDSP_FLAG_WEAK_TONALITY;
+    }
+    o->n_warnings = w.size();
+    if (!w.empty()) {
+        o->warnings = (char**)std::malloc(w.size() * sizeof(char*));
+        for (size_t i = 0; i < w.size(); i++) o->warnings[i] = dup_str(w[i]);
+    }
+    o->has_tempogram_candidates = r.has_cands;
+    if (r.has_cands && !r.cands.empty()) {
+        o->n_tempogram_candidates = r.cands.size();
+        o->tempogram_candidates = (sdsp_tempo_candidate*)std::malloc(r.cands.size() * sizeof(sdsp_tempo_candidate));
+        std::memcpy(o->tempogram_candidates, r.cands.data(), r.cands.size() * sizeof(sdsp_tempo_candidate));
+    }
+    o->tempogram_multi_res_triggered = r.mr_trig;
+    o->tempogram_multi_res_used = r.mr_used;
+    o->tempogram_percussive_triggered = r.perc_trig;
+    o->tempogram_percussive_used = r.perc_used;
+}
+
+// One device-resident batch on `device`.  The engine's main stream first waits for `user_stream`
+// (everything queued on it so far) and for `wait_ev` (a copy's completion), whichever are given.
+// The batch on a context whose mutex the caller holds (run_device, and sdsp_analyze_audio's
+// direct path, which stages its one track into a context buffer under the same lock).
+int32_t run_locked(DeviceCtx& d, const float* d_samples, const uint64_t* offsets, const uint64_t* lens, uint64_t n,
+                   uint32_t sr, const sdsp_config* cfg, void* user_stream, sdsp_result* outs, int stages,
+                   hipEvent_t wait_ev) {
+    if (stages != SDSP_STAGES_FULL && stages != SDSP_STAGES_BPM_ONLY) throw HipError("unknown stage mask");
+    if (user_stream) {
+        hipEvent_t ev;
+        SDSP_HIP_CHECK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+        SDSP_HIP_CHECK(hipEventRecord(ev, (hipStream_t)user_stream));
+        SDSP_HIP_CHECK(hipStreamWaitEvent(d.stream, ev, 0));
+        SDSP_HIP_CHECK(hipEventDestroy(ev));
+    }
+    if (wait_ev) SDSP_HIP_CHECK(hipStreamWaitEvent(d.stream, wait_ev, 0));
+    auto t0 = std::chrono::steady_clock::now();
+    std::vector<uint64_t> off(offsets, offsets + n), ln(lens, lens + n);
+    std::vector<TrackRes> res;
+    Pipeline p(d, *cfg, sr, stages);
+    try {
+        p.run(d_samples, off, ln, res);
+        // Certified block energies: a track whose key vote had an energy-dependent
+        // decision within its margin (KeyOut::near) has its key path run again with the reference's
+        // sequential frame-energy fold, and those key fields replace its own (everything else is
+        // independent of the key energies).
+        std::vector<size_t> near;
+        d.last_near.assign(res.size(), 0);
+        for (size_t i = 0; i < res.size(); i++) {
+            if (res[i].key_near) d.last_near[i] = (uint8_t)res[i].key_near;
+            if (res[i].key_near && !res[i].key_rerun) near.push_back(i);  // the last sub-batch's
+        }
+        if (!near.empty()) {
+            const sdsp_stage_times first = d.last;
+            std::vector<uint64_t> o2, l2;
+            for (size_t i : near) o2.push_back(off[i]), l2.push_back(ln[i]);
+            std::vector<TrackRes> r2;
+            Pipeline px(d, *cfg, sr, stages, true, true);
+            px.run(d_samples, o2, l2, r2);
+            for (size_t j = 0; j < near.size(); j++) {
+                TrackRes& r = res[near[j]];
+                if (r2[j].status != SDSP_OK) {  // (the same front end as the main pass) uncertified: fail
+                    r.status = SDSP_ERR_PROCESSING;
+                    r.err = "Processing error: key certification rerun failed (" + r2[j].err + ")";
+                    continue;
+                }
+                set_key_fields(r, r2[j]);
+            }
+            // the call's stage times stay the main pass's; the rerun is reported beside them
+            const double rerun_ms = d.last.total_ms;
+            d.last = first;
+            d.last.key_reruns += near.size();
+            d.last.rerun_ms += rerun_ms;
+            d.last.total_ms += rerun_ms;
+        }
+    } catch (...) {
+        // a sub-batch may have queued key-stream work (the late join) before a later one threw:
+        // nothing of this call may still run on the engine's streams once the context lock is
+        // released, or the next call's uploads into the same context buffers would race it
+        for (hipStream_t s : d.own) (void)hipStreamSynchronize(s);
+        throw;
+    }
+    const float ms = (float)(std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count() /
+                             (double)std::max<uint64_t>(n, 1));
+    for (uint64_t i = 0; i < n; i++) fill_result(res[(size_t)i], sr, ms, &outs[i]);
+    return SDSP_OK;
+}
+
+int32_t run_device(int device, const float* d_samples, const uint64_t* offsets, const uint64_t* lens, uint64_t n,
+                   uint32_t sr, const sdsp_config* cfg, void* user_stream, sdsp_result* outs,
+                   int stages = SDSP_STAGES_FULL, hipEvent_t wait_ev = nullptr) {
+    DeviceCtx& d = device_ctx(device);
+    std::lock_guard<std::mutex> lk(d.mu);
+    SDSP_HIP_CHECK(hipSetDevice(device));
+    return run_locked(d, d_samples, offsets, lens, n, sr, cfg, user_stream, outs, stages, wait_ev);
+}
+
+}  // namespace
+}  // namespace sdsp
+
+using namespace sdsp;
+
+namespace sdsp {
+namespace {
+struct Slot {
+    float* d = nullptr;
+    uint64_t cap = 0;  // floats
+    hipEvent_t ready = nullptr;
+};
+// A device's staging area: its copy stream and two HBM slots.  Areas are pooled per device and
+// reused by later calls (grow-only slots, like the engine's own buffers), so a repeated call
+// creates no stream, event or allocation; concurrent callers on one device take separate areas.
+struct DeviceStage {
+    int dev = 0;
+    hipStream_t copy = nullptr;
+    Slot slot[2];
+};
+std::mutex g_stage_mu;
+std::map<int, std::vector<DeviceStage*>>* g_stage_free = new std::map<int, std::vector<DeviceStage*>>();  // never freed:
+// the areas outlive the call and are released with the process (no HIP calls at static teardown)
+DeviceStage* stage_acquire(int dev) {
+    std::lock_guard<std::mutex> lk(g_stage_mu);
+    auto& v = (*g_stage_free)[dev];
+    if (!v.empty()) {
+        DeviceStage* ds = v.back();
+        v.pop_back();
+        return ds;
+    }
+    DeviceStage* ds = new DeviceStage();
+    ds->dev = dev;
+    return ds;
+}
+void stage_release(DeviceStage* ds) {
+    if (ds->copy) {  // nothing may still be copying into the slots the next caller receives
+        (void)hipSetDevice(ds->dev);
+        (void)hipStreamSynchronize(ds->copy);
+    }
+    std::lock_guard<std::mutex> lk(g_stage_mu);
+    (*g_stage_free)[ds->dev].push_back(ds);
+}
+// test hook (sdsp_debug_set_test_hooks): the worker devices of sdsp_analyze_batch, repeats
+// allowed (two workers on device 0 exercise the multi-device chunk path on a one-GPU box)
+// (compiled only into the test build, -DSDSP_TEST_HOOKS: the shipping library cannot be re-routed)
+std::vector<int> device_list_override(int ndev) {
+    std::vector<int> devs;
+#ifdef SDSP_TEST_HOOKS
+    for (int v : test_hooks_devices())
+        if (v >= 0 && v < ndev) devs.push_back(v);
+#endif
+    return devs;
+}
+}  // namespace
+}  // namespace sdsp
+
+// Stage probes (include/stratum_hip_debug.h): a probe pipeline on the device context, whose "D."
+// buffers are released again, so an analysis call finds the context as it left it.
+namespace sdsp {
+namespace {
+template <class F>
+int32_t run_stage_probe(const char* name, int32_t device, F f) {
+    try {
+        DeviceCtx& d = device_ctx(device);
+        std::lock_guard<std::mutex> lk(d.mu);
+        SDSP_HIP_CHECK(hipSetDevice(device));
+        int32_t rc = SDSP_OK;
+        try {
+            f(d);
+        } catch (const std::invalid_argument& e) {
+            std::fprintf(stderr, "%s: %s\n", name, e.what());
+            rc = SDSP_ERR_INVALID_INPUT;
+        } catch (const std::exception& e) {
+            std::fprintf(stderr, "%s: %s\n", name, e.what());
+            rc = SDSP_ERR_PROCESSING;
+        }
+        for (hipStream_t s : d.own) (void)hipStreamSynchronize(s);
+        for (auto it = d.bufs.begin(); it != d.bufs.end();)
+            it = it->first.compare(0, 2, "D.") == 0 ? d.bufs.erase(it) : std::next(it);
+        return rc;
+    } catch (const std::exception& e) {
+        std::fprintf(stderr, "%s: %s\n", name, e.what());
+        return SDSP_ERR_PROCESSING;
+    }
+}
+}  // namespace
+}  // namespace sdsp
+
+
+extern "C" {
+
+int32_t sdsp_analyze_batch_device(const float* d_samples, const uint64_t* offsets, const uint64_t* lens,
+                                  uint64_t n_tracks, uint32_t sample_rate, const sdsp_config* cfg, int32_t device,
+                                  void* stream, sdsp_result* outs) {
+    return sdsp_analyze_batch_device_ex(d_samples, offsets, lens, n_tracks, sample_rate, cfg, device, stream,
+                                        SDSP_STAGES_FULL, outs);
+}
+
+int32_t sdsp_analyze_batch_device_ex(const float* d_samples, const uint64_t* offsets, const uint64_t* lens,
+                                     uint64_t n_tracks, uint32_t sample_rate, const sdsp_config* cfg, int32_t device,
+                                     void* stream, int32_t stages, sdsp_result* outs) {
+    try {
+        return run_device(device, d_samples, offsets, lens, n_tracks, sample_rate, cfg, stream, outs, stages);
+    } catch (const std::exception& e) {
+        std::fprintf(stderr, "sdsp_analyze_batch_device: %s\n", e.what());
+        for (uint64_t i = 0; i < n_tracks; i++) {
+            std::memset(&outs[i], 0, sizeof(outs[i]));
+            outs[i].status = SDSP_ERR_PROCESSING;
+            std::snprintf(outs[i].error_message, sizeof outs[i].error_message, "Processing error: %s", e.what());
+        }
+        return SDSP_ERR_PROCESSING;
+    }
+}
+
+// Whether `cfg` at `sample_rate` takes the default key path's block-folded HPCP frame energies
+// (include/stratum_hip_debug.h): the parity tests then compare key_confidence / key_clarity with
+// the oracle within the north star's tolerance, and every other configuration bit for bit.
+int32_t sdsp_debug_key_energy_blocked(const sdsp_config* cfg, uint32_t sample_rate) {
+    if (!cfg || sample_rate == 0) return -1;
+    return key_energy_blocked(*cfg, sample_rate) ? 1 : 0;
+}
+
+// Per track of the last sdsp_analyze_batch_device / sdsp_analyze_audio call on `device`: 1 where
+// its key vote was near an energy-dependent decision and the track was analysed again exactly.
+int32_t sdsp_debug_last_key_near(int32_t device, uint8_t* out, uint64_t n) {
+    try {
+        DeviceCtx& d = device_ctx(device);
+        std::lock_guard<std::mutex> lk(d.mu);
+        for (uint64_t i = 0; i < n; i++) out[i] = i < d.last_near.size() ? d.last_near[(size_t)i] : 0;
+        return SDSP_OK;
+    } catch (const std::exception&) {
+        return SDSP_ERR_PROCESSING;
+    }
+}
+
+// Tracks the last call on `device` reran in place (Pipeline::rerun_tail).
+int32_t sdsp_debug_last_tail_reruns(int32_t device, uint64_t* n_tracks) {
+    try {
+        if (!n_tracks) return SDSP_ERR_INVALID_INPUT;
+        DeviceCtx& d = device_ctx(device);
+        std::lock_guard<std::mutex> lk(d.mu);
+        *n_tracks = d.last_tail_reruns;
+        return SDSP_OK;
+    } catch (const std::exception&) {
+        return SDSP_ERR_PROCESSING;
+    }
+}
+
+int32_t sdsp_debug_tempo_stages(const float* host_mags, const uint64_t* frames, uint64_t n_tracks, uint32_t sample_rate,
+                                uint32_t hop, const sdsp_config* cfg, sdsp_debug_tempo_out* out, int32_t device) {
+    if (!host_mags || !frames || !cfg || !out || n_tracks == 0 || n_tracks > (1u << 20) || sample_rate == 0 || hop == 0 ||
+        hop > 8192)
+        return SDSP_ERR_INVALID_INPUT;
+    for (uint64_t t = 0; t < n_tracks; t++)
+        if (frames[t] == 0 || frames[t] > (1u << 24)) return SDSP_ERR_INVALID_INPUT;
+    return run_stage_probe("sdsp_debug_tempo_stages", device, [&](DeviceCtx& d) {
+        Pipeline p(d, *cfg, sample_rate, SDSP_STAGES_FULL, false, false, false, true);
+        p.debug_tempo_stages(host_mags, frames, n_tracks, (int)hop, out);
+    });
+}
+
+int32_t sdsp_debug_key_stages(const float* host_mags, const uint64_t* frames, uint64_t n_tracks, uint32_t sample_rate,
+                              const sdsp_config* cfg, int32_t mode, float* masked, float* chroma, float* energy,
+                              float* edel, int32_t info[4], int32_t device) {
+    if (!host_mags || !frames || !cfg || !masked || !chroma || !energy || !info || n_tracks == 0 ||
+        n_tracks > (1u << 20) || sample_rate == 0 || mode < 0 || mode > 2)
+        return SDSP_ERR_INVALID_INPUT;
+    for (uint64_t t = 0; t < n_tracks; t++)
+        if (frames[t] == 0 || frames[t] > (1u << 24)) return SDSP_ERR_INVALID_INPUT;
+    return run_stage_probe("sdsp_debug_key_stages", device, [&](DeviceCtx& d) {
+        Pipeline p(d, *cfg, sample_rate, SDSP_STAGES_FULL, mode == 2, false, false, true);
+        p.debug_key_stages(host_mags, frames, n_tracks, mode, masked, chroma, energy, edel, info);
+    });
+}
+
+// Host buffers: chunks of whole tracks (up to SDSP_BATCH_CHUNK_TRACKS tracks, default
+// 512, and about 8 GB) pulled from a shared counter by one worker per device; per device a copier
+// thread stages the next chunk into the second of two HBM slots (its own stream, completion
+// signalled by an event the engine's stream waits on) while the device analyses the current one.
+// The queue itself is batch_sched.hpp (host-only, tested with fake devices).
+int32_t sdsp_analyze_batch(const float* const* tracks, const uint64_t* lens, uint64_t n_tracks, uint32_t sample_rate,
+                           const sdsp_config* cfg, uint32_t device_mask, sdsp_result* outs) {
+    std::vector<int> devs;
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
+        for (uint64_t i = 0; i < n_tracks; i++) {
+            std::memset(&outs[i], 0, sizeof(outs[i]));
+            outs[i].status = SDSP_ERR_PROCESSING;
+            std::snprintf(outs[i].error_message, sizeof outs[i].error_message, "Processing error: no HIP device");
+        }
+        return SDSP_ERR_PROCESSING;
+    }
+    devs = device_list_override(ndev);
+    if (devs.empty())
+        for (int d = 0; d < ndev && d < 32; d++)
+            if (device_mask == 0 ? d == 0 : ((device_mask >> d) & 1u)) devs.push_back(d);
+    if (devs.empty()) devs.push_back(0);
+    uint64_t max_tracks = 512;
+    if (const uint64_t t = test_hooks().batch_chunk_tracks.load()) max_tracks = t;  // sdsp_debug_set_schedule
+    const std::vector<uint64_t> cb = plan_chunks(lens, n_tracks, max_tracks, (uint64_t)2 << 30 /* 8 GB of f32 */);
+    // test hook (sdsp_debug_set_test_hooks): the chunk whose analysis throws (the per-chunk failure path)
+#ifdef SDSP_TEST_HOOKS
+    const long fail_chunk = test_hooks().fail_chunk.load();
+#endif
+    const size_t n_chunks = cb.size() - 1;
+    // every result starts as an error; run_device overwrites the tracks it analyses
+    auto mark_failed = [&](size_t c, const std::string& what) {
+        for (uint64_t i = cb[c]; i < cb[c + 1]; i++) {
+            std::memset(&outs[i], 0, sizeof(outs[i]));
+            outs[i].status = SDSP_ERR_PROCESSING;
+            std::snprintf(outs[i].error_message, sizeof outs[i].error_message, "Processing error: %s", what.c_str());
+        }
+    };
+    for (size_t c = 0; c < n_chunks; c++) mark_failed(c, "track not analysed");
+    std::vector<DeviceStage*> stg;
+    std::vector<ChunkDevice> cds;
+    for (int dev : devs) {
+        stg.push_back(stage_acquire(dev));
+        DeviceStage* ds = stg.back();
+        ChunkDevice cd;
+        cd.stage = [ds, &cb, tracks, lens](int s, size_t c) {
+            SDSP_HIP_CHECK(hipSetDevice(ds->dev));
+            if (!ds->copy) SDSP_HIP_CHECK(hipStreamCreateWithFlags(&ds->copy, hipStreamNonBlocking));
+            Slot& sl = ds->slot[s];
+            if (!sl.ready) SDSP_HIP_CHECK(hipEventCreateWithFlags(&sl.ready, hipEventDisableTiming));
+            uint64_t tot = 0;
+            for (uint64_t i = cb[c]; i < cb[c + 1]; i++) tot += lens[i];
+            if (sl.cap < tot) {
+                if (sl.d) SDSP_HIP_CHECK(hipFree(sl.d));
+                sl.d = nullptr;
+                sl.cap = 0;
+                const uint64_t want = std::max<uint64_t>(tot + tot / 8, 1);  // grow-only, with slack
+                SDSP_HIP_CHECK(hipMalloc(&sl.d, want * sizeof(float)));
+                note_alloc(want * sizeof(float));
+                sl.cap = want;
+            }
+            uint64_t o = 0;
+            for (uint64_t i = cb[c]; i < cb[c + 1]; i++) {
+                if (lens[i])
+                    SDSP_HIP_CHECK(hipMemcpyAsync(sl.d + o, tracks[i], lens[i] * sizeof(float), hipMemcpyHostToDevice,
+                                                  ds->copy));
+                o += lens[i];
+            }
+            SDSP_HIP_CHECK(hipEventRecord(sl.ready, ds->copy));
+        };
+#ifdef SDSP_TEST_HOOKS
+        cd.analyze = [ds, &cb, lens, sample_rate, cfg, outs, fail_chunk](int s, size_t c) {
+            if ((long)c == fail_chunk) throw HipError("injected chunk failure (test hook)");
+#else
+        cd.analyze = [ds, &cb, lens, sample_rate, cfg, outs](int s, size_t c) {  // (no failure injection)
+#endif
+            const uint64_t a = cb[c], b = cb[c + 1];
+            std::vector<uint64_t> off(b - a), ln(b - a);
+            uint64_t tot = 0;
+            for (uint64_t i = a; i < b; i++) {
+                off[i - a] = tot;
+                ln[i - a] = lens[i];
+                tot += lens[i];
+            }
+            run_device(ds->dev, ds->slot[s].d, off.data(), ln.data(), b - a, sample_rate, cfg, nullptr, outs + a,
+                       SDSP_STAGES_FULL, ds->slot[s].ready);
+        };
+        cd.drain = [ds]() {  // after a failed chunk: nothing may still read the slot it reuses
+            // the engine's own streams and this stage's copy stream, never the caller's streams
+            SDSP_HIP_CHECK(hipSetDevice(ds->dev));
+            DeviceCtx& c = device_ctx(ds->dev);
+            {
+                std::lock_guard<std::mutex> lk(c.mu);
+                for (hipStream_t s : c.own) SDSP_HIP_CHECK(hipStreamSynchronize(s));
+            }
+            if (ds->copy) SDSP_HIP_CHECK(hipStreamSynchronize(ds->copy));
+        };
+        cds.push_back(cd);
+    }
+    const size_t failed = run_chunked(n_chunks, cds, [&](size_t c, const std::string& what) {
+        std::fprintf(stderr, "sdsp_analyze_batch: %s\n", what.c_str());
+        mark_failed(c, what);
+    });
+    for (DeviceStage* ds : stg) stage_release(ds);
+    return failed ? SDSP_ERR_PROCESSING : SDSP_OK;
+}
+
+int32_t sdsp_analyze_audio(const float* samples, uint64_t n_samples, uint32_t sample_rate, const sdsp_config* cfg,
+                           sdsp_result* out, char* err, uint64_t errlen) {
+    std::memset(out, 0, sizeof(*out));
+    if (n_samples == 0 || sample_rate == 0) {
+        const char* m = n_samples == 0 ? "Invalid input: Empty audio samples" : "Invalid input: Invalid sample rate";
+        if (err && errlen) std::snprintf(err, (size_t)errlen, "%s", m);
+        out->status = SDSP_ERR_INVALID_INPUT;
+        return SDSP_ERR_INVALID_INPUT;
+    }
+    // one track: staged into a context buffer on the engine's stream under the context lock (no
+    // copy stream, copier thread or staging allocation per call); device 0, as the batch's
+    // default mask
+    int32_t rc = SDSP_OK;
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
+        out->status = SDSP_ERR_PROCESSING;
+        std::snprintf(out->error_message, sizeof out->error_message, "Processing error: no HIP device");
+    } else {
+        try {
+            DeviceCtx& d = device_ctx(0);
+            std::lock_guard<std::mutex> lk(d.mu);
+            SDSP_HIP_CHECK(hipSetDevice(0));
+            DevBuf& in = d.buf("api.track");
+            in.ensure(n_samples * sizeof(float));
+            SDSP_HIP_CHECK(hipMemcpyAsync(in.p, samples, n_samples * sizeof(float), hipMemcpyHostToDevice, d.stream));
+            const uint64_t off = 0;
+            rc = run_locked(d, in.as<float>(), &off, &n_samples, 1, sample_rate, cfg, nullptr, out, SDSP_STAGES_FULL,
+                            nullptr);
+        } catch (const std::exception& e) {
+            std::memset(out, 0, sizeof(*out));
+            out->status = SDSP_ERR_PROCESSING;
+            std::snprintf(out->error_message, sizeof out->error_message, "Processing error: %s", e.what());
+        }
+    }
+    if (rc != SDSP_OK && out->status == SDSP_OK) out->status = rc;
+    if (out->status != SDSP_OK) {
+        if (err && errlen) std::snprintf(err, (size_t)errlen, "%s", out->error_message);
+        const int32_t s = out->status;
+        sdsp_result_free(out);
+        std::memset(out, 0, sizeof(*out));
+        out->status = s;
+        return s;
+    }
+    return SDSP_OK;
+}
+
+int32_t sdsp_generate_synthetic(float* d_out, uint64_t n_tracks, uint64_t len, uint32_t sample_rate, uint64_t seed0,
+                                int32_t bpm_mode, int32_t device, void* stream, float* bpm_out, int32_t* key_out) {
+    try {
+        DeviceCtx& d = device_ctx(device);
+        std::lock_guard<std::mutex> lk(d.mu);
+        SDSP_HIP_CHECK(hipSetDevice(device));
+        std::vector<float> bpm((size_t)n_tracks);
+        std::vector<int> key((size_t)n_tracks);
+        for (uint64_t i = 0; i < n_tracks; i++) {
+            uint64_t x = 0x5EED0000ull + seed0 + i;
+            auto next = [&]() {  // splitmix64
+                x += 0x9E3779B97F4A7C15ull;
+                uint64_t z = x;
+                z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+                z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+                return z ^ (z >> 31);
+            };
+            float b;
+            if (bpm_mode == 1) {  // config 5: thirds in [55,80], [170,200], [80,170]
+                const int third = (int)(i % 3);
+                const uint64_t r = next();
+                if (third == 0)
+                    b = 55.0f + 0.5f * (float)(r % 51);
+                else if (third == 1)
+                    b = 170.0f + 0.5f * (float)(r % 61);
+                else
+                    b = 80.0f + 0.5f * (float)(r % 181);
+            } else {
+                b = 70.0f + 0.5f * (float)(next() % 221);
+            }
+            bpm[(size_t)i] = b;
+            key[(size_t)i] = (int)(next() % 24);
+        }
+        if (bpm_out) std::memcpy(bpm_out, bpm.data(), bpm.size() * sizeof(float));
+        if (key_out) std::memcpy(key_out, key.data(), key.size() * sizeof(int));
+        hipStream_t st = stream ? (hipStream_t)stream : d.stream;
+        DevBuf& db = d.buf("synth.bpm");
+        db.ensure(bpm.size() * 4 + 16);
+        DevBuf& dk = d.buf("synth.key");
+        dk.ensure(key.size() * 4 + 16);
+        DevBuf& dp = d.buf("synth.peak");
+        dp.ensure(key.size() * 4 + 16);
+        SDSP_HIP_CHECK(hipMemcpyAsync(db.p, bpm.data(), bpm.size() * 4, hipMemcpyHostToDevice, st));
+        SDSP_HIP_CHECK(hipMemcpyAsync(dk.p, key.data(), key.size() * 4, hipMemcpyHostToDevice, st));
+        launch_synth(d_out, n_tracks, len, sample_rate, db.as<float>(), dk.as<int>(), seed0, st);
+        launch_synth_normalize(d_out, n_tracks, len, dp.as<unsigned int>(), st);
+        SDSP_HIP_CHECK(hipGetLastError());
+        SDSP_HIP_CHECK(hipStreamSynchronize(st));
+        return SDSP_OK;
+    } catch (const std::exception& e) {
+        std::fprintf(stderr, "sdsp_generate_synthetic: %s\n", e.what());
+        return SDSP_ERR_PROCESSING;
+    }
+}
+
+}  // extern "C"

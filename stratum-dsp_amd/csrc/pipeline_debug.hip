@@ -1,0 +1,369 @@
+// pipeline_debug.hip — the debug_track_id dumps (src/lib.rs:461-487, 547-573, 1471-1538;
+// multi_resolution.rs:304-403, 707-745, 845-857): the reference's eprintln! diagnostics, printed
+// per analysed track in batch order from what the kernels computed (candidate lists, estimates,
+// MrDbg / KeyDbg records), and the stage probes of include/stratum_hip_debug.h.
+#include "pipeline.hpp"
+
+namespace sdsp {
+namespace detail {
+const char* tf_str(bool b) { return b ? "true" : "false"; }
+// cand_support (src/lib.rs:420-431) and lookup_nearest (multi_resolution.rs:281-292)
+float cand_support(const std::vector<Cand4>& c, float bpm, float tol) {
+    float b = 0.0f;
+    for (const Cand4& x : c)
+        if (sd_absf(x.bpm - bpm) <= tol) b = sd_maxf(b, x.score);
+    return b;
+}
+float lookup_nearest_h(const std::vector<Cand4>& c, float bpm, float tol) {
+    float bd = SD_INF_F, bs = 0.0f;
+    for (const Cand4& x : c) {
+        const float d = sd_absf(x.bpm - bpm);
+        if (d <= tol && d < bd) {
+            bd = d;
+            bs = x.score;
+        }
+    }
+    return bs;
+}
+std::string key_str(int key) {  // Key::name
+    char b[8];
+    sdsp_key_name(key < 12 ? 0 : 1, (uint32_t)(key % 12), b, sizeof b);
+    return b;
+}
+void print_debug(const sdsp_config& c, const TrackDbg& d) {
+    const unsigned id = c.debug_track_id;
+    auto gt = [&]() {
+        if (c.has_debug_gt_bpm) std::fprintf(stderr, "GT bpm: %.3f\n", (double)c.debug_gt_bpm);
+    };
+    const float tol = sd_maxf(2.0f, c.bpm_resolution);
+    if (d.base) {
+        const TempoEst& b = d.est;
+        const float s_base = cand_support(d.base_c, b.bpm, tol), s_2x = cand_support(d.base_c, b.bpm * 2.0f, tol),
+                    s_half = cand_support(d.base_c, b.bpm * 0.5f, tol);
+        const bool fam = (s_2x > 0.0f && s_2x >= s_base * 0.90f) || (s_half > 0.0f && s_half >= s_base * 0.90f);
+        const bool fold = b.bpm * 2.0f >= 170.0f && b.bpm * 2.0f <= 200.0f;
+        const bool weak = b.agree == 0 || b.conf < 0.06f;
+        std::fprintf(stderr, "\n=== DEBUG base tempogram (track_id=%u) ===\n", id);
+        gt();
+        std::fprintf(stderr, "base_est: bpm=%.2f conf=%.4f agree=%d (trap_low=%s trap_high=%s ambiguous=%s)\n",
+                     (double)b.bpm, (double)b.conf, b.agree, tf_str(b.trap_low), tf_str(b.trap_high), tf_str(b.ambiguous));
+        std::fprintf(stderr,
+                     "ambiguity signals: family_competes=%s (s_base=%.4f s_2x=%.4f s_half=%.4f) weak_base=%s "
+                     "fold_into_trap=%s\n",
+                     tf_str(fam), (double)s_base, (double)s_2x, (double)s_half, tf_str(weak), tf_str(fold));
+        if (!b.ambiguous) std::fprintf(stderr, "NOTE: multi-res not run (outside trap zones).\n");
+    }
+    if (d.mr) {
+        const size_t top_n = std::max<uint64_t>(c.debug_top_n, 1);
+        std::fprintf(stderr, "\n=== DEBUG multi-res (track_id=%u) ===\n", id);
+        gt();
+        auto top = [&](const char* label, const std::vector<Cand4>& v) {
+            std::fprintf(stderr, "%s top-%zu:\n", label, top_n);
+            for (size_t k = 0; k < v.size() && k < top_n; k++)
+                std::fprintf(stderr, "  bpm=%7.2f score=%.4f\n", (double)v[k].bpm, (double)v[k].score);
+        };
+        top("hop=256", d.c256);
+        top("hop=512", d.c512);
+        top("hop=1024", d.c1024);
+        if (c.has_debug_gt_bpm) {
+            const float g = c.debug_gt_bpm;
+            const float t512 = lookup_nearest_h(d.c512, g, tol), t256 = lookup_nearest_h(d.c256, g, tol),
+                        t1024 = lookup_nearest_h(d.c1024, g, tol);
+            const float d512 = lookup_nearest_h(d.c512, g * 2.0f, tol), d256 = lookup_nearest_h(d.c256, g * 2.0f, tol),
+                        d1024 = lookup_nearest_h(d.c1024, g * 2.0f, tol);
+            const float h512 = lookup_nearest_h(d.c512, g * 0.5f, tol), h256 = lookup_nearest_h(d.c256, g * 0.5f, tol),
+                        h1024 = lookup_nearest_h(d.c1024, g * 0.5f, tol);
+            std::fprintf(stderr, "Support near GT / family (lookup tol=%.2f):\n", (double)tol);
+            std::fprintf(stderr, "  T     @512=%.4f @256=%.4f @1024=%.4f\n", (double)t512, (double)t256, (double)t1024);
+            std::fprintf(stderr, "  2T    @512=%.4f @256=%.4f @1024=%.4f\n", (double)d512, (double)d256, (double)d1024);
+            std::fprintf(stderr, "  T/2   @512=%.4f @256=%.4f @1024=%.4f\n", (double)h512, (double)h256, (double)h1024);
+            const float w512 = c.tempogram_multi_res_w512, w256 = c.tempogram_multi_res_w256,
+                        w1024 = c.tempogram_multi_res_w1024, dt = c.tempogram_multi_res_double_time_512_factor;
+            const float h_t = w512 * t512 + w256 * t256 + w1024 * (t1024 + c.tempogram_multi_res_structural_discount * d1024);
+            float h_2t = w512 * (dt * t512 + (1.0f - dt) * d512) + w256 * d256 + w1024 * d1024;
+            float h_h = w512 * (dt * t512 + (1.0f - dt) * h512) + w256 * h256 + w1024 * h1024;
+            const float eps = 1e-6f;
+            const float r2 = (d256 + eps) / (t256 + eps), rh = (h1024 + eps) / (t1024 + eps);
+            if (r2 < 1.10f) h_2t *= 0.75f;
+            if (r2 < 1.00f) h_2t *= 0.75f;
+            if (rh < 1.10f) h_h *= 0.75f;
+            if (rh < 1.00f) h_h *= 0.75f;
+            struct L {
+                float bpm, s;
+                const char* tag;
+            };
+            std::vector<L> loc = {{g, h_t, "T"}, {g * 2.0f, h_2t, "2T"}, {g * 0.5f, h_h, "T/2"}};
+            std::vector<L> keep;
+            for (const L& l : loc)
+                if (l.bpm >= c.min_bpm && l.bpm <= c.max_bpm) keep.push_back(l);
+            for (L& l : keep) {
+                if (l.bpm > 210.0f) l.s *= 0.80f;
+                else if (l.bpm > 180.0f) l.s *= 0.90f;
+                else if (l.bpm < 60.0f) l.s *= 0.92f;
+            }
+            std::stable_sort(keep.begin(), keep.end(), [](const L& a, const L& b) { return a.s > b.s; });
+            std::fprintf(stderr, "Fusion scores (T anchored at GT, after guardrails+prior):\n");
+            for (const L& l : keep) std::fprintf(stderr, "  %3s bpm=%7.2f score=%.4f\n", l.tag, (double)l.bpm, (double)l.s);
+            if (keep.size() >= 2)
+                std::fprintf(stderr, "  margin(best-second)=%.4f (threshold=%.4f)\n", (double)(keep[0].s - keep[1].s),
+                             (double)c.tempogram_multi_res_margin_threshold);
+            std::fprintf(stderr, "  ratio_2T_256=%.3f ratio_half_1024=%.3f (guardrails)\n", (double)r2, (double)rh);
+        }
+        const MrDbg& m = d.md;
+        if (m.fd)
+            std::fprintf(stderr, "DEBUG fold-down (track_id=%u): %.2f -> %.2f (support ratio %.3f, agree %d->%d).\n", id,
+                         (double)m.fd_from, (double)m.fd_to, (double)m.fd_ratio, m.fd_a0, m.fd_a1);
+        if (m.fu)
+            std::fprintf(stderr, "DEBUG fold-up (track_id=%u): %.2f -> %.2f (support ratio %.3f, agree %d->%d).\n", id,
+                         (double)m.fu_from, (double)m.fu_to, (double)m.fu_ratio, m.fu_a0, m.fu_a1);
+        if (m.tf) {
+            static const char* lab[5] = {"T", "3/2", "2/3", "4/3", "3/4"};
+            std::fprintf(stderr,
+                         "DEBUG triplet-family (track_id=%u): %.2f -> %.2f (%s, support %.3f->%.3f, align %.3f->%.3f)\n",
+                         id, (double)m.tf_from, (double)m.tf_to, lab[m.tf_label < 0 || m.tf_label > 4 ? 0 : m.tf_label],
+                         (double)m.tf_sup0, (double)m.tf_sup1, (double)m.tf_al0, (double)m.tf_al1);
+        }
+        std::fprintf(stderr, "\n=== DEBUG multi-res decision (track_id=%u) ===\n", id);
+        gt();
+        std::fprintf(stderr, "base_est: bpm=%.2f conf=%.4f agree=%d\n", (double)d.est.bpm, (double)d.est.conf, d.est.agree);
+        std::fprintf(stderr, "mr_est:   bpm=%.2f conf=%.4f agree=%d\n", (double)d.mr_est.bpm, (double)d.mr_est.conf,
+                     d.mr_est.agree);
+        std::fprintf(stderr, "ambiguous(trap_low||trap_high)=%s\n", tf_str(d.est.ambiguous));
+        std::fprintf(stderr, "rel=%.3f family_related=%s forbid_promote_high=%s\n", (double)m.rel, tf_str(m.fam),
+                     tf_str(m.forbid));
+        std::fprintf(stderr, "mr_better=%s used_mr=%s\n", tf_str(m.better), tf_str(m.better));
+    }
+    if (d.key) {
+        const KeyDbg& k = d.kd;
+        std::fprintf(stderr, "\n=== DEBUG key (track_id=%u) ===\n", id);
+        std::fprintf(stderr,
+                     "key=%s conf=%.4f clarity=%.4f frames=%d used_frames=%d soft_mapping=%s sigma=%.3f harmonic_mask=%s "
+                     "mask_p=%.2f tuning=%.4f time_smooth=%s margin=%llu edge_trim=%s trim_frac=%.2f\n",
+                     key_str(d.ko.mode * 12 + d.ko.tonic).c_str(), (double)d.ko.conf, (double)d.ko.clarity, k.frames, k.used,
+                     tf_str(c.soft_chroma_mapping), (double)c.soft_mapping_sigma, tf_str(c.enable_key_harmonic_mask),
+                     (double)c.key_harmonic_mask_power, (double)d.tuning, tf_str(c.enable_key_spectrogram_time_smoothing),
+                     (unsigned long long)c.key_spectrogram_smooth_margin, tf_str(c.enable_key_edge_trim),
+                     (double)c.key_edge_trim_fraction);
+        // top_keys: the first three of the final table; the chosen key replaces the third when it is
+        // not among them (detector.rs:506-510)
+        std::vector<std::pair<int, float>> tk;
+        for (int q = 0; q < 3; q++) tk.push_back({k.order[q], k.tab[q]});
+        bool in = false;
+        for (const auto& e : tk) in |= e.first == k.key;
+        if (!in)
+            for (int q = 3; q < 24; q++)
+                if (k.order[q] == k.key) tk.back() = {k.key, k.tab[q]};
+        std::string line;
+        for (size_t q = 0; q < tk.size(); q++) {
+            char b[64];
+            std::snprintf(b, sizeof b, "%s%s:%.4f", q ? ", " : "", key_str(tk[q].first).c_str(), (double)tk[q].second);
+            line += b;
+        }
+        std::fprintf(stderr, "top_keys: %s\n", line.c_str());
+        static const char* notes[12] = {"C", "C#", "D", "D#", "E", "F", "F#", "G", "G#", "A", "A#", "B"};
+        std::vector<int> pcs(12);
+        for (int q = 0; q < 12; q++) pcs[q] = q;
+        std::stable_sort(pcs.begin(), pcs.end(), [&](int a, int b) { return k.agg[a] > k.agg[b]; });
+        line.clear();
+        for (int q = 0; q < 6; q++) {
+            char b[64];
+            std::snprintf(b, sizeof b, "%s%s:%.3f", q ? ", " : "", notes[pcs[q]], (double)k.agg[pcs[q]]);
+            line += b;
+        }
+        std::fprintf(stderr, "top_pitch_classes(weighted): %s\n", line.c_str());
+    }
+}
+}  // namespace detail
+
+static std::vector<Cand4> cand_list(const std::vector<float>& h, size_t row, int cap, int n) {
+    std::vector<Cand4> v;
+    for (int c = 0; c < n; c++) {
+        const float* q = h.data() + (row * (size_t)cap + (size_t)c) * 4;
+        v.push_back({q[0], q[1], q[2], q[3]});
+    }
+    return v;
+}
+
+// src/lib.rs:461-487: the base estimate and its candidate list
+void Pipeline::debug_base(const TempoPassIn& bin, const TempoPassOut& bo, const std::vector<TempoEst>& best,
+                          std::vector<TrackDbg>& tdbg) {
+    const std::vector<float> bc = c_.down(bo.cand, best.size() * (size_t)bin.cand_cap * 4);
+    for (size_t i = 0; i < best.size(); i++) {
+        if (!best[i].ok) continue;
+        TrackDbg& t = tdbg[i];
+        t.base = true;
+        t.est = best[i];
+        t.base_c = cand_list(bc, i, bin.cand_cap, std::min(best[i].n_cands, bin.cand_cap));
+    }
+}
+
+// multi_resolution.rs:304-403, 707-860 and src/lib.rs:547-573: the three hops' candidate lists (the
+// hop-512 one has rows512 rows of cap512, in E order when it is the escalation's own), the
+// multi-resolution estimates and k_multires' decision records
+void Pipeline::debug_multires(const std::vector<int>& E, bool own512, int cap512, int cap_aux, size_t rows512,
+                              const TempoPassOut& o256, const TempoPassOut& b512, const TempoPassOut& o1024,
+                              const std::vector<int>& n256, const std::vector<int>& n512, const std::vector<int>& n1024,
+                              const TempoEst* d_mr, const MrDbg* d_mdbg, std::vector<TrackDbg>& tdbg) {
+    const size_t NE = E.size();
+    const std::vector<float> h256 = c_.down(o256.cand, NE * (size_t)cap_aux * 4);
+    const std::vector<float> h1024 = c_.down(o1024.cand, NE * (size_t)cap_aux * 4);
+    const std::vector<float> h512 = c_.down(b512.cand, rows512 * (size_t)cap512 * 4);
+    const std::vector<TempoEst> hmr = c_.down(d_mr, NE);
+    const std::vector<MrDbg> hmd = c_.down(d_mdbg, NE);
+    for (size_t k = 0; k < NE; k++) {
+        const size_t i = (size_t)E[k];
+        TrackDbg& t = tdbg[i];
+        const size_t j512 = own512 ? k : i;
+        if (!hmr[k].ok || n256[k] < 0 || n1024[k] < 0 || n512[j512] < 0) continue;
+        t.mr = true;
+        t.c256 = cand_list(h256, k, cap_aux, n256[k]);
+        t.c512 = cand_list(h512, j512, cap512, n512[j512]);
+        t.c1024 = cand_list(h1024, k, cap_aux, n1024[k]);
+        t.mr_est = hmr[k];
+        t.md = hmd[k];
+    }
+}
+
+// src/lib.rs:1471-1538 (the beat-synchronous re-vote keeps the frame-level record)
+void Pipeline::debug_key(const KeyLaunch& kl, const std::vector<KeyOut>& kout, std::vector<TrackDbg>& tdbg) {
+    const size_t NK = kl.K.size();
+    if (NK == 0) return;
+    const std::vector<KeyDbg> kd = c_.down(kl.d_kdbg, NK);
+    const std::vector<float> tu = kl.d_tune ? c_.down(kl.d_tune, NK) : std::vector<float>(NK, 0.0f);
+    for (size_t k = 0; k < NK; k++) {
+        if (!kout[k].ok) continue;
+        TrackDbg& t = tdbg[(size_t)kl.K[k]];
+        t.key = true;
+        t.ko = kout[k];
+        t.kd = kd[k];
+        t.tuning = tu[k];
+    }
+}
+
+// sdsp_debug_tempo_stages: tempo_pass through its mags_in / fmax_in path (the percussive
+// fallback's), then the stage buffers and the tempogram lists back to the host.
+void Pipeline::debug_tempo_stages(const float* host_mags, const uint64_t* frames, uint64_t n_tracks, int hop,
+                                  sdsp_debug_tempo_out* out) {
+    if (const std::string why = check_supported(cfg_, sr_); !why.empty()) throw HipError(why);
+    TempoPassIn in;
+    in.hop = hop;
+    in.samples = nullptr;
+    uint64_t total = 0;
+    for (uint64_t t = 0; t < n_tracks; t++) {
+        in.src_off.push_back(0);
+        in.gain_h.push_back(1.0f);
+        in.n_trim.push_back((uint64_t)fs_ + (frames[t] - 1) * (uint64_t)hop);  // frames[t] frames exactly
+        total += frames[t];
+    }
+    in.top_n = 10;
+    in.cand_cap = 10;
+    in.gate = 0;
+    std::vector<float> fmax((size_t)total);
+    for (uint64_t r = 0; r < total; r++) {  // the exact row maximum
+        float m = 0.0f;
+        for (int b = 0; b < nb_; b++) m = std::max(m, host_mags[r * (uint64_t)nb_ + (uint64_t)b]);
+        fmax[(size_t)r] = m;
+    }
+    float* d_mags = c_.dev<float>("P.in", total * (uint64_t)s2_);
+    SDSP_HIP_CHECK(hipMemsetAsync(d_mags, 0, total * (uint64_t)s2_ * sizeof(float), d_.stream));
+    SDSP_HIP_CHECK(hipMemcpy2DAsync(d_mags, (size_t)s2_ * sizeof(float), host_mags, (size_t)nb_ * sizeof(float),
+                                    (size_t)nb_ * sizeof(float), total, hipMemcpyHostToDevice, d_.stream));
+    in.mags_in = d_mags;
+    in.fmax_in = c_.up("P.inmax", fmax);
+    TempoStageDbg g;
+    in.dbg = &g;
+    TempoPassOut po;
+    tempo_pass("B.", in, po);
+    const PassTg& tg = g.tg;
+    out->n_mels = g.fp.n_mels;
+    out->NB = tg.NB;
+    for (int v = 0; v < 4; v++) {
+        out->bs[v] = g.fp.bs[v];
+        out->be[v] = g.fp.be[v];
+        out->band_on[v] = g.fp.band_on[v];
+    }
+    for (int v = 0; v < NVAR; v++) out->present[v] = tg.present[v];
+    if ((uint32_t)g.fp.n_mels > out->mel_cap || (uint32_t)tg.NB > out->acf_cap) throw std::invalid_argument("capacity");
+    for (int k : tg.fft_k)
+        if ((uint32_t)k > out->fft_cap) throw std::invalid_argument("capacity");
+    auto get = [&](const float* d, float* h, size_t n) {
+        if (n) SDSP_HIP_CHECK(hipMemcpyAsync(h, d, n * sizeof(float), hipMemcpyDeviceToHost, d_.stream));
+    };
+    get(po.E, out->E, 4 * (size_t)total);
+    get(po.H, out->H, 4 * (size_t)total);
+    get(po.SFX, out->SFX, 4 * (size_t)total);
+    get(po.SFO, out->SFO, (size_t)total);
+    get(po.MEL, out->MEL, (size_t)g.fp.n_mels * (size_t)total);
+    get(po.nov, out->nov, NVAR * (size_t)total);
+    get(po.nov_sum, out->nov_sum, NVAR * (size_t)n_tracks);
+    const size_t n_it = tg.items.size();
+    uint64_t n_fft = 0;
+    for (size_t i = 0; i < n_it; i++) n_fft = std::max(n_fft, tg.fft_off[i] + (uint64_t)tg.fft_k[i]);
+    const std::vector<float> ab = c_.down(tg.acf_bpm, n_it * (size_t)tg.NB), as = c_.down(tg.acf_str, n_it * (size_t)tg.NB);
+    const std::vector<float> fb = c_.down(tg.fft_bpm, (size_t)n_fft), fw = c_.down(tg.fft_pow, (size_t)n_fft);
+    for (uint64_t k = 0; k < n_tracks * NVAR; k++) out->acf_n[k] = out->fft_n[k] = 0;
+    for (size_t i = 0; i < n_it; i++) {
+        const size_t slot = (size_t)tg.items[i];
+        float* a = out->acf + slot * out->acf_cap * 2;
+        float* f = out->fft + slot * out->fft_cap * 2;
+        for (int j = 0; j < tg.NB; j++) {
+            a[2 * j] = ab[i * (size_t)tg.NB + (size_t)j];
+            a[2 * j + 1] = as[i * (size_t)tg.NB + (size_t)j];
+        }
+        for (int j = 0; j < tg.fft_k[i]; j++) {
+            f[2 * j] = fb[(size_t)tg.fft_off[i] + (size_t)j];
+            f[2 * j + 1] = fw[(size_t)tg.fft_off[i] + (size_t)j];
+        }
+        out->acf_n[slot] = tg.NB;
+        out->fft_n[slot] = tg.fft_k[i];
+    }
+}
+
+// sdsp_debug_key_stages: key_condition (and, for mode 1, tail_exact) over uploaded key spectrograms.
+// exact_energy_ selects mode 2's sequence, as it does for the nested rerun.
+void Pipeline::debug_key_stages(const float* host_mags, const uint64_t* frames, uint64_t n_tracks, int mode,
+                                float* masked, float* chroma, float* energy, float* edel, int32_t info[4]) {
+    if (const std::string why = check_supported(cfg_, sr_); !why.empty()) throw HipError(why);
+    if ((mode == 2) != exact_energy_) throw HipError("debug_key_stages: mode 2 runs on an exact-energy pipeline");
+    if (mode != 0 && !key_energy_blocked(cfg_, sr_)) throw std::invalid_argument("modes 1 and 2 need the band path");
+    const int NK = (int)n_tracks, B8 = kfs_ / 2 + 1;
+    std::vector<uint64_t> kpfx(1, 0), ktile(1, 0);
+    std::vector<int> kid((size_t)NK);
+    for (int k = 0; k < NK; k++) {
+        kpfx.push_back(kpfx.back() + frames[k]);
+        ktile.push_back(ktile.back() + (frames[k] + HP_FRAMES - 1) / HP_FRAMES);
+        kid[(size_t)k] = k;
+    }
+    const uint64_t total8 = kpfx.back();
+    const std::string EP = "E0.";
+    hipStream_t st = d_.stream;
+    uint64_t* d_kpfx = c_.up(EP + "kpfx", kpfx);
+    uint64_t* d_ktile = c_.up(EP + "ktile", ktile);
+    int* d_kid = c_.up(EP + "kid", kid);
+    float* mags8 = c_.dev<float>("E.mags8", total8 * (uint64_t)ks_);
+    SDSP_HIP_CHECK(hipMemsetAsync(mags8, 0, total8 * (uint64_t)ks_ * sizeof(float), st));
+    SDSP_HIP_CHECK(hipMemcpy2DAsync(mags8, (size_t)ks_ * sizeof(float), host_mags, (size_t)B8 * sizeof(float),
+                                    (size_t)B8 * sizeof(float), total8, hipMemcpyHostToDevice, st));
+    Timers kt;
+    kt.init(d_);
+    const KeyCond kc = key_condition(EP, mags8, kpfx, ktile, d_kpfx, d_ktile, d_kid, st, kt);
+    if (mode == 1) {
+        if (!kc.band || !kc.d_ht) throw HipError("debug_key_stages: mode 1 without the band path");
+        KeyTail t;
+        tail_buffers(t, kc, mags8, d_kpfx, total8);
+        tail_exact(t, d_kid, NK, d_ktile, ktile.back(), st);
+    }
+    info[0] = kc.st_lo;
+    info[1] = kc.st_hi;
+    info[2] = kc.band ? 1 : 0;
+    info[3] = B8;
+    SDSP_HIP_CHECK(hipMemcpy2DAsync(masked, (size_t)B8 * sizeof(float), mags8, (size_t)ks_ * sizeof(float),
+                                    (size_t)B8 * sizeof(float), total8, hipMemcpyDeviceToHost, st));
+    SDSP_HIP_CHECK(hipMemcpyAsync(chroma, kc.d_chroma, total8 * 12 * sizeof(float), hipMemcpyDeviceToHost, st));
+    SDSP_HIP_CHECK(hipMemcpyAsync(energy, kc.d_energy, total8 * sizeof(float), hipMemcpyDeviceToHost, st));
+    if (edel && kc.d_edel && mode == 0)
+        SDSP_HIP_CHECK(hipMemcpyAsync(edel, kc.d_edel, total8 * sizeof(float), hipMemcpyDeviceToHost, st));
+    c_.sync();
+}
+
+}  // namespace sdsp

@@ -1,5 +1,6 @@
 // runtime.hip — device contexts, FFT tables, C ABI housekeeping (config defaults, result
-// ownership, version) and stage probes.  The analyze pipeline itself is in pipeline.hip.
+// ownership, version) and stage probes.  The analyze pipeline itself is in pipeline.hip (overview
+// and sub-batch orchestrator) and pipeline_*.hip; its C ABI entry points are in pipeline_abi.hip.
 #include <algorithm>
 #include <atomic>
 #include <cstdio>
