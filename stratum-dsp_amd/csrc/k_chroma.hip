@@ -304,7 +304,7 @@ __device__ inline void hpcp_accumulate(float (*pc)[HP_FRAMES], int i, int bin, f
 template <int KCAP, int KB>
 __device__ __forceinline__ void topk_insert(float (&pm)[KCAP], int (&pb)[KCAP], float& thr, float v, int vb) {
     if (!(v > thr)) return;
-    // the descending list's insertion as in HpcpFrame::walk (k_key.hip): gt[q] = v > pm[q] turns
+    // the descending list's insertion as in HpcpFrame::walk (k_hpcp.hip): gt[q] = v > pm[q] turns
     // true once; slots are updated from the tail in place
     bool gt[KCAP];
 #pragma unroll

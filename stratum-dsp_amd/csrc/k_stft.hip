@@ -534,16 +534,18 @@ __global__ __launch_bounds__(256) void k_stft_gen(int N, const float* __restrict
 // the 16x-overlapped samples 32 KB per 8192-point frame, all from L2):
 //  * a strip = up to STRIP_T consecutive frames of one track, processed in order by one
 //    frame-group (8192: the 256-thread workgroup; 2048: one wave);
-//  * window, pass-1 and pass-2 twiddles and post twiddles are loaded into registers once per strip;
+//  * the tables are loaded once per strip: window and pass-1 twiddles into registers, pass-2 and
+//    post twiddles into LDS (in registers they would cost the third wave per SIMD);
 //  * thread lt holds z[lt + TPF k], k = 0..15, of the current frame in a register ring.  The
 //    next frame starts hop/2 = S*TPF complex values later, so its element k is the current
 //    element k + S: the ring shifts by S and only S new values per thread are loaded (prefetched
 //    one frame ahead);
-//  * two LDS buffers: pass 1 writes A, pass 2 reads A and writes B, the last pass reads B into
-//    registers.  Its columns are assigned so that each real-FFT pair (k, M-k) meets in one thread
+//  * one LDS frame buffer: pass 1 writes it, pass 2 runs in place (each thread writes its 16
+//    results back into the 16 slots it read), the last pass reads it into registers.  The last
+//    pass's columns are assigned so that each real-FFT pair (k, M-k) meets in one thread
 //    (N = 2048) or in lanes l and l^32 of one wave, exchanged by ds_bpermute (N = 8192), so the
-//    post-processing runs from registers: two barriers per frame, no barrier between a pass's
-//    reads and its writes, and two LDS round trips instead of three;
+//    post-processing runs from registers: no barrier between a pass's reads and its writes, and
+//    two LDS round trips instead of three;
 //  * the STFT post twiddles are the spec's symmetric ones, rt[M-k] = (-rt[k].re, rt[k].im), so
 //    bin M-k needs no table entry of its own;
 //  * the correctly rounded sqrt is sqrt_fast; a frame where it met an input outside its exact
@@ -587,232 +589,15 @@ constexpr int slide_rt_base() {
     return StftShape<M>::RT_SPECIAL + 4;
 }
 
-template <int NFFT, int S, bool FRAME_MAX>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) void k_stft_slide(
-    const float* __restrict__ samples, const uint64_t* __restrict__ frame_pfx, const uint64_t* __restrict__ strip_pfx,
-    int n_tracks, uint64_t n_strips, const uint64_t* __restrict__ src_off, const float* __restrict__ gain, int hop,
-    const float* __restrict__ window, const cx* __restrict__ twp, const cx* __restrict__ rtp, float* __restrict__ mags,
-    const uint64_t* __restrict__ mag_row0, int stride, float* __restrict__ frame_max, uint32_t* __restrict__ redo) {
-    constexpr int M = NFFT / 2;
-    using SH = StftShape<M>;
-    constexpr int TPF = SH::TPF;
-    constexpr int FPB = 256 / TPF;               // frame groups (strips) per workgroup
-    constexpr int PADM = M + PADSHIFT * M / 16;  // padded LDS slots per frame buffer
-    static_assert(SH::NPASS > 0 && S >= 1 && S <= 16, "supported: N = 2048, 8192; hop = S * 2 * TPF");
-    __shared__ c2 lds[FPB * 2 * PADM];
-    __shared__ uint32_t miss_flag[2];  // N = 8192: frame i's "some wave missed" flag at [i & 1]
-
-    const int lt = threadIdx.x % TPF;
-    const int fl = threadIdx.x / TPF;
-    // wave-uniform by construction (a frame group is whole waves); readfirstlane lets the compiler
-    // keep the strip's scalars and buffer descriptors in SGPRs
-    const uint64_t strip =
-        (uint64_t)__builtin_amdgcn_readfirstlane((int)((uint64_t)xcd_block(blockIdx.x, gridDim.x) * FPB + fl));
-    if (strip >= n_strips) return;  // only whole frame groups: a wave (TPF = 64) or the workgroup (FPB = 1)
-    if (TPF == 256 && threadIdx.x < 2) miss_flag[threadIdx.x] = 0;  // ordered by frame 0's barriers
-    const int trk = find_track(strip_pfx, n_tracks, strip);
-    const uint64_t F = frame_pfx[trk + 1] - frame_pfx[trk];
-    const uint64_t f0 = (strip - strip_pfx[trk]) * (uint64_t)STRIP_T;
-    const int nf = (int)(F - f0 < (uint64_t)STRIP_T ? F - f0 : (uint64_t)STRIP_T);
-    const float gn = gain[trk];
-    c2* bufA = lds + fl * 2 * PADM;
-    c2* bufB = bufA + PADM;
-    const int vo = 8 * lt;
-    // the strip's samples: frame f0 + i starts at complex index (f0 + i) * hop / 2
-    const uint64_t cstart = f0 * (uint64_t)(hop / 2);
-    const uint64_t clen = (uint64_t)(nf - 1) * (uint64_t)(hop / 2) + (uint64_t)M;  // complex values the strip reads
-    const float* sbase = samples + src_off[trk] + 2 * cstart;
-    const __amdgpu_buffer_rsrc_t rx = rsrc_of(sbase, (uint32_t)(8u * clen));
-    const __amdgpu_buffer_rsrc_t rw = rsrc_of(window, 4u * NFFT);
-    const __amdgpu_buffer_rsrc_t rtw = rsrc_of(twp, 8u * 15u * (TPF + TPF / 16 + 1));
-    const __amdgpu_buffer_rsrc_t rrt = rsrc_of(rtp, 8u * (slide_rt_base<M>() + 8 * TPF + 1));
-
-    // per-strip constants
-    c2 win[16], tw1[15], tw2[15], wk[8];
-    c2 ring[16];
-#pragma unroll
-    for (int k = 0; k < 16; k++) {  // the ring holds x * gain (the normalised samples, src/lib.rs:124)
-        const c2 x = ld_c2(rx, vo, 8 * TPF * k);
-        ring[k] = {x.x * gn, x.y * gn};
-    }
-#pragma unroll
-    for (int k = 0; k < 16; k++) win[k] = ld_c2(rw, vo, 8 * TPF * k);
-#pragma unroll
-    for (int j = 0; j < 15; j++) tw1[j] = ld_c2(rtw, vo, 8 * TPF * j);
-    const int pp2 = lt / 16;  // pass 2 (s = 16): p' = lt / 16
-#pragma unroll
-    for (int j = 0; j < 15; j++) tw2[j] = ld_c2(rtw, 8 * pp2, 8 * (15 * TPF + j * (TPF / 16)));
-#pragma unroll
-    for (int j = 0; j < 8; j++) wk[j] = ld_c2(rrt, vo, 8 * (slide_rt_base<M>() + TPF * j));
-    c2 tw3[15];  // pass 3 (M = 4096): p' = 0, wave-uniform
-    if constexpr (M == 4096) {
-#pragma unroll
-        for (int j = 0; j < 15; j++) {
-            const cx t = twp[15 * TPF + 15 * (TPF / 16) + j];
-            tw3[j] = c2{t.re, t.im};
-        }
-    }
-    const c2 rtH = ld_c2(rrt, 0, 8 * (slide_rt_base<M>() + 8 * TPF));  // bin M/2
-    // last-pass columns and the bins of the post slots
-    int colA, colA2, colB, colB2;
-    if constexpr (M == 4096) {
-        colA = slide_col8(lt);
-        colA2 = colB = colB2 = 0;
-    } else {
-        slide_cols2(lt, &colA, &colA2, &colB, &colB2);
-    }
-    const bool self0 = M == 4096 ? (threadIdx.x == 0) : (lt == 0);  // the column-0 thread
-    const bool self128 = M == 4096 && threadIdx.x == 32;             // the column-128 lane (N = 8192)
-    // N = 8192: the partner lane (l ^ 32), or the lane itself for the self-paired columns
-    const int src_lane = (self0 || self128) ? (threadIdx.x & 63) : ((threadIdx.x & 63) ^ 32);
-
-    // every per-strip load has landed before the frame loop: the loop header then carries no
-    // pending load, so the compiler does not wait there for the previous frame's stores
-    __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0)
-    for (int i = 0; i < nf; i++) {
-        const uint64_t f = f0 + (uint64_t)i;
-        // prefetch the next frame's S new ring values: z[(i+1) h + lt + TPF (16 - S + s)].  After
-        // the strip's last frame the offsets are past the descriptor's range, where buffer loads
-        // return 0 without touching memory, so the load needs no branch (a conditional load
-        // makes the compiler wait for it at once).
-        c2 nxt[S];
-#pragma unroll
-        for (int s2 = 0; s2 < S; s2++) nxt[s2] = ld_c2(rx, vo, 8 * ((i + 1) * (hop / 2) + TPF * (16 - S + s2)));
-        c2 v[16];
-#pragma unroll
-        for (int k = 0; k < 16; k++) v[k] = {ring[k].x * win[k].x, ring[k].y * win[k].y};
-        // pass 1 (n = M, s = 1, p' = lt) -> A
-        radix16<false>(v, tw1);
-#pragma unroll
-        for (int k = 0; k < 16; k++) bufA[P17 * lt + k] = v[k];
-        frame_sync<TPF>();
-        if constexpr (TPF == 256) {
-            // frame i - 1's flag is final (its waves set it before this barrier); cleared before
-            // this frame's second barrier, so before frame i + 1 can set it again
-            if (threadIdx.x == 0 && i > 0 && miss_flag[(i - 1) & 1]) {
-                miss_flag[(i - 1) & 1] = 0;
-                redo[1 + atomicAdd(redo, 1u)] = (uint32_t)(frame_pfx[trk] + f - 1);
-            }
-        }
-        // pass 2 (n = M/16, s = 16): A -> B
-        {
-            constexpr int s2 = 16, m1 = (M / 16) / 16;
-            const int q = lt % s2;
-            const int rb = lpad(q + s2 * pp2), rs = s2 * m1 + PADSHIFT * (s2 * m1) / 16;
-#pragma unroll
-            for (int k = 0; k < 16; k++) v[k] = bufA[rb + rs * k];
-            radix16<false>(v, tw2);
-            const int wb = q + P272 * pp2;
-#pragma unroll
-            for (int k = 0; k < 16; k++) bufB[wb + P17 * k] = v[k];
-        }
-        frame_sync<TPF>();
-        // last pass, then the post-processing from registers (sdsp_fft_spec.h STFT section):
-        //   S = Z[k] + conj(Z[M-k]),  D' = (Z[k].im + Z[M-k].im, -(Z[k].re - Z[M-k].re)),
-        //   Y = S + rt[k] D' (FMA form),  |X[k]| = 2^-33 sqrt(fma(Y.re, Y.re, Y.im Y.im)) (the window carries
-        //   2^32, so Y = 2^33 X);  bin M-k from the
-        //   same S, D' conjugated with rt[M-k] = (-rt[k].re, rt[k].im).
-        float* out = mags + (mag_row0[trk] + f) * (uint64_t)stride;
-        float mx = 0.0f;
-        uint32_t lo = 0xFFFFFFFFu, hi = 0u;
-        auto sq = [&](float yx, float yy) { return 0x1p-33f * sqrt_fast(__builtin_fmaf(yx, yx, yy * yy), lo, hi); };
-        // frame maximum: magnitudes are +0 or positive, so v_max_f32 (IEEE maxNum: a NaN operand
-        // yields the other) is sd_maxf here except for the payload of an all-NaN row
-        auto put = [&](int k, float mag) {
-            out[k] = mag;
-            if (FRAME_MAX) mx = __builtin_fmaxf(mx, mag);
-        };
-        // one pair: own bin k from Zk, partner bin M-k from Zr, post twiddle w = rt[k]
-        auto pair = [&](c2 Zk, c2 Zr, c2 w, int k) {
-            const float sx = Zk.x + Zr.x, sy = Zk.y - Zr.y, dx = Zk.y + Zr.y, dy = -(Zk.x - Zr.x);
-            put(k, sq(__builtin_fmaf(w.x, dx, __builtin_fmaf(-w.y, dy, sx)), __builtin_fmaf(w.x, dy, __builtin_fmaf(w.y, dx, sy))));
-            put(M - k, sq(__builtin_fmaf(-w.x, dx, __builtin_fmaf(w.y, dy, sx)), __builtin_fmaf(w.x, dy, __builtin_fmaf(w.y, dx, -sy))));
-        };
-        auto single = [&](c2 Z, c2 w, int k) {  // a self-paired bin (k = M/2)
-            const float sx = Z.x + Z.x, sy = Z.y - Z.y, dx = Z.y + Z.y, dy = -(Z.x - Z.x);
-            put(k, sq(__builtin_fmaf(w.x, dx, __builtin_fmaf(-w.y, dy, sx)), __builtin_fmaf(w.x, dy, __builtin_fmaf(w.y, dx, sy))));
-        };
-        if constexpr (M == 4096) {
-            // pass 3 (n = 16, s = 256, p' = 0) on column colA: v[m] = Z[colA + 256 m]
-            const int rb = lpad(colA);
-#pragma unroll
-            for (int k = 0; k < 16; k++) v[k] = bufB[rb + P272 * k];
-            radix16<true>(v, tw3);
-            // exchange: every lane sends its elements 8..15 to the partner lane (ds_bpermute);
-            // the column-0 lane sends itself elements 9..15, 0 (its pairs are (m, 16 - m))
-            c2 rv[8];
-#pragma unroll
-            for (int i = 0; i < 8; i++) {
-                const c2 snd = self0 ? v[(9 + i) & 15] : v[8 + i];
-                rv[i] = {__shfl(snd.x, src_lane, 64), __shfl(snd.y, src_lane, 64)};
-            }
-            // pair j: Z[colA + 256 j] with the partner column's element 15 - j (= rv[7 - j])
-#pragma unroll
-            for (int j = 0; j < 8; j++) pair(v[j], rv[7 - j], wk[j], colA + 256 * j);
-            if (self0) single(v[8], rtH, M / 2);
-        } else {
-            // trailing radix-4 (n = 4, s = M/4, p = 0) on the thread's four columns
-            c2 A[4], A2[4], Bv[4], B2[4];
-            auto col4 = [&](int c, c2 (&z)[4]) {
-                const int b = lpad(c);
-                bfly4<false>(bufB[b], bufB[b + P272], bufB[b + 2 * P272], bufB[b + 3 * P272], c2{}, c2{}, c2{}, z[0],
-                             z[1], z[2], z[3]);
-            };
-            col4(colA, A);
-            col4(colA2, A2);
-            col4(colB, Bv);
-            col4(colB2, B2);
-            // pairs of (colA, colA2): (A[j], A2[3 - j]); thread 0 (columns 0 and 128, each self-paired):
-            // (A0, A0) -> bins 0 / M, (A1, A3) -> 256 / 768, (A2'0, A2'3) -> 128 / 896, (A2'1, A2'2) -> 384 / 640
-            const c2 zk0 = A[0], zr0 = self0 ? A[0] : A2[3];
-            const c2 zk1 = A[1], zr1 = self0 ? A[3] : A2[2];
-            const c2 zk2 = self0 ? A2[0] : A[2], zr2 = self0 ? A2[3] : A2[1];
-            const c2 zk3 = self0 ? A2[1] : A[3], zr3 = self0 ? A2[2] : A2[0];
-            pair(zk0, zr0, wk[0], self0 ? 0 : colA);
-            pair(zk1, zr1, wk[1], self0 ? 256 : colA + 256);
-            pair(zk2, zr2, wk[2], self0 ? 128 : colA + 512);
-            pair(zk3, zr3, wk[3], self0 ? 384 : colA + 768);
-#pragma unroll
-            for (int j = 0; j < 4; j++) pair(Bv[j], B2[3 - j], wk[4 + j], colB + 256 * j);
-            if (self0) single(A[2], rtH, M / 2);
-        }
-        // a magnitude^2 of subnormal scale (or inf / NaN) somewhere in the frame: the frame goes on
-        // the redo list, which k_stft_mag recomputes with the general sqrt right after this kernel
-        // (stream order), overwriting the whole row.  Each frame is listed at most once, so the
-        // list never holds more entries than the launch has frames: one wave per frame (N = 2048)
-        // appends directly; the 4 waves of an 8192-point frame OR a flag in LDS, which thread 0
-        // reads after the next frame's first barrier (or after the strip) and appends.
-        const bool missed = __builtin_amdgcn_ballot_w64(sqrt_fast_missed(lo, hi)) != 0;
-        if constexpr (TPF == 64) {
-            if (__builtin_expect(missed, 0) && lt == 0) redo[1 + atomicAdd(redo, 1u)] = (uint32_t)(frame_pfx[trk] + f);
-        } else {
-            if (__builtin_expect(missed, 0) && (threadIdx.x & 63) == 0) atomicOr(&miss_flag[i & 1], 1u);
-        }
-        if constexpr (FRAME_MAX) {
-            static_assert(!FRAME_MAX || TPF == 64, "frame maxima: one wave per frame");
-            mx = wave_max(mx);
-            if (lt == 0) frame_max[mag_row0[trk] + f] = mx;
-        }
-        // slide the ring
-#pragma unroll
-        for (int k = 0; k < 16 - S; k++) ring[k] = ring[k + S];
-#pragma unroll
-        for (int s2 = 0; s2 < S; s2++) ring[16 - S + s2] = {nxt[s2].x * gn, nxt[s2].y * gn};
-    }
-    if constexpr (TPF == 256) {  // the strip's last frame
-        __syncthreads();
-        if (threadIdx.x == 0 && miss_flag[(nf - 1) & 1]) redo[1 + atomicAdd(redo, 1u)] = (uint32_t)(frame_pfx[trk] + f0 + nf - 1);
-    }
-}
-
 // ---------------------------------------------------------------------------------------------
 // k_stft_slide2s: the sliding strip for N = 2048 (M = 1024, one wave per strip, 4 strips per
-// workgroup) with ONE frame buffer per strip and the pass-2 / post twiddles in LDS, for 3 waves
-// per SIMD (k_stft_slide<2048>: two buffers per strip, 227 VGPRs, 2 waves).  Pass 2 runs in place:
+// workgroup) with ONE frame buffer per strip and the pass-2 / post twiddles in LDS, which fits 3
+// waves per SIMD (<= 168 VGPRs; isolated 0.0255 ms per track, profiles/r04yf_stft_probe.jsonl; HBM
+// bytes 1.031 x the algorithmic ones, profiles/pmc_stft2048.json).  Pass 2 runs in place:
 // a thread reads its 16 slots and writes its 16 results back into them (a wave's LDS operations
 // run in issue order, so no barrier), so z[q + 256 pp + 16 k] lives where x[q + 16 pp + 64 k] was
 // read, and the trailing radix-4 reads column c, Z[c + 256 j], from (c % 16) + 68 (c / 16) + 17 j.
-// Same arithmetic as k_stft_slide (bit-identical magnitudes and frame maxima).
+// Same arithmetic as k_stft_mag (bit-identical magnitudes and frame maxima).
 template <int S, bool FRAME_MAX>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) void k_stft_slide2s(
     const float* __restrict__ samples, const uint64_t* __restrict__ frame_pfx, const uint64_t* __restrict__ strip_pfx,
@@ -858,7 +643,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
 
     c2 win[16], tw1[15], ring[16];
 #pragma unroll
-    for (int k = 0; k < 16; k++) {
+    for (int k = 0; k < 16; k++) {  // the ring holds x * gain (the normalised samples, src/lib.rs:124)
         const c2 x = ld_c2(rx, vo, 8 * TPF * k);
         ring[k] = {x.x * gn, x.y * gn};
     }
@@ -881,16 +666,23 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
     const int vA2 = 4 * (self0 ? 128 : colA + 512), vA2r = 4 * (M - (self0 ? 128 : colA + 512));
     const int vA3 = 4 * (self0 ? 384 : colA + 768), vA3r = 4 * (M - (self0 ? 384 : colA + 768));
     const int vB = 4 * colB, vBr = 4 * (M - colB - 768);
-    __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0): the per-strip loads have landed
+    // every per-strip load has landed before the frame loop: the loop header then carries no
+    // pending load, so the compiler does not wait there for the previous frame's stores
+    __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0)
 
     for (int i = 0; i < nf; i++) {
         const uint64_t f = f0 + (uint64_t)i;
+        // prefetch the next frame's S new ring values: z[(i+1) h + lt + TPF (16 - S + s)].  After
+        // the strip's last frame the offsets are past the descriptor's range, where buffer loads
+        // return 0 without touching memory, so the load needs no branch (a conditional load
+        // makes the compiler wait for it at once).
         c2 nxt[S];
 #pragma unroll
         for (int s2 = 0; s2 < S; s2++) nxt[s2] = ld_c2(rx, vo, 8 * ((i + 1) * (hop / 2) + TPF * (16 - S + s2)));
         c2 v[16];
 #pragma unroll
         for (int k = 0; k < 16; k++) v[k] = {ring[k].x * win[k].x, ring[k].y * win[k].y};
+        // pass 1 (n = M, s = 1, p' = lt)
         radix16<false>(v, tw1);
         frame_sync<TPF>();  // the previous frame's column reads are done (in-order LDS)
 #pragma unroll
@@ -903,12 +695,19 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
 #pragma unroll
         for (int k = 0; k < 16; k++) buf[rb2 + 68 * k] = v[k];
         frame_sync<TPF>();
-        // the frame's row as a buffer resource: per-lane byte offsets fixed for the strip, the
+        // last pass, then the post-processing from registers (sdsp_fft_spec.h STFT section):
+        //   S = Z[k] + conj(Z[M-k]),  D' = (Z[k].im + Z[M-k].im, -(Z[k].re - Z[M-k].re)),
+        //   Y = S + rt[k] D' (FMA form),  |X[k]| = 2^-33 sqrt(fma(Y.re, Y.re, Y.im Y.im)) (the window
+        //   carries 2^32, so Y = 2^33 X);  bin M-k from the same S, D' conjugated with
+        //   rt[M-k] = (-rt[k].re, rt[k].im).
+        // The frame's row is a buffer resource: per-lane byte offsets fixed for the strip, the
         // slot's bin offset a scalar constant (no 64-bit address arithmetic per store)
         const __amdgpu_buffer_rsrc_t ro = rsrc_of(mags + (mag_row0[trk] + f) * (uint64_t)stride, 4u * (M + 1));
         float mx = 0.0f;
         uint32_t lo = 0xFFFFFFFFu, hi = 0u;
         auto sq = [&](float yx, float yy) { return 0x1p-33f * sqrt_fast(__builtin_fmaf(yx, yx, yy * yy), lo, hi); };
+        // frame maximum: magnitudes are +0 or positive, so v_max_f32 (IEEE maxNum: a NaN operand
+        // yields the other) is sd_maxf here except for the payload of an all-NaN row
         auto put = [&](int voff, int soff, float mag) {
             __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(mag), ro, voff, soff, 0);
             if (FRAME_MAX) mx = __builtin_fmaxf(mx, mag);
@@ -933,6 +732,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
         col4(colA2, A2);
         col4(colB, Bv);
         col4(colB2, B2);
+        // pairs of (colA, colA2): (A[j], A2[3 - j]); thread 0 (columns 0 and 128, each self-paired):
+        // (A0, A0) -> bins 0 / M, (A1, A3) -> 256 / 768, (A2'0, A2'3) -> 128 / 896, (A2'1, A2'2) -> 384 / 640
         const c2 zk0 = A[0], zr0 = self0 ? A[0] : A2[3];
         const c2 zk1 = A[1], zr1 = self0 ? A[3] : A2[2];
         const c2 zk2 = self0 ? A2[0] : A[2], zr2 = self0 ? A2[3] : A2[1];
@@ -946,6 +747,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
 #pragma unroll
         for (int j = 0; j < 4; j++) pair(Bv[j], B2[3 - j], wks[(4 + j) * TPF + lt], vB, 1024 * j, vBr, 1024 * (3 - j));
         if (self0) single(A[2], rtH, M / 2);
+        // a magnitude^2 of subnormal scale (or inf / NaN) somewhere in the frame: the frame goes on
+        // the redo list, which k_stft_mag recomputes with the general sqrt right after this kernel
+        // (stream order), overwriting the whole row.  One wave per frame, so each frame is listed
+        // at most once and the list never holds more entries than the launch has frames.
         const bool missed = __builtin_amdgcn_ballot_w64(sqrt_fast_missed(lo, hi)) != 0;
         if (__builtin_expect(missed, 0) && lt == 0) redo[1 + atomicAdd(redo, 1u)] = (uint32_t)(frame_pfx[trk] + f);
         if constexpr (FRAME_MAX) {
@@ -960,202 +765,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
 }
 
 // ---------------------------------------------------------------------------------------------
-// k_stft_slide8: the sliding strip for N = 8192 (M = 4096 = 16^3, one 256-thread workgroup per
-// strip), software-pipelined across frames.  The kernel holds its per-strip constants in ~110
-// VGPRs, so it runs 2 waves per SIMD, and one wave alone issues a VALU instruction at most every
-// 4 cycles (MI355X_MICROARCH.md, issue costs): the SIMD reaches its 2-cycle rate only while both
-// of its waves issue VALU.  Every LDS round trip is therefore given independent VALU work of
-// another frame to cover its latency:
-//   region 1 (after the barrier that publishes frame i's pass-1 output in A):
-//       issue frame i's pass-2 reads from A; post-process frame i-1 (held in registers: S, D',
-//       the FMA form, the exact sqrt, 16 buffer stores); pass 2 of frame i; write B;
-//   barrier;
-//   region 2: issue frame i's pass-3 reads from B; window + pass 1 of frame i+1 from the sample
-//       ring, write A (every pass-2 read of A finished before the barrier); pass 3 of frame i; the
-//       (k, M-k) exchange between lanes l and l^32 (ds_bpermute) into the held registers;
-//   barrier (A complete for frame i+1; every pass-3 read of B done before the next B write).
-// Two barriers per frame, as before, and the same arithmetic (bit-identical magnitudes).  Rows
-// are written by buffer stores whose per-lane offsets are fixed for the strip and whose row is a
-// scalar descriptor (no 64-bit address arithmetic per store); the descriptor of the row "before
-// frame 0" has no records, so its stores are dropped by the hardware without a branch.  Frames
-// whose sqrt met an input outside its exact range are collected in a wave-uniform 64-bit mask and
-// listed once per strip after the loop (no per-frame LDS flag).
-template <int S>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) void k_stft_slide8(
-    const float* __restrict__ samples, const uint64_t* __restrict__ frame_pfx, const uint64_t* __restrict__ strip_pfx,
-    int n_tracks, uint64_t n_strips, const uint64_t* __restrict__ src_off, const float* __restrict__ gain, int hop,
-    const float* __restrict__ window, const cx* __restrict__ twp, const cx* __restrict__ rtp, float* __restrict__ mags,
-    const uint64_t* __restrict__ mag_row0, int stride, uint32_t* __restrict__ redo) {
-    constexpr int M = 4096, TPF = 256;
-    constexpr int PADM = M + PADSHIFT * M / 16;
-    static_assert(S >= 1 && S <= 16 && STRIP_T == 64, "hop = S * 512; the miss mask holds 64 frames");
-    __shared__ c2 lds[2 * PADM];
-    __shared__ uint64_t miss_mask[4];
-
-    const int lt = threadIdx.x;
-    const uint64_t strip = (uint64_t)__builtin_amdgcn_readfirstlane((int)xcd_block(blockIdx.x, gridDim.x));
-    if (strip >= n_strips) return;  // the whole workgroup
-    const int trk = find_track(strip_pfx, n_tracks, strip);
-    const uint64_t F = frame_pfx[trk + 1] - frame_pfx[trk];
-    const uint64_t f0 = (strip - strip_pfx[trk]) * (uint64_t)STRIP_T;
-    const int nf = (int)(F - f0 < (uint64_t)STRIP_T ? F - f0 : (uint64_t)STRIP_T);
-    const float gn = gain[trk];
-    c2* const bufA = lds;
-    c2* const bufB = lds + PADM;
-    const int vo = 8 * lt;
-    const uint64_t cstart = f0 * (uint64_t)(hop / 2);
-    const uint64_t clen = (uint64_t)(nf - 1) * (uint64_t)(hop / 2) + (uint64_t)M;
-    const __amdgpu_buffer_rsrc_t rx = rsrc_of(samples + src_off[trk] + 2 * cstart, (uint32_t)(8u * clen));
-    const __amdgpu_buffer_rsrc_t rw = rsrc_of(window, 4u * 8192u);
-    const __amdgpu_buffer_rsrc_t rtw = rsrc_of(twp, 8u * 15u * (TPF + TPF / 16 + 1));
-    const __amdgpu_buffer_rsrc_t rrt = rsrc_of(rtp, 8u * (slide_rt_base<M>() + 8 * TPF + 1));
-    float* const row0 = mags + (mag_row0[trk] + f0) * (uint64_t)stride;
-
-    // per-strip constants (as k_stft_slide)
-    c2 win[16], tw1[15], tw2[15], tw3[15], wk[8], ring[16];
-#pragma unroll
-    for (int k = 0; k < 16; k++) {
-        const c2 x = ld_c2(rx, vo, 8 * TPF * k);
-        ring[k] = {x.x * gn, x.y * gn};
-    }
-#pragma unroll
-    for (int k = 0; k < 16; k++) win[k] = ld_c2(rw, vo, 8 * TPF * k);
-#pragma unroll
-    for (int j = 0; j < 15; j++) tw1[j] = ld_c2(rtw, vo, 8 * TPF * j);
-    const int pp2 = lt / 16, q2 = lt % 16;
-#pragma unroll
-    for (int j = 0; j < 15; j++) tw2[j] = ld_c2(rtw, 8 * pp2, 8 * (15 * TPF + j * (TPF / 16)));
-#pragma unroll
-    for (int j = 0; j < 8; j++) wk[j] = ld_c2(rrt, vo, 8 * (slide_rt_base<M>() + TPF * j));
-#pragma unroll
-    for (int j = 0; j < 15; j++) {
-        const cx t = twp[15 * TPF + 15 * (TPF / 16) + j];
-        tw3[j] = c2{t.re, t.im};
-    }
-    const c2 rtH = ld_c2(rrt, 0, 8 * (slide_rt_base<M>() + 8 * TPF));  // bin M/2
-    const int colA = slide_col8(lt);
-    const bool self0 = lt == 0, self128 = lt == 32;
-    const int src_lane = (self0 || self128) ? (lt & 63) : ((lt & 63) ^ 32);
-    // LDS bases: pass-2 reads x[q + 16 pp + 256 k] (lpad: + 272 k), writes z[q + 256 pp + 16 k] (+ 17 k);
-    // pass-3 reads column colA, Z[colA + 256 m] (+ 272 m)
-    const int rb2 = lpad(q2 + 16 * pp2), wb2 = q2 + P272 * pp2, rb3 = lpad(colA);
-    // byte offsets in a row: own bins colA + 256 j, partner bins M - colA - 256 j
-    const int vown = 4 * colA, vpart = 4 * (M - colA - 256 * 7), vmid = 4 * (M / 2);
-    __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0): the per-strip loads have landed
-
-    // prologue: pass 1 of frame 0 into A, the ring advanced to frame 1
-    c2 v[16];
-#pragma unroll
-    for (int k = 0; k < 16; k++) v[k] = {ring[k].x * win[k].x, ring[k].y * win[k].y};
-    radix16<false>(v, tw1);
-#pragma unroll
-    for (int k = 0; k < 16; k++) bufA[P17 * lt + k] = v[k];
-    {
-        c2 nx[S];
-#pragma unroll
-        for (int s2 = 0; s2 < S; s2++) nx[s2] = ld_c2(rx, vo, 8 * ((hop / 2) + TPF * (16 - S + s2)));
-#pragma unroll
-        for (int k = 0; k < 16 - S; k++) ring[k] = ring[k + S];
-#pragma unroll
-        for (int s2 = 0; s2 < S; s2++) ring[16 - S + s2] = {nx[s2].x * gn, nx[s2].y * gn};
-    }
-    __syncthreads();
-
-    // the held frame (i - 1): P[0..7] own Z[colA + 256 j], P[8..15] the partner column's elements
-    // 8..15 (received), Pm = own element 8 (bin M/2 on the column-0 lane)
-    c2 P[16], Pm = {0.0f, 0.0f};
-#pragma unroll
-    for (int k = 0; k < 16; k++) P[k] = {0.0f, 0.0f};
-    uint64_t miss = 0;  // wave-uniform: bit i = frame f0 + i met the sqrt's inexact range
-    for (int i = 0;; i++) {
-        // ---- region 1 ----
-        c2 nx[S];  // the ring's new values for frame i + 2 (zeros past the strip: outside rx)
-#pragma unroll
-        for (int s2 = 0; s2 < S; s2++) nx[s2] = ld_c2(rx, vo, 8 * ((i + 2) * (hop / 2) + TPF * (16 - S + s2)));
-#pragma unroll
-        for (int k = 0; k < 16; k++) v[k] = bufA[rb2 + P272 * k];
-        __builtin_amdgcn_sched_barrier(0);  // the reads first: the post-processing below covers their latency
-        {
-            // post-processing of frame i - 1 (sdsp_fft_spec.h STFT section; see k_stft_slide)
-            const bool live = i > 0;
-            const __amdgpu_buffer_rsrc_t ro = rsrc_of(row0 + (int64_t)(i - 1) * stride, live ? 4u * (M + 1) : 0u);
-            uint32_t lo = 0xFFFFFFFFu, hi = 0u;
-            // |X| = 2^-33 sqrt(e) with the exact fast sqrt
-            auto sq = [&](float yx, float yy) { return 0x1p-33f * sqrt_fast(__builtin_fmaf(yx, yx, yy * yy), lo, hi); };
-            auto st = [&](float mag, int voff, int soff) {
-                __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(mag), ro, voff, soff, 0);
-            };
-#pragma unroll
-            for (int j = 0; j < 8; j++) {
-                const c2 Zk = P[j], Zr = P[15 - j], w = wk[j];
-                const float sx = Zk.x + Zr.x, sy = Zk.y - Zr.y, dx = Zk.y + Zr.y, dy = -(Zk.x - Zr.x);
-                st(sq(__builtin_fmaf(w.x, dx, __builtin_fmaf(-w.y, dy, sx)), __builtin_fmaf(w.x, dy, __builtin_fmaf(w.y, dx, sy))),
-                   vown, 1024 * j);
-                st(sq(__builtin_fmaf(-w.x, dx, __builtin_fmaf(w.y, dy, sx)), __builtin_fmaf(w.x, dy, __builtin_fmaf(w.y, dx, -sy))),
-                   vpart, 1024 * (7 - j));
-            }
-            if (self0) {  // bin M/2, self-paired
-                const c2 Z = Pm, w = rtH;
-                const float sx = Z.x + Z.x, sy = Z.y - Z.y, dx = Z.y + Z.y, dy = -(Z.x - Z.x);
-                st(sq(__builtin_fmaf(w.x, dx, __builtin_fmaf(-w.y, dy, sx)), __builtin_fmaf(w.x, dy, __builtin_fmaf(w.y, dx, sy))),
-                   vmid, 0);
-            }
-            const bool missed = __builtin_amdgcn_ballot_w64(sqrt_fast_missed(lo, hi)) != 0;
-            miss |= (uint64_t)(missed && live) << ((i - 1) & 63);
-        }
-        if (i == nf) break;
-        radix16<false>(v, tw2);
-#pragma unroll
-        for (int k = 0; k < 16; k++) bufB[wb2 + P17 * k] = v[k];
-        __syncthreads();
-        __builtin_amdgcn_sched_barrier(0);  // keep region 2's VALU below the barrier (it covers the pass-3 reads)
-        // ---- region 2 ----
-        c2 u[16];
-#pragma unroll
-        for (int k = 0; k < 16; k++) u[k] = bufB[rb3 + P272 * k];
-        __builtin_amdgcn_sched_barrier(0);  // the reads first: pass 1 below covers their latency
-        // pass 1 of frame i + 1 (past the strip's end: unused values into A, nothing reads them)
-#pragma unroll
-        for (int k = 0; k < 16; k++) v[k] = {ring[k].x * win[k].x, ring[k].y * win[k].y};
-        radix16<false>(v, tw1);
-#pragma unroll
-        for (int k = 0; k < 16; k++) bufA[P17 * lt + k] = v[k];
-#pragma unroll
-        for (int k = 0; k < 16 - S; k++) ring[k] = ring[k + S];
-#pragma unroll
-        for (int s2 = 0; s2 < S; s2++) ring[16 - S + s2] = {nx[s2].x * gn, nx[s2].y * gn};
-        // pass 3 of frame i (n = 16, s = 256, p' = 0) on column colA, then the exchange: every lane
-        // sends its elements 8..15 to the partner lane; the column-0 lane sends itself 9..15, 0
-        radix16<true>(u, tw3);
-#pragma unroll
-        for (int k = 0; k < 8; k++) {
-            const c2 snd = self0 ? u[(9 + k) & 15] : u[8 + k];
-            P[8 + k] = {__shfl(snd.x, src_lane, 64), __shfl(snd.y, src_lane, 64)};
-            P[k] = u[k];
-        }
-        Pm = u[8];
-        __syncthreads();
-        __builtin_amdgcn_sched_barrier(0);  // keep the post-processing below the barrier (it covers the pass-2 reads)
-    }
-    // list the strip's missed frames once (k_stft_mag recomputes them right after this kernel)
-    if ((lt & 63) == 0) miss_mask[lt >> 6] = miss;
-    __syncthreads();
-    if (lt == 0) {
-        uint64_t m = miss_mask[0] | miss_mask[1] | miss_mask[2] | miss_mask[3];
-        while (m) {
-            const int b = __builtin_ctzll(m);
-            m &= m - 1;
-            redo[1 + atomicAdd(redo, 1u)] = (uint32_t)(frame_pfx[trk] + f0 + (uint64_t)b);
-        }
-    }
-}
-
-// ---------------------------------------------------------------------------------------------
-// k_stft_slide8w3: the sliding strip for N = 8192 at 3 waves per SIMD (3 workgroups per CU; the
-// budget is <= 168 VGPRs and <= 53 KB of LDS per 256-thread workgroup).  k_stft_slide8 runs 2
-// waves per SIMD (229 VGPRs, two 34.8 KB frame buffers), and one wave issues a VALU instruction
-// at most every 4 cycles, so the SIMD's VALU idles whenever either wave waits.
-// What moves to fit the budget, the arithmetic unchanged (bit-identical magnitudes):
+// k_stft_slide8w3: the sliding strip for N = 8192 (M = 4096 = 16^3, one 256-thread workgroup per
+// strip) at 3 waves per SIMD (3 workgroups per CU; the budget is <= 168 VGPRs and <= 53 KB of LDS
+// per 256-thread workgroup).  One wave issues a VALU instruction at most every 4 cycles, so with 2
+// waves per SIMD the VALU idles whenever either wave waits: a layout with every per-strip constant
+// in registers and two frame buffers (229 VGPRs, 69.6 KB) measured 51 % VALU-active and 0.114 ms
+// per track against 0.110 for this one (profiles/r03_sq_isolated.txt,
+// r04j_sq_stft8192_isolated.txt, r04j_stft_probe.jsonl).  How it fits the budget,
+// with k_stft_mag's arithmetic (bit-identical magnitudes):
 //  * ONE frame buffer, pass 2 in place: a pass-2 thread reads its 16 slots, runs the radix-16
 //    pass and writes the 16 results back into the same slots (the threads' slot sets are
 //    disjoint, so no barrier between its reads and its writes).  Element z[q + 256 pp + 16 k]
@@ -1166,6 +783,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 //  * the pass-2 twiddles (16 p' x 15, 1.9 KB, four distinct p' per wave: broadcast reads) and the
 //    post twiddles (8 slots x 256 lanes, 16 KB) from LDS instead of 46 VGPRs; the pass-3
 //    twiddles stay wave-uniform scalars; window, pass-1 twiddles and the sample ring stay in VGPRs.
+// Rows are written by buffer stores whose per-lane offsets are fixed for the strip and whose row
+// is a scalar descriptor (no 64-bit address arithmetic per store).  Frames whose sqrt met an input
+// outside its exact range are collected in a wave-uniform 64-bit mask and listed once per strip
+// after the loop.
 template <int S>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) void k_stft_slide8w3(
     const float* __restrict__ samples, const uint64_t* __restrict__ frame_pfx, const uint64_t* __restrict__ strip_pfx,
@@ -1263,12 +884,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
         __syncthreads();
         // last pass (n = 16, s = 256, p' = 0) on column colA, then the (k, M-k) exchange between
         // lanes l and l^32: every lane sends its elements 8..15; the column-0 lane sends itself 9..15, 0
-#ifndef SDSP_STFT8_PAIRED
         lds_ld16<P17>(&buf[rb3], v);
-#else
-#pragma unroll
-        for (int k = 0; k < 16; k++) v[k] = buf[rb3 + P17 * k];
-#endif
         radix16<true>(v, tw3);
         c2 P[16];
 #pragma unroll
@@ -1278,7 +894,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
             P[k] = v[k];
         }
         const c2 Pm = v[8];
-        // post-processing of frame i (sdsp_fft_spec.h STFT section; see k_stft_slide)
+        // post-processing of frame i (sdsp_fft_spec.h STFT section; see k_stft_slide2s)
         const __amdgpu_buffer_rsrc_t ro = rsrc_of(row0 + (int64_t)i * stride, 4u * (M + 1));
         uint32_t lo = 0xFFFFFFFFu, hi = 0u;
         auto sq = [&](float yx, float yy) { return 0x1p-33f * sqrt_fast(__builtin_fmaf(yx, yx, yy * yy), lo, hi); };
@@ -1396,7 +1012,7 @@ void stft_tables(int N, const std::vector<float>& tw, const std::vector<float>& 
     put(rtp, (size_t)sp + 1, rtm);
     put(rtp, (size_t)sp + 2, &rt[2 * (size_t)(M / 2)]);
     put(rtp, (size_t)sp + 3, &tw[0]);
-    // k_stft_slide's post table: [slot j < 8][lane] = rt of the slot's own bin (slide_bin), then
+    // the sliding-strip kernels' post table: [slot j < 8][lane] = rt of the slot's own bin (slide_bin), then
     // rt[M/2]; bins above M/2 take the symmetric value (-rt[M-k].re, rt[M-k].im)
     const size_t sbase = (size_t)sp + 4;
     rtp->resize(2 * (sbase + 8 * (size_t)TPF + 1), 0.0f);
@@ -1413,12 +1029,56 @@ void stft_tables(int N, const std::vector<float>& tw, const std::vector<float>& 
 bool stft_tuned(int N) { return N == 2048 || N == 8192; }
 bool stft_size_ok(int N) { return N >= STFT_GEN_MIN && N <= STFT_GEN_MAX && (N & (N - 1)) == 0; }
 
-// hop = S * 2 * TPF complex values with a k_stft_slide instance
+// hop = S * 2 * TPF samples with a k_stft_slide8w3<S> / k_stft_slide2s<S> instance (launch_stft)
 bool stft_slide_ok(int nfft, int hop) {
     if (nfft == 8192) return hop == 512 || hop == 1024;
     if (nfft == 2048) return hop == 256 || hop == 512 || hop == 1024;
     return false;
 }
+
+namespace {
+// launch_stft's arguments as the tuned kernels take them, and one launch helper per kernel
+struct StftArgs {
+    const float *samples, *gain, *window;
+    const uint64_t *frame_pfx, *strip_pfx, *src_off, *mag_row0;
+    const cx *twp, *rtp;
+    float *mags, *fmax;
+    uint32_t* redo;
+    int n_tracks, hop, stride;
+    uint64_t total_frames, n_strips;
+    hipStream_t st;
+};
+template <int S>
+void slide8w3(const StftArgs& a) {  // one workgroup per strip
+    hipLaunchKernelGGL(k_stft_slide8w3<S>, dim3((unsigned)a.n_strips), dim3(256), 0, a.st, a.samples, a.frame_pfx,
+                       a.strip_pfx, a.n_tracks, a.n_strips, a.src_off, a.gain, a.hop, a.window, a.twp, a.rtp, a.mags,
+                       a.mag_row0, a.stride, a.redo);
+}
+template <int S, bool FM>
+void slide2s(const StftArgs& a) {  // 4 strips per workgroup
+    hipLaunchKernelGGL((k_stft_slide2s<S, FM>), dim3((unsigned)((a.n_strips + 3) / 4)), dim3(256), 0, a.st, a.samples,
+                       a.frame_pfx, a.strip_pfx, a.n_tracks, a.n_strips, a.src_off, a.gain, a.hop, a.window, a.twp,
+                       a.rtp, a.mags, a.mag_row0, a.stride, a.fmax, a.redo);
+}
+template <bool FM>
+void slide2s_by_hop(const StftArgs& a) {
+    if (a.hop == 256) return slide2s<2, FM>(a);
+    if (a.hop == 512) return slide2s<4, FM>(a);
+    slide2s<8, FM>(a);
+}
+template <int NFFT, bool FM>
+void mag(const StftArgs& a, dim3 grid, const uint32_t* redo) {
+    hipLaunchKernelGGL((k_stft_mag<NFFT, FM>), grid, dim3(256), 0, a.st, a.samples, a.frame_pfx, a.n_tracks,
+                       a.total_frames, a.src_off, a.gain, a.hop, a.window, a.twp, a.rtp, a.mags, a.mag_row0, a.stride,
+                       a.fmax, redo);
+}
+// k_stft_mag over the whole launch (redo = nullptr) or over the redo list
+void mag_for(const StftArgs& a, int nfft, bool frame_max, dim3 grid, const uint32_t* redo) {
+    if (nfft == 8192) return mag<8192, false>(a, grid, redo);
+    if (frame_max) return mag<2048, true>(a, grid, redo);
+    mag<2048, false>(a, grid, redo);
+}
+}  // namespace
 
 // host launcher (the runtime owns all buffers; see runtime.hip).  With strip_pfx (stft_strips of
 // the frame prefix, on the device) and a hop stft_slide_ok accepts, the sliding-strip kernel runs;
@@ -1448,83 +1108,23 @@ void launch_stft(int nfft, bool frame_max, const float* samples, const uint64_t*
                                n_tracks, total_frames, src_off, gain, hop, window, twp, rtp, mags, mag_row0, stride, fmax);
         return;
     }
+    const StftArgs a = {samples, gain, window, frame_pfx, strip_pfx, src_off, mag_row0, twp, rtp,
+                        mags, fmax, redo, n_tracks, hop, stride, total_frames, n_strips, st};
     if (strip_pfx && n_strips && redo && stft_slide_ok(nfft, hop)) {
         // redo[0] = 0; redo[1..] receives the frames the sliding kernel could not finish exactly
         SDSP_HIP_CHECK(hipMemsetAsync(redo, 0, sizeof(uint32_t), st));
-#ifdef SDSP_STFT2_W2
-#define SDSP_SLIDE(N, S, FM)                                                                                      \
-    hipLaunchKernelGGL((k_stft_slide<N, S, FM>), dim3((unsigned)((n_strips + 256 / (N / 32) - 1) / (256 / (N / 32)))), \
-                       block, 0, st, samples, frame_pfx, strip_pfx, n_tracks, n_strips, src_off, gain, hop, window, twp, \
-                       rtp, mags, mag_row0, stride, fmax, redo)
-#else
-#define SDSP_SLIDE(N, S, FM)                                                                                      \
-    hipLaunchKernelGGL((k_stft_slide2s<S, FM>), dim3((unsigned)((n_strips + 3) / 4)), block, 0, st, samples,         \
-                       frame_pfx, strip_pfx, n_tracks, n_strips, src_off, gain, hop, window, twp, rtp, mags, mag_row0, \
-                       stride, fmax, redo)
-#endif
-        if (nfft == 8192) {
-            const dim3 g8((unsigned)n_strips);
-            // SDSP_STFT8_CAP2 (experiment): 4 KB of dynamic LDS beside the 53 KB static make a
-            // workgroup too large for 3 per CU, so the kernel runs 2 per CU
-#ifdef SDSP_STFT8_CAP2
-            const size_t dyn8 = 4096;
-#else
-            const size_t dyn8 = 0;
-#endif
-#ifdef SDSP_STFT8_W2
-#define SDSP_K8 k_stft_slide8
-#else
-#define SDSP_K8 k_stft_slide8w3
-#endif
-            if (hop == 512)
-                hipLaunchKernelGGL(SDSP_K8<1>, g8, block, dyn8, st, samples, frame_pfx, strip_pfx, n_tracks, n_strips,
-                                   src_off, gain, hop, window, twp, rtp, mags, mag_row0, stride, redo);
-            else
-                hipLaunchKernelGGL(SDSP_K8<2>, g8, block, dyn8, st, samples, frame_pfx, strip_pfx, n_tracks, n_strips,
-                                   src_off, gain, hop, window, twp, rtp, mags, mag_row0, stride, redo);
-#undef SDSP_K8
-        } else if (frame_max) {
-            if (hop == 256)
-                SDSP_SLIDE(2048, 2, true);
-            else if (hop == 512)
-                SDSP_SLIDE(2048, 4, true);
-            else
-                SDSP_SLIDE(2048, 8, true);
-        } else {
-            if (hop == 256)
-                SDSP_SLIDE(2048, 2, false);
-            else if (hop == 512)
-                SDSP_SLIDE(2048, 4, false);
-            else
-                SDSP_SLIDE(2048, 8, false);
-        }
-#undef SDSP_SLIDE
-        // the redo pass: a few workgroups that read the count and exit when it is 0
-        const dim3 rgrid(256);
         if (nfft == 8192)
-            hipLaunchKernelGGL((k_stft_mag<8192, false>), rgrid, block, 0, st, samples, frame_pfx, n_tracks, total_frames,
-                               src_off, gain, hop, window, twp, rtp, mags, mag_row0, stride, fmax, redo);
+            hop == 512 ? slide8w3<1>(a) : slide8w3<2>(a);
         else if (frame_max)
-            hipLaunchKernelGGL((k_stft_mag<2048, true>), rgrid, block, 0, st, samples, frame_pfx, n_tracks, total_frames,
-                               src_off, gain, hop, window, twp, rtp, mags, mag_row0, stride, fmax, redo);
+            slide2s_by_hop<true>(a);
         else
-            hipLaunchKernelGGL((k_stft_mag<2048, false>), rgrid, block, 0, st, samples, frame_pfx, n_tracks, total_frames,
-                               src_off, gain, hop, window, twp, rtp, mags, mag_row0, stride, fmax, redo);
+            slide2s_by_hop<false>(a);
+        // the redo pass: a few workgroups that read the count and exit when it is 0
+        mag_for(a, nfft, frame_max, dim3(256), redo);
         return;
     }
-    if (nfft == 2048) {
-        const dim3 grid((unsigned)((total_frames + 3) / 4));
-        if (frame_max)
-            hipLaunchKernelGGL((k_stft_mag<2048, true>), grid, block, 0, st, samples, frame_pfx, n_tracks,
-                               total_frames, src_off, gain, hop, window, twp, rtp, mags, mag_row0, stride, fmax, nullptr);
-        else
-            hipLaunchKernelGGL((k_stft_mag<2048, false>), grid, block, 0, st, samples, frame_pfx, n_tracks,
-                               total_frames, src_off, gain, hop, window, twp, rtp, mags, mag_row0, stride, fmax, nullptr);
-    } else if (nfft == 8192) {
-        hipLaunchKernelGGL((k_stft_mag<8192, false>), dim3((unsigned)total_frames), block, 0, st, samples, frame_pfx,
-                           n_tracks, total_frames, src_off, gain, hop, window, twp, rtp, mags, mag_row0, stride, fmax,
-                           nullptr);
-    }
+    // frame-parallel: 4 frames per workgroup (N = 2048), one (N = 8192)
+    mag_for(a, nfft, frame_max, dim3((unsigned)(nfft == 2048 ? (total_frames + 3) / 4 : total_frames)), nullptr);
 }
 
 }  // namespace sdsp

@@ -205,10 +205,13 @@ __global__ __launch_bounds__(256) void k_fft_tempogram(const int* __restrict__ i
 
 // ----------------------------------------------------------------------------------------
 // Autocorrelation tempogram: one thread per BPM of the min..=max grid (lag per BPM given).  The
-// lag sum is a sequential fold; its operands are loaded ACF_U steps at a time, the next block in
-// flight while the current one is folded, so the fold waits on one L2 round trip per ACF_U steps
-// instead of one per step.  (Staging the curve in LDS measured 2x slower: 62 KB per workgroup
-// cut the waves per CU.)
+// lag sum is a sequential fold.  By default the novelty is staged through LDS in ACF_CH-frame
+// chunks (20 KB with the ACF_HMAX halo), 15 % faster per launch than folding from global memory;
+// staging the whole curve (62 KB per workgroup) had measured 2x slower, because it cut the waves
+// per CU.  What the halo does not cover (a lag above ACF_HMAX, or NB > blockDim) takes the
+// global-memory fold: its operands are loaded ACF_U steps at a time, the next block in flight
+// while the current one is folded, so the fold waits on one L2 round trip per ACF_U steps instead
+// of one per step.
 __global__ __launch_bounds__(256) void k_acf_tempogram(const int* __restrict__ items, const float* __restrict__ nov,
                                                        const uint64_t* __restrict__ frame_pfx, uint64_t total,
                                                        const float* __restrict__ bpm_grid,
@@ -223,7 +226,6 @@ __global__ __launch_bounds__(256) void k_acf_tempogram(const int* __restrict__ i
     const float* x = nov + (uint64_t)v * total + frame_pfx[trk];
     int K2 = 1;
     while (K2 < NB) K2 <<= 1;
-#ifndef SDSP_ACF_GLOBAL
     // The novelty is staged through LDS in ACF_CH-frame chunks with the largest lag as halo, and
     // every lag's thread continues its fold across the chunks (i ascending, the same products in
     // the same order): each step reads LDS instead of two vector-memory loads per element, which
@@ -261,49 +263,50 @@ __global__ __launch_bounds__(256) void k_acf_tempogram(const int* __restrict__ i
         } else if (j < K2) {
             keys[j] = ~0ull;  // K2 <= blockDim.x here (NB <= blockDim.x)
         }
-    } else
-#endif
-    for (int j = threadIdx.x; j < K2; j += blockDim.x) {
-        uint64_t key = ~0ull;
-        if (j < NB) {
-            const int64_t lag = lag_grid[j];
-            const int64_t n = L - lag;  // terms i = 0 .. n-1 (autocorrelation over i + lag < L)
-            float acc = 0.0f;
-            int64_t i = 0;
-            if (n >= ACF_U) {
-                float a[ACF_U], b[ACF_U], na[ACF_U], nb[ACF_U];
-#pragma unroll
-                for (int u = 0; u < ACF_U; u++) {
-                    a[u] = x[u];
-                    b[u] = x[u + lag];
-                }
-                for (;;) {
-                    const bool more = i + 2 * ACF_U <= n;
-                    if (more) {
-#pragma unroll
-                        for (int u = 0; u < ACF_U; u++) {
-                            na[u] = x[i + ACF_U + u];
-                            nb[u] = x[i + ACF_U + u + lag];
-                        }
-                    }
-#pragma unroll
-                    for (int u = 0; u < ACF_U; u++) acc += a[u] * b[u];
-                    i += ACF_U;
-                    if (!more) break;
+    } else {
+        // the global-memory fold: a lag beyond the halo, or more BPMs than threads
+        for (int j = threadIdx.x; j < K2; j += blockDim.x) {
+            uint64_t key = ~0ull;
+            if (j < NB) {
+                const int64_t lag = lag_grid[j];
+                const int64_t n = L - lag;  // terms i = 0 .. n-1 (autocorrelation over i + lag < L)
+                float acc = 0.0f;
+                int64_t i = 0;
+                if (n >= ACF_U) {
+                    float a[ACF_U], b[ACF_U], na[ACF_U], nb[ACF_U];
 #pragma unroll
                     for (int u = 0; u < ACF_U; u++) {
-                        a[u] = na[u];
-                        b[u] = nb[u];
+                        a[u] = x[u];
+                        b[u] = x[u + lag];
+                    }
+                    for (;;) {
+                        const bool more = i + 2 * ACF_U <= n;
+                        if (more) {
+#pragma unroll
+                            for (int u = 0; u < ACF_U; u++) {
+                                na[u] = x[i + ACF_U + u];
+                                nb[u] = x[i + ACF_U + u + lag];
+                            }
+                        }
+#pragma unroll
+                        for (int u = 0; u < ACF_U; u++) acc += a[u] * b[u];
+                        i += ACF_U;
+                        if (!more) break;
+#pragma unroll
+                        for (int u = 0; u < ACF_U; u++) {
+                            a[u] = na[u];
+                            b[u] = nb[u];
+                        }
                     }
                 }
+                for (; i < n; i++) acc += x[i] * x[i + lag];
+                const int32_t cnt = n > 0 ? (int32_t)n : 0;
+                const float sv = cnt > 0 ? acc / (float)cnt : 0.0f;
+                vals[j] = sv;
+                key = key_desc(sv, (uint32_t)j);
             }
-            for (; i < n; i++) acc += x[i] * x[i + lag];
-            const int32_t cnt = n > 0 ? (int32_t)n : 0;
-            const float sv = cnt > 0 ? acc / (float)cnt : 0.0f;
-            vals[j] = sv;
-            key = key_desc(sv, (uint32_t)j);
+            keys[j] = key;
         }
-        keys[j] = key;
     }
     block_bitonic_u64(keys, K2);
     float* ob = out_bpm + (uint64_t)blockIdx.x * NB;

@@ -136,7 +136,10 @@ struct BeatOut {
     int ok;
 };
 
-// ---- k_key ----
+// ---- k_mask, k_hpcp ----
+// k_mask*'s workgroup width (bins per workgroup, one wave) and thereby the width of the energy
+// partial-sum blocks k_mask_rp writes and k_hpcp_band folds (launch_hpcp_band's block count)
+constexpr int MASK_T = 64;
 constexpr int HP_KMAX = 32;
 constexpr int HP_FRAMES = 256;  // frames per k_hpcp workgroup
 constexpr int HP_HMAX = 8;
@@ -152,6 +155,7 @@ struct HpcpParams {
     int hmax;
     float p;
 };
+// ---- k_key_vote ----
 struct KeyParams {
     int weighting;
     float min_tonal, tonal_pow, energy_pow;
@@ -357,7 +361,7 @@ void launch_beat_sync(const int* tracks, int n_items, const uint64_t* frame_pfx,
                       const float* fenergy, const float* beats, const uint64_t* beat_off, const uint64_t* row_pfx,
                       float fd, float* chroma, float* energy, hipStream_t st);
 // the default key path's band-limited mask + block energy sums and the HPCP that reads them
-// (k_key.hip k_mask_rp / k_hpcp_band; only for margin 12, power 2)
+// (k_mask.hip k_mask_rp / k_hpcp.hip k_hpcp_band; only for margin 12, power 2)
 bool mask_band_ok(int margin, float power);
 void launch_mask_band(float* mags, int stride, int B, const uint64_t* frame_pfx, const int* tracks, int n_items,
                       float power, int st_lo, int st_hi, float* part, uint64_t total, hipStream_t st,

@@ -122,8 +122,8 @@ struct TestHooks {
 TestHooks& test_hooks();
 std::vector<int> test_hooks_devices();
 
-// STFT sizes with the tuned kernels (k_stft_mag / k_stft_slide: N = 2048, 8192).  Other powers of
-// two in [STFT_GEN_MIN, STFT_GEN_MAX], and N = 8192 with frame maxima, run the general kernel
+// STFT sizes with the tuned kernels (k_stft_mag, k_stft_slide2s, k_stft_slide8w3: N = 2048, 8192).
+// Other powers of two in [STFT_GEN_MIN, STFT_GEN_MAX], and N = 8192 with frame maxima, run the general kernel
 // k_stft_gen, which reads the spec's plain tables (FftTables::tw / rt); stft_twp / stft_rtp pick
 // the tables launch_stft expects.
 constexpr int STFT_GEN_MIN = 64, STFT_GEN_MAX = 16384;

@@ -103,7 +103,7 @@ def test_mode0_band_path():
     is within its own bound of the sequential fold; the bound is not vacuous (edel < 1) and, for
     e in [2^-60, 2^100], at most EDEL_CAP.
 
-    The cap, from energy_delta's formula (k_key.hip, "A rigorous bound on |e_blk - e_ref| / e_blk"),
+    The cap, from energy_delta's formula (k_hpcp.hip, "A rigorous bound on |e_blk - e_ref| / e_blk"),
     with u = 2^-24, S = sum of the block sums Bt_b, pu = S / (1 - g63):
       eref term   sum_b min(Bu_b, n_b u (1 + u) (1 + gN) pu_b) <= u (1 + u)(1 + gN) pu sum_b n_b = B u pu (1 + ..)
       block fold  u (1 + u)(1 + g64) sum_b (Bt_0 + .. + Bt_b)  <= n_blocks u S (1 + ..)

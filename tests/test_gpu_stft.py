@@ -12,8 +12,9 @@ pytestmark = pytest.mark.gpu
 @pytest.mark.parametrize("nfft,hop", [(2048, 512), (2048, 256), (2048, 1024), (8192, 512), (8192, 1024), (2048, 300),
                                       (8192, 256)])
 def test_stft_bit_exact(nfft, hop, frame_parallel):
-    """The sliding-strip kernel (hops k_stft_slide serves; strips of 64 frames, a partial last
-    strip) and the frame-parallel kernel (every hop; the stft_frame_parallel test hook forces it)."""
+    """The sliding-strip kernels (the hops k_stft_slide2s / k_stft_slide8w3 serve; strips of 64 frames,
+    a partial last strip) and the frame-parallel kernel (every hop; the stft_frame_parallel test hook
+    forces it)."""
     rng = np.random.default_rng(nfft + hop)
     x = (rng.standard_normal(44100 * 3) * 0.3).astype(np.float32)
     gain = np.float32(0.8912509)

@@ -12,7 +12,8 @@ base=$(basename $src .hip)
 make -s -j8 >/dev/null
 mkdir -p lib_exp build/exp
 HIPFLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -fno-fast-math -fhip-fp32-correctly-rounded-divide-sqrt -Wno-unused-result -fno-slp-vectorize -I$(pwd)/csrc"
-others=$(ls build/*.o | grep -v "build/$base.o")
+# the objects of the current sources (build/ may still hold objects of files since removed)
+others=$(for s in csrc/*.hip; do b=$(basename $s .hip); [ "$b" = "$base" ] || echo build/$b.o; done)
 names=()
 while [ $# -ge 2 ]; do
   name=$1; flags=$2; shift 2

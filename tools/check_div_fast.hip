@@ -1,6 +1,6 @@
 // Exhaustive GPU check of two FMA-corrected f32 divisions against the correctly rounded a / b
 // (-fhip-fp32-correctly-rounded-divide-sqrt), for the mask quotient hp / (hp + rp + eps)
-// (k_key.hip) and the per-frame X / max quotient (k_features.hip):
+// (k_mask.hip) and the per-frame X / max quotient (k_features.hip):
 //   D1 (general):   y = rcp(b); y1 = y + y (1 - b y); q0 = a y1; q = q0 + (a - b q0) y1
 //   D2 (fixed b):   yr = 1 / b correctly rounded once per divisor; q = q0 + (a - b q0) yr, q0 = a yr
 // Every step is a scaled-exact operation (FMA, products, the hardware reciprocal), so for normal

@@ -19,7 +19,7 @@ KERNEL = "k_stft_slide8w3<" if N == 8192 else "k_stft_slide2s<"  # the pipeline'
 
 
 def dispatches(path, name):
-    # the product kernel (k_stft_slide; k_stft_mag is its out-of-line fix-up pass)
+    # the product kernel (k_stft_slide2s / k_stft_slide8w3; k_stft_mag is its out-of-line fix-up pass)
     rows = [r for r in csv.DictReader(open(path))
             if r["Counter_Name"] == name and KERNEL in r["Kernel_Name"]]
     if not rows:
