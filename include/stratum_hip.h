@@ -417,6 +417,43 @@ int32_t sdsp_decode_batch_device(const uint8_t* const* files, const uint64_t* si
  * (sdsp_last_flac_decode_stats keeps reporting calls made through the FLAC entry). */
 int32_t sdsp_last_decode_stats(int32_t device, sdsp_decode_stats* out);
 
+/*
+ * Batched decode on the device of everything the front-end reads: sdsp_decode_batch_device with
+ * Ogg Vorbis on the device as well.  Arguments, ownership, per-file status and error texts are
+ * those of sdsp_decode_batch_device, and every file that entry dispatches is dispatched the same
+ * way here; in addition
+ *   Ogg Vorbis (the first logical stream)  the Vorbis kernels: one lane per packet decodes floors,
+ *                                          residues and coupling into spectra, the inverse MDCT and
+ *                                          window per (packet, channel), the overlap-add and mono
+ *                                          mix per output sample
+ * bit-identical to sdsp_decode_audio_file on the same bytes.  The host plan reads the Ogg pages,
+ * the headers and each audio packet's first bits, so a header the host decoder refuses is that
+ * file's error with the host's text, not a fallback.  Decoded by the host decoder, uploaded and
+ * counted in host_fallback_files: G.711, ADPCM, CAF lpcm, Ogg FLAC, Opus and every other
+ * unsupported codec (which gets the host's error text), Matroska (Vorbis in Matroska included), an
+ * ALAC frame length above 16384, PCM wider than 8 channels, a Vorbis setup whose flattened tables
+ * exceed 64 MiB, a file of 2 GiB or more, files past the call's HBM budget.  sdsp_decode_batch_device
+ * keeps its contract: there an Ogg file is a host fallback.
+ */
+typedef struct sdsp_audio_decode_stats {
+    uint64_t files, device_files, host_fallback_files, error_files;
+    uint64_t flac_files, alac_files, pcm_files, vorbis_files; /* device files per family */
+    uint64_t alac_packets, alac_packets_decoded, alac_packets_skipped;
+    uint64_t vorbis_packets;        /* kept audio packets of the device Vorbis files */
+    uint64_t vorbis_packets_zeroed; /* of those: a floor decode failed, the block is silent */
+    uint64_t bytes_in, samples_out;
+    double upload_ms, flac_ms, alac_ms, pcm_ms, gather_ms, vorbis_ms; /* HIP events */
+    double total_ms;                                                  /* the call's wall time */
+} sdsp_audio_decode_stats;
+
+int32_t sdsp_decode_audio_batch_device(const uint8_t* const* files, const uint64_t* sizes, uint64_t n_files,
+                                       int32_t device, void* stream,
+                                       float** d_samples, /* out: free with sdsp_device_free */
+                                       uint64_t* offsets, uint64_t* lens, uint32_t* sample_rates,
+                                       int32_t* status, char* errs /* n_files x 256 */);
+/* Counters and phase times of the last sdsp_decode_audio_batch_device call on `device`. */
+int32_t sdsp_last_audio_decode_stats(int32_t device, sdsp_audio_decode_stats* out);
+
 /* Library identification: "stratum-hip <abi> gfx950" */
 const char* sdsp_version(void);
 

@@ -177,6 +177,19 @@ int32_t sdsp_debug_alac_decode_phased(const uint8_t* data, uint64_t n, float** s
                                       uint32_t* sample_rate, uint64_t counts[3], char* err, uint64_t errlen);
 
 /*
+ * The device Vorbis decoder's phases on the CPU, through the code the kernels run
+ * (csrc/vorbis_core.hpp) and with their buffer layouts (csrc/vorbis_phased.hpp): the host plan (Ogg
+ * pages, the identification and setup headers, every audio packet's first bits), every kept
+ * packet's spectra, every (packet, channel) windowed block, every output sample from its packet
+ * pair.  Status, text and samples equal sdsp_decode_audio_file's for the same bytes in a file;
+ * *samples is malloc'ed (sdsp_free_samples).  info (NULL allowed) receives the kept packets and
+ * those a failed floor decode silenced.  SDSP_ERR_NOT_IMPLEMENTED ("not planned: ...") for bytes
+ * that are no Ogg Vorbis stream.  No device is touched.
+ */
+int32_t sdsp_debug_vorbis_decode_phased(const uint8_t* data, uint64_t n, float** samples, uint64_t* n_samples,
+                                        uint32_t* sample_rate, uint64_t info[2], char* err, uint64_t errlen);
+
+/*
  * The device PCM path's steps on the CPU: the host plan of a RIFF/WAVE or AIFF / AIFF-C file, then
  * csrc/pcm_core.hpp over the planned frames.  info (NULL allowed) receives the plan: sample kind
  * (0 u8, 1 s16, 2 s24, 3 s32, 4 f32, 5 f64) | big-endian << 8, channels, data offset, frames.

@@ -8,8 +8,8 @@
 //
 // --gpu-decode (opt-in; the output is the same): the workers only read the files' bytes.  The files
 // are cut into chunks under a device-memory bound, and each chunk is decoded on a GPU by
-// sdsp_decode_batch_device (native FLAC, ALAC in M4A / CAF, WAV and AIFF PCM by HIP kernels; every
-// other format by the host decoder inside that call) and analysed from the device buffer
+// sdsp_decode_audio_batch_device (native FLAC, ALAC in M4A / CAF, WAV and AIFF PCM, Ogg Vorbis by HIP
+// kernels; every other format by the host decoder inside that call) and analysed from the device buffer
 // (sdsp_analyze_batch_device), one call per sample rate the decoder returned: no host PCM exists
 // and host memory holds the files' bytes only.  Chunks go round-robin over the devices of
 // --devices, one host thread per device.
@@ -32,7 +32,7 @@ struct Item {
     std::vector<float> samples;
     std::vector<uint8_t> bytes;  // --gpu-decode: the file's bytes
     uint64_t need = 0;           // --gpu-decode: device bytes the file's decode is expected to take
-    bool device = false;         // --gpu-decode: the file goes through sdsp_decode_batch_device
+    bool device = false;         // --gpu-decode: the file goes through sdsp_decode_audio_batch_device
     uint32_t sr = 0;
     bool decoded = false;
     std::string error;
@@ -141,7 +141,7 @@ int main(int argc, char** argv) {
                          "--jobs N        Decode workers (default: CPU-1)\n"
                          "--devices MASK  GPU bitmask (default: all visible GPUs)\n"
                          "--json          Emit one JSON object per line (JSONL)\n"
-                         "--gpu-decode    Decode on the GPUs: FLAC, ALAC (M4A / CAF), WAV and AIFF by kernels (same output)\n");
+                         "--gpu-decode    Decode on the GPUs: FLAC, ALAC (M4A / CAF), WAV, AIFF and Ogg Vorbis by kernels (same output)\n");
             return 0;
         } else {
             paths.push_back(s);
@@ -248,8 +248,8 @@ int main(int argc, char** argv) {
                 sizes[k] = items[ch.idx[k]].bytes.size();
             }
             float* d_samples = nullptr;
-            const int32_t rc = sdsp_decode_batch_device(ptrs.data(), sizes.data(), n, dev, nullptr, &d_samples, offs.data(),
-                                                        lens.data(), rates.data(), status.data(), errs.data());
+            const int32_t rc = sdsp_decode_audio_batch_device(ptrs.data(), sizes.data(), n, dev, nullptr, &d_samples, offs.data(),
+                                                              lens.data(), rates.data(), status.data(), errs.data());
             std::map<uint32_t, std::vector<size_t>> by_rate;  // the decoded files, by the rate the decoder returned
             for (size_t k = 0; k < n; k++) {
                 Item& it = items[ch.idx[k]];

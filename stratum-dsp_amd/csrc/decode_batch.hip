@@ -1,7 +1,8 @@
-// decode_batch.hip — sdsp_decode_batch_device: one batched lossless decode entry.  Every file is
+// decode_batch.hip — sdsp_decode_batch_device, the batched lossless decode entry, and
+// sdsp_decode_audio_batch_device, the same call with Ogg Vorbis on the device too.  Every file is
 // probed as the host front-end probes it (sdsp_probe_format) and sent to its stage
 // (decode_stages.hpp): native FLAC (k_flac.hip), ALAC in ISO MP4 / CAF (k_alac.hip), linear PCM in
-// RIFF/WAVE and AIFF (k_pcm.hip); everything else, and what a stage leaves, goes to the host
+// RIFF/WAVE and AIFF (k_pcm.hip), through the audio entry Ogg Vorbis (k_vorbis.hip); everything else, and what a stage leaves, goes to the host
 // decoder and is uploaded.  All tracks land in one caller-owned output buffer.  Also the parts of a
 // call the two batch entries share (Call's methods).
 #include <atomic>
@@ -22,6 +23,7 @@ namespace sdsp_dec {
 namespace {
 std::mutex g_mu;
 std::map<int, sdsp_decode_stats> g_stats;
+std::map<int, sdsp_audio_decode_stats> g_audio_stats;
 
 // pinned staging for the files' bytes, grow-only, per device (used under the device's lock)
 struct Pinned {
@@ -138,10 +140,12 @@ void Call::upload_fallbacks(float* out) {
 
 namespace {
 
-int32_t decode_batch(const uint8_t* const* files, const uint64_t* sizes, uint64_t n_files, int32_t device, void* stream,
+// `audio`: the call came through sdsp_decode_audio_batch_device, which also sends Ogg Vorbis to its
+// stage; through the lossless entry an Ogg file stays a host fallback
+int32_t decode_batch(bool audio, const uint8_t* const* files, const uint64_t* sizes, uint64_t n_files, int32_t device, void* stream,
                      float** d_samples, uint64_t* offsets, uint64_t* lens, uint32_t* rates, int32_t* status, char* errs) {
     const auto t_begin = std::chrono::steady_clock::now();
-    sdsp_decode_stats stt{};
+    sdsp_audio_decode_stats stt{};
     stt.files = n_files;
     DeviceCtx& c = device_ctx(device);
     std::lock_guard<std::mutex> lk(c.mu);
@@ -157,6 +161,15 @@ int32_t decode_batch(const uint8_t* const* files, const uint64_t* sizes, uint64_
     FlacStage flac;
     AlacStage alac;
     PcmStage pcm;
+    VorbisStage vorbis;
+    std::vector<VorbisPrepared> ogg_plans;  // the audio entry's Ogg files, in file order
+    size_t ogg_next = 0;
+    if (audio) {
+        std::vector<uint64_t> ogg_idx;
+        for (uint64_t i = 0; i < n_files; i++)
+            if (files[i] && sizes[i] < (1ull << 31) && sdsp_probe_format(files[i], sizes[i]) == SdspFormat::OGG) ogg_idx.push_back(i);
+        ogg_plans = VorbisStage::prepare(k, ogg_idx);
+    }
     for (uint64_t i = 0; i < n_files; i++) {
         stt.bytes_in += sizes[i];
         if (!files[i] || sizes[i] >= (1ull << 31)) {
@@ -175,6 +188,12 @@ int32_t decode_batch(const uint8_t* const* files, const uint64_t* sizes, uint64_
                     break;
                 case SdspFormat::WAV: pcm.plan(k, i, false); break;
                 case SdspFormat::AIFF: pcm.plan(k, i, true); break;
+                case SdspFormat::OGG:
+                    if (audio)
+                        vorbis.plan(k, i, ogg_plans[ogg_next++]);
+                    else
+                        k.fallback.push_back(i);
+                    break;
                 default: k.fallback.push_back(i);
             }
         } catch (const std::exception& e) {  // sizes a damaged header declares can make an allocation fail
@@ -182,7 +201,7 @@ int32_t decode_batch(const uint8_t* const* files, const uint64_t* sizes, uint64_
         }
     }
 
-    constexpr int NEV = 8;
+    constexpr int NEV = 10;
     hipEvent_t ev[NEV];
     for (auto& e : ev) SDSP_HIP_CHECK(hipEventCreate(&e));
     struct EvGuard {
@@ -199,6 +218,8 @@ int32_t decode_batch(const uint8_t* const* files, const uint64_t* sizes, uint64_
     flac.run(k, b_bytes, ev[7], ev[7], ev[2]);  // its inner phase marks are not reported here
     alac.run(k, b_bytes);
     SDSP_HIP_CHECK(hipEventRecord(ev[3], st));
+    vorbis.run(k);
+    SDSP_HIP_CHECK(hipEventRecord(ev[8], st));
 
     // ---- the files no stage took: the host decoder (overlaps the kernels) ----
     k.decode_fallbacks();
@@ -208,11 +229,15 @@ int32_t decode_batch(const uint8_t* const* files, const uint64_t* sizes, uint64_
     uint64_t total = flac.place(k, 0);
     total = alac.place(k, total);
     total = pcm.place(k, total);
+    total = vorbis.place(k, total);
     total = k.place_fallbacks(total);
     stt.flac_files = flac.device_files;
     stt.alac_files = alac.device_files;
     stt.pcm_files = pcm.device_files;
-    stt.device_files = stt.flac_files + stt.alac_files + stt.pcm_files;
+    stt.vorbis_files = vorbis.device_files;
+    stt.vorbis_packets = vorbis.packets;
+    stt.vorbis_packets_zeroed = vorbis.packets_zeroed;
+    stt.device_files = stt.flac_files + stt.alac_files + stt.pcm_files + stt.vorbis_files;
     stt.host_fallback_files = k.host_tracks.size();
     stt.alac_packets = alac.packets;
     stt.alac_packets_decoded = alac.packets_decoded;
@@ -228,6 +253,8 @@ int32_t decode_batch(const uint8_t* const* files, const uint64_t* sizes, uint64_
         SDSP_HIP_CHECK(hipEventRecord(ev[5], st));
         pcm.write(k, b_bytes, out);
         SDSP_HIP_CHECK(hipEventRecord(ev[6], st));
+        vorbis.write(k, out);
+        SDSP_HIP_CHECK(hipEventRecord(ev[9], st));
         k.upload_fallbacks(out);
         SDSP_HIP_CHECK(hipStreamSynchronize(st));
     } catch (...) {
@@ -247,9 +274,24 @@ int32_t decode_batch(const uint8_t* const* files, const uint64_t* sizes, uint64_
     stt.gather_ms = ms;  // both gathers
     SDSP_HIP_CHECK(hipEventElapsedTime(&ms, ev[5], ev[6]));
     stt.pcm_ms = ms;
+    SDSP_HIP_CHECK(hipEventElapsedTime(&ms, ev[3], ev[8]));
+    stt.vorbis_ms = ms;  // uploads, packets, imdct
+    SDSP_HIP_CHECK(hipEventElapsedTime(&ms, ev[6], ev[9]));
+    stt.vorbis_ms += ms;  // overlap-add
     stt.total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
     std::lock_guard<std::mutex> sl(g_mu);
-    g_stats[device] = stt;
+    if (audio) {
+        g_audio_stats[device] = stt;
+    } else {  // the lossless entry's struct is the audio one without the Vorbis fields
+        sdsp_decode_stats o{};
+        o.files = stt.files, o.device_files = stt.device_files, o.host_fallback_files = stt.host_fallback_files;
+        o.error_files = stt.error_files, o.flac_files = stt.flac_files, o.alac_files = stt.alac_files, o.pcm_files = stt.pcm_files;
+        o.alac_packets = stt.alac_packets, o.alac_packets_decoded = stt.alac_packets_decoded;
+        o.alac_packets_skipped = stt.alac_packets_skipped, o.bytes_in = stt.bytes_in, o.samples_out = stt.samples_out;
+        o.upload_ms = stt.upload_ms, o.flac_ms = stt.flac_ms, o.alac_ms = stt.alac_ms, o.pcm_ms = stt.pcm_ms;
+        o.gather_ms = stt.gather_ms, o.total_ms = stt.total_ms;
+        g_stats[device] = o;
+    }
     return SDSP_OK;
 }
 
@@ -258,9 +300,9 @@ int32_t decode_batch(const uint8_t* const* files, const uint64_t* sizes, uint64_
 
 extern "C" {
 
-int32_t sdsp_decode_batch_device(const uint8_t* const* files, const uint64_t* sizes, uint64_t n_files, int32_t device,
-                                 void* stream, float** d_samples, uint64_t* offsets, uint64_t* lens, uint32_t* sample_rates,
-                                 int32_t* status, char* errs) {
+static int32_t decode_entry(bool audio, const uint8_t* const* files, const uint64_t* sizes, uint64_t n_files, int32_t device,
+                            void* stream, float** d_samples, uint64_t* offsets, uint64_t* lens, uint32_t* sample_rates,
+                            int32_t* status, char* errs) {
     if (!d_samples || (n_files && (!files || !sizes || !offsets || !lens || !sample_rates || !status || !errs)))
         return SDSP_ERR_INVALID_INPUT;
     *d_samples = nullptr;
@@ -277,11 +319,31 @@ int32_t sdsp_decode_batch_device(const uint8_t* const* files, const uint64_t* si
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail_all("Processing error: no HIP device");
     if (device < 0 || device >= ndev) return fail_all("Processing error: no such HIP device");
     try {
-        return sdsp_dec::decode_batch(files, sizes, n_files, device, stream, d_samples, offsets, lens, sample_rates, status,
+        return sdsp_dec::decode_batch(audio, files, sizes, n_files, device, stream, d_samples, offsets, lens, sample_rates, status,
                                       errs);
     } catch (const std::exception& e) {
         return fail_all((std::string("Processing error: ") + e.what()).c_str());
     }
+}
+
+int32_t sdsp_decode_batch_device(const uint8_t* const* files, const uint64_t* sizes, uint64_t n_files, int32_t device,
+                                 void* stream, float** d_samples, uint64_t* offsets, uint64_t* lens, uint32_t* sample_rates,
+                                 int32_t* status, char* errs) {
+    return decode_entry(false, files, sizes, n_files, device, stream, d_samples, offsets, lens, sample_rates, status, errs);
+}
+
+int32_t sdsp_decode_audio_batch_device(const uint8_t* const* files, const uint64_t* sizes, uint64_t n_files, int32_t device,
+                                       void* stream, float** d_samples, uint64_t* offsets, uint64_t* lens, uint32_t* sample_rates,
+                                       int32_t* status, char* errs) {
+    return decode_entry(true, files, sizes, n_files, device, stream, d_samples, offsets, lens, sample_rates, status, errs);
+}
+
+int32_t sdsp_last_audio_decode_stats(int32_t device, sdsp_audio_decode_stats* out) {
+    if (!out) return SDSP_ERR_INVALID_INPUT;
+    std::lock_guard<std::mutex> sl(sdsp_dec::g_mu);
+    auto it = sdsp_dec::g_audio_stats.find(device);
+    *out = it == sdsp_dec::g_audio_stats.end() ? sdsp_audio_decode_stats{} : it->second;
+    return SDSP_OK;
 }
 
 int32_t sdsp_last_decode_stats(int32_t device, sdsp_decode_stats* out) {

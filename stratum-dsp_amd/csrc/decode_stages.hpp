@@ -1,9 +1,11 @@
 // decode_stages.hpp — the stages of the batched device decode (host only).  One call
-// (sdsp_decode_batch_device in decode_batch.hip, sdsp_decode_flac_batch_device in k_flac.hip) is a
+// (sdsp_decode_batch_device and sdsp_decode_audio_batch_device in decode_batch.hip,
+// sdsp_decode_flac_batch_device in k_flac.hip) is a
 // Call plus one stage per format it sends to the device; every stage has the same four steps:
 //   plan    on the host: parse the container, commit HBM from the call's budget, reserve the file's
 //           place in the bytes buffer (or leave the file to the host decoder, or set its error);
-//   run     after the bytes are uploaded: the kernels that find each file's length;
+//   run     after the bytes are uploaded: the kernels that find each file's length (PCM and Vorbis
+//           know it from the plan: Vorbis decodes here, into its own buffers);
 //   place   after the stream is synchronised: offsets and lengths of the stage's files in the
 //           call's one output buffer;
 //   write   the kernels that write the tracks at those offsets.
@@ -17,6 +19,7 @@
 #include "../../include/stratum_hip.h"
 #include "lossless_host.hpp"
 #include "sdsp_runtime.hpp"
+#include "vorbis_host.hpp"
 
 namespace sdsp_dec {
 
@@ -140,6 +143,67 @@ struct PcmStage {
     void plan(Call& k, uint64_t i, bool aiff);
     uint64_t place(Call& k, uint64_t total);
     void write(Call& k, DevBuf& bytes, float* out);
+};
+
+// ---- Ogg Vorbis (k_vorbis.hip): packets, imdct | ola ----
+// Lengths follow from the packets' first bits, so the host plan knows them: run() only decodes.
+struct VorbisFile {
+    uint64_t tree_off, vq_off;  // the file's first entry in the stage's flat setup tables
+    uint32_t book_off, floor_off, res_off, map_off, mode_off;
+    int32_t channels, bs0, bs1, nmodes;
+    uint32_t p_first, p_count;  // its kept packets
+    uint64_t out_off, frames;   // the track in the output (place()), its length after the granule cut
+};
+
+struct VorbisPacket {
+    uint64_t off;   // first byte in the stage's packet bytes
+    uint64_t spec;  // first float of its spectra (channels x n/2); its windowed blocks start at 2 * spec
+    uint64_t out;   // first output sample in the file's track
+    uint32_t size, file;
+    uint16_t n, prev_n;
+    uint8_t blockflag, prev_long, next_long;
+};
+
+// a file whose flattened setup (decode trees, VQ values, floors, residues, mappings, modes) is larger
+// goes to the host decoder; libvorbis setups are a few hundred KiB
+constexpr uint64_t VORBIS_MAX_TABLE_BYTES = 64ull << 20;
+
+// the host plan of one file, made ahead of the stage's serial plan() on the call's worker threads
+struct VorbisPrepared {
+    int r = 0;  // sdsp_vorbis_plan_ogg's result, or -2: the plan threw (`why` holds the text)
+    std::string why;
+    sdsp_vorbis_plan pl;
+};
+
+struct VorbisStage {
+    std::vector<VorbisFile> ft;
+    std::vector<uint64_t> dev_idx;
+    std::vector<VorbisPacket> pk;
+    std::vector<std::vector<uint8_t>> file_bytes;  // per device file: its kept packets, back to back
+    std::vector<uint64_t> file_byte0;              // their first byte in the device's packet bytes
+    uint64_t bytes_total = 0;
+    std::vector<vorbis_core::Book> books;
+    std::vector<int32_t> trees;
+    std::vector<float> vq;
+    std::vector<vorbis_core::Floor> floors;
+    std::vector<vorbis_core::Residue> residues;
+    std::vector<vorbis_core::Mapping> maps;
+    std::vector<vorbis_core::Mode> modes;
+    uint64_t spec_total = 0;
+    std::vector<uint32_t> p_zero;  // per packet: a floor decode failed and the block is silent
+    // upload sources of run(), kept until the call's stream is synchronised
+    std::vector<double> tab;
+    std::vector<uint2> items;  // (packet, channel) by block size
+    std::vector<uint64_t> wave_off;
+    std::vector<uint32_t> wave_cap;
+    uint64_t device_files = 0, packets = 0, packets_zeroed = 0;
+
+    // the Ogg files' host plans (demultiplex, headers, every packet's first bits), several at a time
+    static std::vector<VorbisPrepared> prepare(const Call& k, const std::vector<uint64_t>& idx);
+    void plan(Call& k, uint64_t i, VorbisPrepared& pre);
+    void run(Call& k);
+    uint64_t place(Call& k, uint64_t total);
+    void write(Call& k, float* out);
 };
 
 }  // namespace sdsp_dec

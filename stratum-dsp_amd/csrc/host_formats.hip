@@ -25,6 +25,7 @@
 #include <vector>
 
 #include "lossless_host.hpp"
+#include "vorbis_host.hpp"
 
 bool sdsp_decode_flac(const std::vector<uint8_t>& f, std::vector<float>* out, uint32_t* sr, std::string* err);
 bool sdsp_decode_caf_alac(const std::vector<uint8_t>& f, std::vector<float>* out, uint32_t* sr, std::string* err);
@@ -345,9 +346,15 @@ uint32_t ogg_crc(const uint8_t* p, size_t n) {
 }
 }  // namespace
 
-// Ogg: the first logical stream's packets; the FLAC mapping is decoded, other codecs named
-bool sdsp_decode_ogg(const std::vector<uint8_t>& f, std::vector<float>* out, uint32_t* sr, std::string* err) {
-    std::vector<std::vector<uint8_t>> packets;
+// Ogg pages into the first logical stream's packets (also the Vorbis plan's demultiplexer)
+void sdsp_ogg_demux(const uint8_t* fdata, size_t fsize, std::vector<std::vector<uint8_t>>* packets_out, int64_t* last_granule_out) {
+    struct {
+        const uint8_t* d;
+        size_t n;
+        size_t size() const { return n; }
+        const uint8_t* data() const { return d; }
+    } f{fdata, fsize};
+    std::vector<std::vector<uint8_t>>& packets = *packets_out;
     std::vector<uint8_t> cur;
     bool have_serial = false;
     uint32_t serial = 0;
@@ -391,6 +398,14 @@ bool sdsp_decode_ogg(const std::vector<uint8_t>& f, std::vector<float>* out, uin
         }
         pos += plen;
     }
+    *last_granule_out = last_granule;
+}
+
+// Ogg: the first logical stream's packets; the FLAC mapping is decoded, other codecs named
+bool sdsp_decode_ogg(const std::vector<uint8_t>& f, std::vector<float>* out, uint32_t* sr, std::string* err) {
+    std::vector<std::vector<uint8_t>> packets;
+    int64_t last_granule = -1;
+    sdsp_ogg_demux(f.data(), f.size(), &packets, &last_granule);
     if (packets.empty()) return fail(err, "no Ogg packets");
     const std::vector<uint8_t>& h = packets[0];
     if (h.size() >= 7 && h[0] == 0x01 && std::memcmp(h.data() + 1, "vorbis", 6) == 0)

@@ -14,13 +14,21 @@
 // decoding error.  A lossy decoder's output depends on its arithmetic, so parity with
 // symphonia is unpinned: tests/vorbis_enc.py writes spec-conforming streams and the tests check
 // the decoded samples against the encoder's own synthesis of the quantised spectra.
+//
+// The packet-level code (bit reader, Huffman walk, floor 1, residues, coupling, the inverse MDCT,
+// the window, the overlap-add with the mono mix) is vorbis_core.hpp, the code the device kernels
+// (k_vorbis.hip) run.  Here: the setup header's parse into the core's flat structs, the tables of
+// transcendentals the core reads, the plan of a stream, and the packet loop of the host decoder.
 #include <algorithm>
 #include <array>
 #include <cmath>
-#include <complex>
 #include <cstring>
+#include <memory>
+#include <mutex>
 #include <string>
 #include <vector>
+
+#include "vorbis_host.hpp"
 
 namespace {
 
@@ -29,34 +37,11 @@ bool fail(std::string* err, const std::string& m) {
     return false;
 }
 
-// LSB-first bit reader (Vorbis packs fields from the least significant bit of each byte)
-struct LBits {
-    const uint8_t* p;
-    size_t n;
-    uint64_t pos = 0;
-    bool over = false;
-    LBits(const uint8_t* d, size_t len) : p(d), n(len) {}
-    uint32_t read(int k) {
-        uint32_t v = 0;
-        for (int i = 0; i < k; i++) {
-            const size_t b = (size_t)(pos >> 3);
-            if (b >= n) {
-                over = true;
-                return v;
-            }
-            v |= (uint32_t)((p[b] >> (pos & 7)) & 1) << i;
-            pos++;
-        }
-        return v;
-    }
-    bool bit() { return read(1) != 0; }
-};
+namespace vc = vorbis_core;
 
-int ilog(uint32_t v) {
-    int r = 0;
-    while (v) r++, v >>= 1;
-    return r;
-}
+// LSB-first bit reader (Vorbis packs fields from the least significant bit of each byte)
+using LBits = vc::Bits;
+using vc::ilog;
 
 float float32_unpack(uint32_t x) {
     const double mant = (double)(x & 0x1fffff);
@@ -148,19 +133,6 @@ struct Codebook {
             }
         }
         return true;
-    }
-    // -1: end of packet or an unassigned codeword
-    int decode(LBits& b) const {
-        int node = 0;
-        for (int depth = 0; depth < 33; depth++) {
-            const int bit = (int)b.read(1);
-            if (b.over) return -1;
-            const int32_t t = tree[(size_t)(2 * node + bit)];
-            if (t < 0) return -t - 1;
-            if (t == 0) return -1;
-            node = t;
-        }
-        return -1;
     }
 };
 
@@ -361,278 +333,124 @@ bool read_setup(LBits& b, Vorbis& v, std::string* err) {
     return true;
 }
 
-// floor 1 inverse dB table: -140 dB .. 0 dB in steps of 140/256 dB (table[255] = 1)
-float inverse_db(int i) {
-    static float tab[256];
-    static bool init = false;
-    if (!init) {
-        for (int k = 0; k < 256; k++) tab[k] = (float)std::pow(10.0, -(255 - k) * (140.0 / 256.0) / 20.0);
-        init = true;
+// the parsed setup into the core's flat structs (every index was checked by read_setup)
+void flatten(const Vorbis& v, sdsp_vorbis_setup* s) {
+    s->channels = v.channels;
+    s->rate = v.rate;
+    s->bs[0] = v.bs[0], s->bs[1] = v.bs[1];
+    for (const Codebook& c : v.books) {
+        vc::Book b{};
+        b.dims = c.dims, b.entries = c.entries, b.lookup = c.lookup;
+        b.tree_off = (uint32_t)s->trees.size(), b.tree_n = (uint32_t)c.tree.size();
+        s->trees.insert(s->trees.end(), c.tree.begin(), c.tree.end());
+        b.vq_off = (uint32_t)s->vq.size();
+        s->vq.insert(s->vq.end(), c.vq.begin(), c.vq.end());
+        s->books.push_back(b);
     }
-    return tab[i < 0 ? 0 : i > 255 ? 255 : i];
-}
-
-void render_line(int x0, int y0, int x1, int y1, std::vector<int>& v) {
-    if (x1 <= x0) return;  // setup parsing rejects repeated X values; a zero-width line draws nothing
-    const int dy = y1 - y0, adx = x1 - x0;
-    int ady = std::abs(dy);
-    const int base = dy / adx;
-    const int sy = dy < 0 ? base - 1 : base + 1;
-    int x = x0, y = y0, errv = 0;
-    ady -= std::abs(base) * adx;
-    if (x < (int)v.size()) v[(size_t)x] = y;
-    for (x = x0 + 1; x < x1; x++) {
-        errv += ady;
-        if (errv >= adx) {
-            errv -= adx;
-            y += sy;
-        } else {
-            y += base;
+    for (const Floor1& f : v.floors) {
+        vc::Floor o{};
+        o.partitions = f.partitions, o.multiplier = f.multiplier, o.rangebits = f.rangebits, o.nv = (int)f.X.size();
+        for (int i = 0; i < f.partitions; i++) o.part_class[i] = (uint8_t)f.part_class[(size_t)i];
+        for (size_t c = 0; c < f.class_dim.size(); c++) {
+            o.class_dim[c] = (uint8_t)f.class_dim[c];
+            o.class_sub[c] = (uint8_t)f.class_sub[c];
+            o.class_master[c] = (int16_t)f.class_master[c];
+            for (int j = 0; j < 8; j++) o.sub_books[c][j] = j < (int)f.sub_books[c].size() ? (int16_t)f.sub_books[c][(size_t)j] : (int16_t)-1;
         }
-        if (x < (int)v.size()) v[(size_t)x] = y;
-    }
-}
-
-// floor 1 packet decode + curve synthesis into curve[0 .. n/2); false: the channel is unused
-bool floor1_decode(LBits& b, const Vorbis& v, const Floor1& f, int n2, std::vector<float>& curve, bool* bad) {
-    *bad = false;
-    if (!b.bit()) return false;
-    static const int ranges[4] = {256, 128, 86, 64};
-    const int range = ranges[f.multiplier - 1];
-    const int nv = (int)f.X.size();
-    std::vector<int> Y((size_t)nv, 0);
-    Y[0] = (int)b.read(ilog((uint32_t)(range - 1)));
-    Y[1] = (int)b.read(ilog((uint32_t)(range - 1)));
-    int off = 2;
-    for (int p = 0; p < f.partitions; p++) {
-        const int c = f.part_class[(size_t)p];
-        const int cdim = f.class_dim[(size_t)c], cbits = f.class_sub[(size_t)c];
-        const int csub = (1 << cbits) - 1;
-        int cval = 0;
-        if (cbits > 0) {
-            cval = v.books[(size_t)f.class_master[(size_t)c]].decode(b);
-            if (cval < 0) return *bad = true, false;
-        }
-        for (int j = 0; j < cdim; j++) {
-            const int book = f.sub_books[(size_t)c][(size_t)(cval & csub)];
-            cval >>= cbits;
-            if (book >= 0) {
-                const int y = v.books[(size_t)book].decode(b);
-                if (y < 0) return *bad = true, false;
-                Y[(size_t)off++] = y;
-            } else {
-                Y[(size_t)off++] = 0;
+        const int nv = o.nv;
+        for (int i = 0; i < nv; i++) o.X[i] = (uint16_t)f.X[(size_t)i];
+        for (int i = 2; i < nv; i++) {  // the low / high neighbours among the earlier points
+            int lo = 0, hi = 1, lx = -1, hx = 1 << 30;
+            for (int j = 0; j < i; j++) {
+                if (f.X[(size_t)j] < f.X[(size_t)i] && f.X[(size_t)j] > lx) lx = f.X[(size_t)j], lo = j;
+                if (f.X[(size_t)j] > f.X[(size_t)i] && f.X[(size_t)j] < hx) hx = f.X[(size_t)j], hi = j;
             }
+            o.lo[i] = (uint8_t)lo, o.hi[i] = (uint8_t)hi;
         }
+        std::vector<int> order((size_t)nv);
+        for (int i = 0; i < nv; i++) order[(size_t)i] = i;
+        std::stable_sort(order.begin(), order.end(), [&](int a, int c) { return f.X[(size_t)a] < f.X[(size_t)c]; });
+        for (int i = 0; i < nv; i++) o.order[i] = (uint8_t)order[(size_t)i];
+        s->floors.push_back(o);
     }
-    if (b.over) return *bad = true, false;
-    // amplitude synthesis (step 1)
-    std::vector<int> fy((size_t)nv);
-    std::vector<char> used((size_t)nv, 0);
-    fy[0] = Y[0], fy[1] = Y[1];
-    used[0] = used[1] = 1;
-    for (int i = 2; i < nv; i++) {
-        int lo = 0, hi = 1, lx = -1, hx = 1 << 30;
-        for (int j = 0; j < i; j++) {
-            if (f.X[(size_t)j] < f.X[(size_t)i] && f.X[(size_t)j] > lx) lx = f.X[(size_t)j], lo = j;
-            if (f.X[(size_t)j] > f.X[(size_t)i] && f.X[(size_t)j] < hx) hx = f.X[(size_t)j], hi = j;
-        }
-        const int x0 = f.X[(size_t)lo], y0 = fy[(size_t)lo], x1 = f.X[(size_t)hi], y1 = fy[(size_t)hi];
-        const int dy = y1 - y0, adx = x1 - x0, ady = std::abs(dy);
-        const int e = ady * (f.X[(size_t)i] - x0);
-        const int o = e / adx;
-        const int pred = dy < 0 ? y0 - o : y0 + o;
-        const int val = Y[(size_t)i];
-        const int highroom = range - pred, lowroom = pred;
-        const int room = (highroom < lowroom ? highroom : lowroom) * 2;
-        if (val != 0) {
-            used[(size_t)lo] = used[(size_t)hi] = used[(size_t)i] = 1;
-            if (val >= room)
-                fy[(size_t)i] = highroom > lowroom ? val - lowroom + pred : pred - val + highroom - 1;
-            else
-                fy[(size_t)i] = (val & 1) ? pred - (val + 1) / 2 : pred + val / 2;
-        } else {
-            fy[(size_t)i] = pred;
-        }
+    for (const Residue& r : v.residues) {
+        vc::Residue o{};
+        o.type = r.type, o.begin = r.begin, o.end = r.end, o.psize = r.psize, o.classes = r.classes, o.classbook = r.classbook;
+        for (int c = 0; c < 64; c++)
+            for (int j = 0; j < 8; j++) o.books[c][j] = c < r.classes ? (int16_t)r.books[(size_t)c][(size_t)j] : (int16_t)-1;
+        s->residues.push_back(o);
     }
-    // curve synthesis (step 2): the used points in x order, lines between them
-    std::vector<int> order((size_t)nv);
-    for (int i = 0; i < nv; i++) order[(size_t)i] = i;
-    std::stable_sort(order.begin(), order.end(), [&](int a, int c) { return f.X[(size_t)a] < f.X[(size_t)c]; });
-    std::vector<int> iv((size_t)n2, 0);
-    int lx = 0, ly = fy[(size_t)order[0]] * f.multiplier, hx = 0, hy = 0;
-    for (int k = 1; k < nv; k++) {
-        const int i = order[(size_t)k];
-        if (!used[(size_t)i]) continue;
-        hy = fy[(size_t)i] * f.multiplier;
-        hx = f.X[(size_t)i];
-        if (lx < n2) render_line(lx, ly, hx, hy, iv);
-        lx = hx;
-        ly = hy;
+    for (const Mapping& m : v.maps) {
+        vc::Mapping o{};
+        o.submaps = m.submaps, o.steps = (int)m.mag.size();
+        for (size_t q = 0; q < m.mag.size(); q++) o.mag[q] = (uint8_t)m.mag[q], o.ang[q] = (uint8_t)m.ang[q];
+        for (int c = 0; c < v.channels; c++) o.mux[c] = (uint8_t)m.mux[(size_t)c];
+        for (int q = 0; q < m.submaps; q++) o.sub_floor[q] = (uint8_t)m.sub_floor[(size_t)q], o.sub_residue[q] = (uint8_t)m.sub_residue[(size_t)q];
+        s->maps.push_back(o);
     }
-    if (hx < n2) render_line(hx, hy, n2, hy, iv);
-    for (int j = 0; j < n2; j++) curve[(size_t)j] = inverse_db(iv[(size_t)j]);
-    return true;
-}
-
-// residue decode for the channels of one submap (vectors of n/2, zero on entry)
-bool residue_decode(LBits& b, const Vorbis& v, const Residue& r, int n2, std::vector<std::vector<float>*>& vecs,
-                    const std::vector<char>& skip) {
-    const int ch = (int)vecs.size();
-    const Codebook& cb = v.books[(size_t)r.classbook];
-    const int cwords = (int)cb.dims;
-    if (cwords <= 0) return false;
-    auto decode_set = [&](std::vector<std::vector<float>*>& vs, const std::vector<char>& sk, uint32_t size, int type) {
-        const uint32_t lb = std::min(r.begin, size), le = std::min(r.end, size);
-        const uint32_t nread = le > lb ? le - lb : 0;
-        const uint32_t parts = nread / r.psize;
-        if (parts == 0) return true;
-        const int nc = (int)vs.size();
-        std::vector<std::vector<int>> cls((size_t)nc, std::vector<int>((size_t)parts + (size_t)cwords, 0));
-        for (int pass = 0; pass < 8; pass++) {
-            uint32_t pc = 0;
-            while (pc < parts) {
-                if (pass == 0)
-                    for (int j = 0; j < nc; j++) {
-                        if (sk[(size_t)j]) continue;
-                        int temp = cb.decode(b);
-                        if (temp < 0) return false;
-                        for (int i = cwords - 1; i >= 0; i--) {
-                            cls[(size_t)j][(size_t)i + pc] = temp % r.classes;
-                            temp /= r.classes;
-                        }
-                    }
-                for (int i = 0; i < cwords && pc < parts; i++, pc++) {
-                    for (int j = 0; j < nc; j++) {
-                        if (sk[(size_t)j]) continue;
-                        const int book = r.books[(size_t)cls[(size_t)j][pc]][(size_t)pass];
-                        if (book < 0) continue;
-                        const Codebook& vb = v.books[(size_t)book];
-                        if (vb.lookup == 0 || vb.dims == 0) return false;
-                        std::vector<float>& out = *vs[(size_t)j];
-                        const uint32_t off = lb + pc * r.psize;
-                        const uint32_t dims = vb.dims;
-                        if (type == 0) {
-                            const uint32_t step = r.psize / dims;
-                            for (uint32_t s = 0; s < step; s++) {
-                                const int e = vb.decode(b);
-                                if (e < 0) return false;
-                                for (uint32_t k = 0; k < dims; k++) out[off + s + k * step] += vb.vq[(size_t)e * dims + k];
-                            }
-                        } else {
-                            uint32_t i2 = 0;
-                            while (i2 < r.psize) {
-                                const int e = vb.decode(b);
-                                if (e < 0) return false;
-                                for (uint32_t k = 0; k < dims && i2 < r.psize; k++) out[off + i2++] += vb.vq[(size_t)e * dims + k];
-                            }
-                        }
-                    }
-                }
-            }
-        }
-        return true;
-    };
-    if (r.type < 2) {
-        if (!decode_set(vecs, skip, (uint32_t)n2, r.type)) return false;
-        return true;
-    }
-    // type 2: the channels interleaved into one vector, decoded as format 1
-    bool any = false;
-    for (int j = 0; j < ch; j++) any = any || !skip[(size_t)j];
-    if (!any) return true;
-    std::vector<float> inter((size_t)n2 * (size_t)ch, 0.0f);
-    std::vector<std::vector<float>*> one{&inter};
-    std::vector<char> sk1{0};
-    if (!decode_set(one, sk1, (uint32_t)(n2 * ch), 1)) return false;
-    for (int i = 0; i < n2; i++)
-        for (int j = 0; j < ch; j++) (*vecs[(size_t)j])[(size_t)i] += inter[(size_t)i * ch + j];
-    return true;
-}
-
-// in-place radix-2 complex FFT (forward, exp(-2 pi i j k / n)), n a power of two
-void fft(std::vector<std::complex<double>>& a) {
-    const size_t n = a.size();
-    for (size_t i = 1, j = 0; i < n; i++) {
-        size_t bit = n >> 1;
-        for (; j & bit; bit >>= 1) j ^= bit;
-        j ^= bit;
-        if (i < j) std::swap(a[i], a[j]);
-    }
-    // twiddles exp(-2 pi i k / n) for k < n / 2, once per size (a stage of length len uses every
-    // (n / len)-th one)
-    static thread_local std::vector<std::complex<double>> tw;
-    static thread_local size_t tw_n = 0;
-    if (tw_n != n) {
-        tw.resize(n / 2);
-        for (size_t k = 0; k < n / 2; k++)
-            tw[k] = std::complex<double>(std::cos(-2.0 * M_PI * (double)k / (double)n), std::sin(-2.0 * M_PI * (double)k / (double)n));
-        tw_n = n;
-    }
-    for (size_t len = 2; len <= n; len <<= 1) {
-        const size_t stride = n / len;
-        for (size_t i = 0; i < n; i += len)
-            for (size_t k = 0; k < len / 2; k++) {
-                const std::complex<double> w = tw[k * stride];
-                const std::complex<double> u = a[i + k], t = a[i + k + len / 2] * w;
-                a[i + k] = u + t;
-                a[i + k + len / 2] = u - t;
-            }
-    }
-}
-
-// y[n] = sum_k X[k] cos(2 pi / N (n + 1/2 + N/4)(k + 1/2)), n < N, k < N/2: a DCT-IV of size N/2
-// on an N/4-point complex FFT, unfolded by the DCT-IV's symmetries (computed in double)
-void imdct(const std::vector<float>& X, std::vector<float>& y) {
-    const int M = (int)X.size(), H = M / 2, N = 2 * M;
-    std::vector<std::complex<double>> a((size_t)H);
-    for (int k = 0; k < H; k++) {
-        const double ph = -M_PI * (4.0 * k + 1.0) / (4.0 * M);
-        a[(size_t)k] = std::complex<double>(X[(size_t)(2 * k)], X[(size_t)(M - 1 - 2 * k)]) *
-                       std::complex<double>(std::cos(ph), std::sin(ph));
-    }
-    fft(a);
-    std::vector<double> u((size_t)M);
-    for (int j = 0; j < H; j++) {
-        const double ph = -M_PI * j / (double)M;
-        const std::complex<double> z = a[(size_t)j] * std::complex<double>(std::cos(ph), std::sin(ph));
-        u[(size_t)(2 * j)] = z.real();
-        u[(size_t)(M - 1 - 2 * j)] = -z.imag();
-    }
-    y.assign((size_t)N, 0.0f);
-    for (int n = 0; n < N; n++) {
-        double val;
-        if (n < M / 2)
-            val = u[(size_t)(n + M / 2)];
-        else if (n < 3 * M / 2)
-            val = -u[(size_t)(3 * M / 2 - 1 - n)];
-        else
-            val = -u[(size_t)(n - 3 * M / 2)];
-        y[(size_t)n] = (float)val;
-    }
-}
-
-// the window slope of length len (rising, or falling with right), cached per (len, side)
-const std::vector<float>& vslope(int len, bool right) {
-    static thread_local std::vector<float> cache[2][16];
-    int lg = 0;
-    while ((1 << lg) < len) lg++;
-    std::vector<float>& c = cache[right ? 1 : 0][lg & 15];
-    if ((int)c.size() != len) {
-        c.resize((size_t)len);
-        for (int i = 0; i < len; i++) {
-            const double x = ((double)i + 0.5) / (double)len * M_PI / 2.0 + (right ? M_PI / 2.0 : 0.0);
-            const double s = std::sin(x);
-            c[(size_t)i] = (float)std::sin(M_PI / 2.0 * s * s);
-        }
-    }
-    return c;
+    for (const Mode& md : v.modes) s->modes.push_back(vc::Mode{(uint8_t)md.blockflag, (uint8_t)md.mapping});
 }
 
 }  // namespace
 
-bool sdsp_decode_vorbis(const std::vector<std::vector<uint8_t>>& packets, int64_t last_granule, std::vector<float>* out,
-                        uint32_t* sr, std::string* err) {
+// floor 1 inverse dB table: -140 dB .. 0 dB in steps of 140/256 dB (table[255] = 1)
+const float* sdsp_vorbis_inv_db() {
+    static float tab[256];
+    static std::once_flag once;
+    std::call_once(once, [] {
+        for (int k = 0; k < 256; k++) tab[k] = (float)std::pow(10.0, -(255 - k) * (140.0 / 256.0) / 20.0);
+    });
+    return tab;
+}
+
+// The transcendentals of block size N (M = N/2, H = N/4), each with the expression the decoder has
+// always used: the DCT-IV's pre- and post-twiddles, the FFT's twiddles exp(-2 pi i k / H), and the
+// two slopes of the power-complementary window of length N/2.
+const sdsp_vorbis_tables& sdsp_vorbis_block_tables(int N) {
+    static std::mutex mu;
+    static std::unique_ptr<sdsp_vorbis_tables> cache[32];
+    int lg = 0;
+    while ((1 << lg) < N) lg++;
+    std::lock_guard<std::mutex> lk(mu);
+    std::unique_ptr<sdsp_vorbis_tables>& slot = cache[lg & 31];
+    if (slot) return *slot;
+    slot.reset(new sdsp_vorbis_tables());
+    sdsp_vorbis_tables& t = *slot;
+    t.N = N;
+    const int M = N / 2, H = M / 2;
+    t.pre.resize((size_t)H), t.post.resize((size_t)H), t.tw.resize((size_t)H / 2);
+    for (int k = 0; k < H; k++) {
+        const double ph = -M_PI * (4.0 * k + 1.0) / (4.0 * M);
+        t.pre[(size_t)k] = vc::cd{std::cos(ph), std::sin(ph)};
+    }
+    for (int j = 0; j < H; j++) {
+        const double ph = -M_PI * j / (double)M;
+        t.post[(size_t)j] = vc::cd{std::cos(ph), std::sin(ph)};
+    }
+    const size_t n = (size_t)H;
+    for (size_t k = 0; k < n / 2; k++)
+        t.tw[k] = vc::cd{std::cos(-2.0 * M_PI * (double)k / (double)n), std::sin(-2.0 * M_PI * (double)k / (double)n)};
+    const int len = N / 2;
+    t.up.resize((size_t)len), t.dn.resize((size_t)len);
+    for (int right = 0; right < 2; right++)
+        for (int i = 0; i < len; i++) {
+            const double x = ((double)i + 0.5) / (double)len * M_PI / 2.0 + (right ? M_PI / 2.0 : 0.0);
+            const double s = std::sin(x);
+            (right ? t.dn : t.up)[(size_t)i] = (float)std::sin(M_PI / 2.0 * s * s);
+        }
+    return t;
+}
+
+vorbis_core::Setup sdsp_vorbis_setup::view() const {
+    vc::Setup s{};
+    s.channels = channels, s.bs0 = bs[0], s.bs1 = bs[1], s.nmodes = (int32_t)modes.size();
+    s.books = books.data(), s.trees = trees.data(), s.vq = vq.data(), s.floors = floors.data();
+    s.residues = residues.data(), s.maps = maps.data(), s.modes = modes.data(), s.inv_db = sdsp_vorbis_inv_db();
+    return s;
+}
+
+bool sdsp_vorbis_plan_packets(const std::vector<std::vector<uint8_t>>& packets, int64_t last_granule, sdsp_vorbis_plan* plan,
+                              std::string* err) {
     if (packets.size() < 3) return fail(err, "truncated Vorbis stream");
     Vorbis v;
     {
@@ -655,132 +473,93 @@ bool sdsp_decode_vorbis(const std::vector<std::vector<uint8_t>>& packets, int64_
         LBits b(s.data() + 7, s.size() - 7);
         if (!read_setup(b, v, err)) return false;
     }
-    const int C = v.channels;
-    std::vector<std::vector<float>> chans((size_t)C);
-    std::vector<std::vector<float>> prev((size_t)C);
+    flatten(v, &plan->setup);
+    const vc::Setup sv = plan->setup.view();
+    // the audio packets' first bits: block size, window shape, place in the output
+    size_t kept_bytes = 0;
+    for (size_t pi = 3; pi < packets.size(); pi++) kept_bytes += packets[pi].size();
+    plan->bytes.reserve(kept_bytes + 8);
     int prev_n = 0;
-    std::vector<float> curve, y;
+    uint64_t total = 0;
     for (size_t pi = 3; pi < packets.size(); pi++) {
         const std::vector<uint8_t>& pk = packets[pi];
-        if (pk.empty()) continue;
         LBits b(pk.data(), pk.size());
-        if (b.read(1) != 0) continue;  // not an audio packet
-        const int mode_no = (int)b.read(ilog((uint32_t)(v.modes.size() - 1)));
-        if (b.over || mode_no >= (int)v.modes.size()) continue;
-        const Mode& md = v.modes[(size_t)mode_no];
-        const int n = v.bs[md.blockflag], n2 = n / 2;
-        bool prev_long = false, next_long = false;
-        if (md.blockflag) {
-            prev_long = b.bit();
-            next_long = b.bit();
-        }
-        const Mapping& mp = v.maps[(size_t)md.mapping];
-        // floors
-        std::vector<std::vector<float>> fc((size_t)C, std::vector<float>((size_t)n2, 0.0f));
-        std::vector<char> unused((size_t)C, 0);
-        bool bad = false;
-        for (int c = 0; c < C && !bad; c++) {
-            const int sm = mp.mux[(size_t)c];
-            bool b2 = false;
-            const bool used = floor1_decode(b, v, v.floors[(size_t)mp.sub_floor[(size_t)sm]], n2, fc[(size_t)c], &b2);
-            bad = b2;
-            unused[(size_t)c] = !used;
-        }
-        std::vector<std::vector<float>> res((size_t)C, std::vector<float>((size_t)n2, 0.0f));
-        if (!bad) {
-            std::vector<char> skip(unused);
-            for (size_t s = 0; s < mp.mag.size(); s++)
-                if (!unused[(size_t)mp.mag[s]] || !unused[(size_t)mp.ang[s]]) skip[(size_t)mp.mag[s]] = skip[(size_t)mp.ang[s]] = 0;
-            for (int sm = 0; sm < mp.submaps && !bad; sm++) {
-                std::vector<std::vector<float>*> vecs;
-                std::vector<char> sk;
-                for (int c = 0; c < C; c++)
-                    if (mp.mux[(size_t)c] == sm) vecs.push_back(&res[(size_t)c]), sk.push_back(skip[(size_t)c]);
-                // a packet that ends inside the residue keeps what was decoded (the rest is zero)
-                residue_decode(b, v, v.residues[(size_t)mp.sub_residue[(size_t)sm]], n2, vecs, sk);
-            }
-            // inverse coupling, last step first
-            for (size_t s = mp.mag.size(); s-- > 0;) {
-                std::vector<float>& M = res[(size_t)mp.mag[s]];
-                std::vector<float>& A = res[(size_t)mp.ang[s]];
-                for (int j = 0; j < n2; j++) {
-                    const float m = M[(size_t)j], a = A[(size_t)j];
-                    float nm, na;
-                    if (m > 0.0f) {
-                        if (a > 0.0f)
-                            nm = m, na = m - a;
-                        else
-                            na = m, nm = m + a;
-                    } else {
-                        if (a > 0.0f)
-                            nm = m, na = m + a;
-                        else
-                            na = m, nm = m - a;
-                    }
-                    M[(size_t)j] = nm;
-                    A[(size_t)j] = na;
-                }
-            }
-        }
-        // window of this block
-        int ls, le, ln, rs, re, rn;
-        if (md.blockflag && !prev_long)
-            ls = n / 4 - v.bs[0] / 4, le = n / 4 + v.bs[0] / 4, ln = v.bs[0] / 2;
-        else
-            ls = 0, le = n / 2, ln = n / 2;
-        if (md.blockflag && !next_long)
-            rs = n * 3 / 4 - v.bs[0] / 4, re = n * 3 / 4 + v.bs[0] / 4, rn = v.bs[0] / 2;
-        else
-            rs = n / 2, re = n, rn = n / 2;
-        std::vector<std::vector<float>> cur((size_t)C);
+        int mode_no;
+        bool prev_long, next_long;
+        if (!vc::packet_header(sv, b, pk.size(), &mode_no, &prev_long, &next_long)) continue;
+        const vc::Mode md = plan->setup.modes[(size_t)mode_no];
+        sdsp_vorbis_packet p{};
+        p.off = plan->bytes.size();
+        p.size = (uint32_t)pk.size();
+        p.n = (uint16_t)v.bs[md.blockflag];
+        p.prev_n = (uint16_t)prev_n;
+        p.blockflag = md.blockflag, p.prev_long = prev_long, p.next_long = next_long;
+        p.out = total;
+        if (prev_n) total += (uint64_t)(prev_n / 4 + p.n / 4);
+        prev_n = p.n;
+        plan->bytes.insert(plan->bytes.end(), pk.begin(), pk.end());
+        plan->packets.push_back(p);
+    }
+    plan->total = total;
+    plan->frames = total;
+    if (last_granule >= 0 && (uint64_t)last_granule < total) plan->frames = (uint64_t)last_granule;
+    return true;
+}
+
+int sdsp_vorbis_plan_ogg(const uint8_t* f, size_t n, sdsp_vorbis_plan* plan, std::string* err) {
+    std::vector<std::vector<uint8_t>> packets;
+    int64_t last_granule = -1;
+    sdsp_ogg_demux(f, n, &packets, &last_granule);
+    if (packets.empty()) return fail(err, "no Ogg packets"), -1;
+    const std::vector<uint8_t>& h = packets[0];
+    if (!(h.size() >= 7 && h[0] == 0x01 && std::memcmp(h.data() + 1, "vorbis", 6) == 0)) return 0;
+    return sdsp_vorbis_plan_packets(packets, last_granule, plan, err) ? 1 : -1;
+}
+
+// the packet loop: each kept packet's spectra, the inverse MDCT and window of every channel, the
+// overlap-add with the previous block straight into the mono track
+void sdsp_vorbis_decode_plan(const sdsp_vorbis_plan& plan, std::vector<float>* out) {
+    const vc::Setup sv = plan.setup.view();
+    const int C = sv.channels, nmax = sv.bs1;
+    std::vector<uint32_t> work(vc::work_words(C, nmax / 2));
+    const vc::Work w{work.data(), 1, work.size()};
+    int32_t ybuf[vc::FLOOR_MAX_POINTS];
+    const vc::YStore Y{ybuf, 1};
+    std::vector<float> spec((size_t)C * (size_t)(nmax / 2)), prev((size_t)C * (size_t)nmax), cur((size_t)C * (size_t)nmax);
+    std::vector<vc::cd> a((size_t)nmax / 4);
+    const vc::BlockTables ts = sdsp_vorbis_block_tables(sv.bs0).view();
+    out->clear();
+    out->reserve(plan.total);
+    for (const sdsp_vorbis_packet& p : plan.packets) {
+        int32_t zeroed = 0;
+        vc::decode_packet(sv, plan.bytes.data() + p.off, p.size, w, Y, spec.data(), &zeroed);
+        const int n = p.n, M = n / 2, H = n / 4;
+        int lgH = 0;
+        while ((1 << lgH) < H) lgH++;
+        const vc::BlockTables tb = sdsp_vorbis_block_tables(n).view();
         for (int c = 0; c < C; c++) {
-            std::vector<float> spec((size_t)n2, 0.0f);
-            if (!bad && !unused[(size_t)c])
-                for (int j = 0; j < n2; j++) spec[(size_t)j] = fc[(size_t)c][(size_t)j] * res[(size_t)c][(size_t)j];
-            imdct(spec, y);
-            const std::vector<float>& lw = vslope(ln, false);
-            const std::vector<float>& rw = vslope(rn, true);
-            for (int i = 0; i < n; i++) {
-                float w;
-                if (i < ls || i >= re)
-                    w = 0.0f;
-                else if (i < le)
-                    w = lw[(size_t)(i - ls)];
-                else if (i < rs)
-                    w = 1.0f;
-                else
-                    w = rw[(size_t)(i - rs)];
-                y[(size_t)i] *= w;
-            }
-            cur[(size_t)c] = y;
+            const float* X = spec.data() + (size_t)c * (size_t)M;
+            for (int k = 0; k < H; k++) vc::imdct_pre(X, M, lgH, k, tb.pre, a.data());
+            for (int len = 2; len <= H; len <<= 1)
+                for (int t = 0; t < H / 2; t++) vc::fft_butterfly(a.data(), H, len, t, tb.tw);
+            float* y = cur.data() + (size_t)c * (size_t)n;
+            for (int i = 0; i < n; i++)
+                y[i] = vc::imdct_out(a.data(), M, i, tb.post) * vc::window_at(n, sv.bs0, p.blockflag, p.prev_long, p.next_long, i, tb, ts);
         }
-        // overlap-add: the samples from the previous window's centre to this one's
-        if (prev_n) {
-            const int L = prev_n / 4 + n / 4;
-            for (int c = 0; c < C; c++) {
-                for (int i = 0; i < L; i++) {
-                    const int pi2 = prev_n / 2 + i, ci = i - L + n / 2;
-                    const float pv = pi2 < prev_n ? prev[(size_t)c][(size_t)pi2] : 0.0f;
-                    const float cv = ci >= 0 ? cur[(size_t)c][(size_t)ci] : 0.0f;
-                    chans[(size_t)c].push_back(pv + cv);
-                }
-            }
+        if (p.prev_n) {
+            const int L = p.prev_n / 4 + n / 4;
+            for (int i = 0; i < L; i++) out->push_back(vc::ola_mix(prev.data(), p.prev_n, cur.data(), n, C, i));
         }
-        prev = std::move(cur);
-        prev_n = n;
+        prev.swap(cur);
     }
-    size_t frames = chans[0].size();
-    if (last_granule >= 0 && (uint64_t)last_granule < frames) frames = (size_t)last_granule;
-    out->resize(frames);
-    for (size_t i = 0; i < frames; i++) {
-        if (C == 1) {
-            (*out)[i] = chans[0][i];
-        } else {
-            float s = -0.0f;
-            for (int c = 0; c < C; c++) s = s + chans[(size_t)c][i];
-            (*out)[i] = s / (float)C;
-        }
-    }
-    *sr = v.rate;
+    out->resize(plan.frames);
+}
+
+bool sdsp_decode_vorbis(const std::vector<std::vector<uint8_t>>& packets, int64_t last_granule, std::vector<float>* out,
+                        uint32_t* sr, std::string* err) {
+    sdsp_vorbis_plan plan;
+    if (!sdsp_vorbis_plan_packets(packets, last_granule, &plan, err)) return false;
+    sdsp_vorbis_decode_plan(plan, out);
+    *sr = plan.setup.rate;
     return true;
 }

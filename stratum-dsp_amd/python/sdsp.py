@@ -14,8 +14,8 @@ import subprocess
 
 import numpy as np
 
-from sdsp_abi import (ERROR_NAMES, FLAG_NAMES, SdspConfidence, SdspConfig, SdspDecodeStats, SdspFlacDecodeStats, SdspResult,
-                      SdspStageTimes, result_to_dict)
+from sdsp_abi import (ERROR_NAMES, FLAG_NAMES, SdspAudioDecodeStats, SdspConfidence, SdspConfig, SdspDecodeStats,
+                      SdspFlacDecodeStats, SdspResult, SdspStageTimes, result_to_dict)
 
 PKG = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LIB_PATH = os.environ.get("SDSP_LIB_PATH") or os.path.join(PKG, "lib", "libstratum_hip.so")  # override: layout/ablation builds
@@ -106,7 +106,11 @@ def _load(path):
         L.sdsp_decode_batch_device.restype = C.c_int32
         L.sdsp_last_decode_stats.argtypes = [C.c_int32, C.POINTER(SdspDecodeStats)]
         L.sdsp_last_decode_stats.restype = C.c_int32
-        for f in ("sdsp_debug_alac_decode_phased", "sdsp_debug_pcm_decode_planned"):
+        L.sdsp_decode_audio_batch_device.argtypes = L.sdsp_decode_flac_batch_device.argtypes
+        L.sdsp_decode_audio_batch_device.restype = C.c_int32
+        L.sdsp_last_audio_decode_stats.argtypes = [C.c_int32, C.POINTER(SdspAudioDecodeStats)]
+        L.sdsp_last_audio_decode_stats.restype = C.c_int32
+        for f in ("sdsp_debug_alac_decode_phased", "sdsp_debug_pcm_decode_planned", "sdsp_debug_vorbis_decode_phased"):
             getattr(L, f).argtypes = L.sdsp_debug_flac_decode_phased.argtypes
             getattr(L, f).restype = C.c_int32
         L.sdsp_free_samples.restype = None
@@ -383,6 +387,20 @@ def decode_batch_device(blobs, device=0, stream=None):
     return _decode_batch(lib().sdsp_decode_batch_device, decode_stats, "device decode", blobs, device, stream)
 
 
+def audio_decode_stats(device=0):
+    """sdsp_last_audio_decode_stats: counters and phase times of the last sdsp_decode_audio_batch_device call on `device`."""
+    t = SdspAudioDecodeStats()
+    if lib().sdsp_last_audio_decode_stats(device, C.byref(t)) != 0:
+        raise RuntimeError("sdsp_last_audio_decode_stats failed")
+    return {k: getattr(t, k) for k, _ in SdspAudioDecodeStats._fields_}
+
+
+def decode_audio_batch_device(blobs, device=0, stream=None):
+    """sdsp_decode_audio_batch_device: decode_batch_device with Ogg Vorbis decoded on the device too.
+    Returns the same tuple, with the audio_decode_stats dict."""
+    return _decode_batch(lib().sdsp_decode_audio_batch_device, audio_decode_stats, "device decode", blobs, device, stream)
+
+
 def debug_flac_decode_phased(data):
     """sdsp_debug_flac_decode_phased: the device decoder's four phases on the CPU.  Returns (mono
     float32 array, sample_rate, (candidates, accepted, rejected)); raises AnalysisError as
@@ -426,6 +444,13 @@ def debug_alac_decode_phased(data):
     float32 array, sample_rate, (packets, decoded, skipped)); raises AnalysisError as decode_audio_file
     does, or AnalysisError(NotImplemented, "... not planned ...") for bytes that are no ALAC container."""
     return _debug_decode(lib().sdsp_debug_alac_decode_phased, data, 3)
+
+
+def debug_vorbis_decode_phased(data):
+    """sdsp_debug_vorbis_decode_phased: the device Vorbis decoder's phases on the CPU.  Returns (mono
+    float32 array, sample_rate, (packets, zeroed)); raises AnalysisError as decode_audio_file does, or
+    AnalysisError(NotImplemented, "... not planned ...") for bytes that are no Ogg Vorbis stream."""
+    return _debug_decode(lib().sdsp_debug_vorbis_decode_phased, data, 2)
 
 
 def debug_pcm_decode_planned(data):

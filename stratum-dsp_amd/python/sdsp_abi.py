@@ -252,6 +252,35 @@ class SdspDecodeStats(C.Structure):
     ]
 
 
+class SdspAudioDecodeStats(C.Structure):
+    """sdsp_audio_decode_stats: counters and phase times of the last sdsp_decode_audio_batch_device call."""
+
+    _fields_ = [
+        ("files", u64),
+        ("device_files", u64),
+        ("host_fallback_files", u64),
+        ("error_files", u64),
+        ("flac_files", u64),
+        ("alac_files", u64),
+        ("pcm_files", u64),
+        ("vorbis_files", u64),
+        ("alac_packets", u64),
+        ("alac_packets_decoded", u64),
+        ("alac_packets_skipped", u64),
+        ("vorbis_packets", u64),
+        ("vorbis_packets_zeroed", u64),
+        ("bytes_in", u64),
+        ("samples_out", u64),
+        ("upload_ms", C.c_double),
+        ("flac_ms", C.c_double),
+        ("alac_ms", C.c_double),
+        ("pcm_ms", C.c_double),
+        ("gather_ms", C.c_double),
+        ("vorbis_ms", C.c_double),
+        ("total_ms", C.c_double),
+    ]
+
+
 class SdspConfidence(C.Structure):
     _fields_ = [
         ("bpm_confidence", f32),
