@@ -290,6 +290,72 @@ int32_t sdsp_analyze_batch_device_ex(const float* d_samples, const uint64_t* off
 void sdsp_result_free(sdsp_result* r);
 
 /*
+ * Overview envelopes (new; the reference has none): per track a compact amplitude and band summary
+ * in C columns, computed inside the analysis call from what it already holds on the device (the
+ * gain and trim bounds, the samples, the base tempo pass's magnitude spectrogram), so a caller whose
+ * audio exists only in HBM (sdsp_decode_audio_batch_device) neither downloads nor decodes it again.
+ *
+ * Per track, with n the trimmed length, first_sample the trim start in the caller's track,
+ *   x[i] = raw[first_sample + i] * gain   (one f32 multiply: the normalised, trimmed signal as the
+ *                                          reference stores it, whatever the normalisation method,
+ *                                          and with normalisation or trimming switched off)
+ *   frame_size, hop = the configuration's frame_size and hop_size, B = frame_size / 2 + 1
+ *   F = n < frame_size ? 0 : (n - frame_size) / hop + 1
+ *   M[t][k] = the magnitudes of the hop_size STFT of x (the base tempo pass's rows)
+ * the request selects the columns by exactly one of
+ *   columns > 0            C = min(columns, F),               f0(c) = floor(c * F / C)
+ *   frames_per_column > 0  C = ceil(F / frames_per_column),   f0(c) = min(c * frames_per_column, F)
+ * (u64 arithmetic; f0(C) = F), the bands by
+ *   b1 = min(B, floor((double)low_max_hz * frame_size / sample_rate))
+ *   b2 = min(B, max(b1, floor((double)mid_max_hz * frame_size / sample_rate)))
+ *   low = bins [0, b1), mid = [b1, b2), high = [b2, B)
+ * and column c holds
+ *   smin[c], smax[c]   the minimum and maximum of x[i] over i in [f0(c) * hop, s1), with
+ *                      s1 = f0(c + 1) * hop for c + 1 < C and s1 = n for the last column (which
+ *                      takes the samples after the last hop); where both zeros occur, -0 < +0
+ *   low[c], mid[c], high[c]   the maximum of M[t][k] over t in [f0(c), f0(c + 1)) and k in the
+ *                      band; 0.0f for an empty band
+ * Every value is a minimum or maximum, so it is exact: equal, bit for bit, to the same reduction
+ * over the reference's normalised signal and spectrogram.  Non-finite input samples are out of
+ * scope: the overview of a track that holds a NaN or an infinity is unspecified.
+ *
+ * F = 0 (a track shorter than one frame) gives zero columns and leaves the status alone.  A track
+ * whose analysis status is not SDSP_OK gets that status, zero columns, and zero n_frames,
+ * first_sample and n_samples.  frame_size, hop_size and band_bins are filled for every track.
+ */
+typedef struct sdsp_overview_request {
+    uint32_t columns;
+    uint32_t frames_per_column;
+    float low_max_hz, mid_max_hz;
+} sdsp_overview_request;
+
+typedef struct sdsp_overview {
+    uint64_t n_columns, n_frames;     /* C, F */
+    uint64_t first_sample, n_samples; /* the trim start in the caller's track, n */
+    uint32_t frame_size, hop_size;
+    uint32_t band_bins[2];            /* b1, b2 */
+    float *smin, *smax, *low, *mid, *high; /* library-owned, n_columns each (NULL for none) */
+    int32_t status;                   /* the track's sdsp_status */
+} sdsp_overview;
+
+/*
+ * sdsp_analyze_batch_device_ex, and for each track its overview in overviews[i] (n_tracks entries,
+ * freed one by one with sdsp_overview_free).  With SDSP_STAGES_FULL and SDSP_STAGES_BPM_ONLY alike:
+ * both run the base tempo pass.  req == NULL is sdsp_analyze_batch_device_ex itself (the same
+ * launches, the same results; overviews is not touched and may be NULL).  A request with both
+ * counts zero or both non-zero, or with a band edge that is not finite, is negative, or
+ * low_max_hz > mid_max_hz, fails the call with SDSP_ERR_INVALID_INPUT before any device is touched:
+ * every outs[i] carries the status and the reason, every overview is zeroed.
+ */
+int32_t sdsp_analyze_batch_device_overview(const float* d_samples, const uint64_t* offsets,
+                                           const uint64_t* lens, uint64_t n_tracks, uint32_t sample_rate,
+                                           const sdsp_config* cfg, int32_t device, void* stream,
+                                           int32_t stages, sdsp_result* outs,
+                                           const sdsp_overview_request* req, sdsp_overview* overviews);
+/* Frees the arrays owned by one overview (never free() them one by one: they share one allocation). */
+void sdsp_overview_free(sdsp_overview* o);
+
+/*
  * Synthetic track generator on device: writes n_tracks tracks of `len`
  * samples each, track i at d_out + i*len, seeds seed0 + i.  bpm_out/key_out (host, may be
  * NULL) receive the generated tempo and key (key = mode*12 + tonic).  bpm_mode 0 = uniform

@@ -100,6 +100,20 @@ int32_t sdsp_debug_frame_rms(const float* host_x, uint64_t n_total, const uint64
 int32_t sdsp_debug_last_tail_reruns(int32_t device, uint64_t* n_tracks);
 
 /*
+ * The overview kernels of the last sdsp_analyze_batch_device_overview call with a request on
+ * `device`, summed over its sub-batches: HIP event times of the sample-envelope kernel
+ * (k_ov_segments) and of the band-envelope kernels (k_ov_columns, and k_ov_fold where a column is
+ * cut into pieces), the bytes each reads by the definition (4 n per track; 4 F (frame_size / 2 + 1)
+ * per track), and the columns produced.  All zero after a call without a request.
+ */
+typedef struct sdsp_debug_overview_times {
+    double sample_ms, band_ms;
+    double sample_bytes, band_bytes;
+    uint64_t columns, sub_batches;
+} sdsp_debug_overview_times;
+int32_t sdsp_debug_last_overview_times(int32_t device, sdsp_debug_overview_times* out);
+
+/*
  * Stage probe of the tempo path: the pipeline's own tempo pass (features, novelty, both tempograms;
  * the same parameter set-up and launches as an analysis call) over host magnitude spectrograms
  * instead of an STFT.  host_mags holds the tracks' rows back to back, frame_size / 2 + 1 values per

@@ -14,7 +14,15 @@
 // and host memory holds the files' bytes only.  Chunks go round-robin over the devices of
 // --devices, one host thread per device.
 //
-//   analyze_batch [--jobs N] [--devices MASK] [--json] [--gpu-decode] <file1> <file2> ...
+// --overview N / --overview-frames K (opt-in; JSONL only): each line's object gets one more member
+// at its end, "overview": the track's overview envelope (include/stratum_hip.h, sdsp_overview) in N
+// columns, or one column per K frames, with the low / mid / high bands split at 250 Hz and 4 kHz.
+// The analysis then runs through sdsp_analyze_batch_device_overview: from the decoder's device
+// buffer with --gpu-decode, otherwise from the decoded tracks uploaded to the first device of
+// --devices, one call per sample rate and at most 512 tracks or 8 GB.
+//
+//   analyze_batch [--jobs N] [--devices MASK] [--json] [--gpu-decode] [--overview N | --overview-frames K]
+//                 <file1> <file2> ...
 #include <algorithm>
 #include <atomic>
 #include <chrono>
@@ -40,7 +48,34 @@ struct Item {
     float bpm = 0, bpm_conf = 0, key_conf = 0, ms = 0;
     std::string key;
     int8_t tr[4] = {-1, -1, -1, -1};
+    std::string overview;  // --overview: the "overview" member's value
 };
+
+// floats so that an f32 round-trips
+void json_floats(std::string& s, const char* name, const float* v, uint64_t n) {
+    s += std::string(",\"") + name + "\":[";
+    char b[32];
+    for (uint64_t i = 0; i < n; i++) {
+        std::snprintf(b, sizeof b, i ? ",%.9g" : "%.9g", (double)v[i]);
+        s += b;
+    }
+    s += "]";
+}
+std::string overview_json(const sdsp_overview& o) {
+    char b[320];
+    std::snprintf(b, sizeof b,
+                  "{\"n_columns\":%llu,\"n_frames\":%llu,\"first_sample\":%llu,\"n_samples\":%llu,\"frame_size\":%u,"
+                  "\"hop_size\":%u,\"band_bins\":[%u,%u],\"status\":%d",
+                  (unsigned long long)o.n_columns, (unsigned long long)o.n_frames, (unsigned long long)o.first_sample,
+                  (unsigned long long)o.n_samples, o.frame_size, o.hop_size, o.band_bins[0], o.band_bins[1], o.status);
+    std::string s = b;
+    json_floats(s, "smin", o.smin, o.n_columns);
+    json_floats(s, "smax", o.smax, o.n_columns);
+    json_floats(s, "low", o.low, o.n_columns);
+    json_floats(s, "mid", o.mid, o.n_columns);
+    json_floats(s, "high", o.high, o.n_columns);
+    return s + "}";
+}
 
 // percentile as the example computes it: sort, index round((len-1) * p)
 float percentile(std::vector<float> xs, float p) {
@@ -117,6 +152,8 @@ int main(int argc, char** argv) {
     bool json = false, gpu_decode = false;
     uint64_t jobs = 0;
     uint32_t devices = 0;
+    sdsp_overview_request ovreq{0, 0, 250.0f, 4000.0f};
+    bool overview = false;
     std::vector<std::string> paths;
     for (size_t i = 0; i < a.size(); i++) {
         const std::string& s = a[i];
@@ -135,18 +172,35 @@ int main(int argc, char** argv) {
             else
                 devices = (uint32_t)v;
             i++;
+        } else if (s == "--overview" || s == "--overview-frames") {
+            uint64_t v;
+            if (i + 1 >= a.size() || !parse_usize_str(a[i + 1], &v) || v == 0 || v > 0xFFFFFFFFull) {
+                std::fprintf(stderr, "Error: %s requires a count of at least 1\n", s.c_str());
+                return 1;
+            }
+            (s == "--overview" ? ovreq.columns : ovreq.frames_per_column) = (uint32_t)v;
+            overview = true;
+            i++;
         } else if (s == "--help" || s == "-h") {
             std::fprintf(stderr,
-                         "Usage: analyze_batch [--jobs N] [--devices MASK] [--json] [--gpu-decode] <file1> <file2> ...\n\n"
+                         "Usage: analyze_batch [--jobs N] [--devices MASK] [--json] [--gpu-decode] [--overview N | "
+                         "--overview-frames K] <file1> <file2> ...\n\n"
                          "--jobs N        Decode workers (default: CPU-1)\n"
                          "--devices MASK  GPU bitmask (default: all visible GPUs)\n"
                          "--json          Emit one JSON object per line (JSONL)\n"
-                         "--gpu-decode    Decode on the GPUs: FLAC, ALAC (M4A / CAF), WAV, AIFF and Ogg Vorbis by kernels (same output)\n");
+                         "--gpu-decode    Decode on the GPUs: FLAC, ALAC (M4A / CAF), WAV, AIFF and Ogg Vorbis by kernels (same output)\n"
+                         "--overview N    With --json: add each track's overview envelope in N columns (\"overview\")\n"
+                         "--overview-frames K  ... or in one column per K analysis frames\n");
             return 0;
         } else {
             paths.push_back(s);
         }
     }
+    if (ovreq.columns && ovreq.frames_per_column) {
+        std::fprintf(stderr, "Error: --overview and --overview-frames exclude each other\n");
+        return 1;
+    }
+    if (overview && !json) std::fprintf(stderr, "Note: --overview / --overview-frames add to the --json lines only\n");
     if (paths.empty()) {
         std::fprintf(stderr, "ERROR: Provide at least one audio file path. Use --help for usage.\n");
         return 2;
@@ -200,7 +254,8 @@ int main(int argc, char** argv) {
 
     sdsp_config cfg;
     sdsp_config_default(&cfg);
-    auto take = [](Item& it, const sdsp_result& r) {
+    auto take = [](Item& it, const sdsp_result& r, const sdsp_overview* ov = nullptr) {
+        if (ov) it.overview = overview_json(*ov);
         if (r.status != 0) {
             it.error = std::string("analysis failed: ") + r.error_message;
             return;
@@ -270,11 +325,14 @@ int main(int argc, char** argv) {
                     l2.push_back(lens[k]);
                 }
                 std::vector<sdsp_result> outs(okk.size());
-                (void)sdsp_analyze_batch_device(d_samples, o2.data(), l2.data(), okk.size(), kv.first, &cfg, dev, nullptr,
-                                                outs.data());
+                std::vector<sdsp_overview> ovs(overview ? okk.size() : 0);  // (zeroed; without a request: the plain entry)
+                (void)sdsp_analyze_batch_device_overview(d_samples, o2.data(), l2.data(), okk.size(), kv.first, &cfg, dev,
+                                                         nullptr, SDSP_STAGES_FULL, outs.data(), overview ? &ovreq : nullptr,
+                                                         overview ? ovs.data() : nullptr);
                 for (size_t j = 0; j < okk.size(); j++) {
-                    take(items[ch.idx[okk[j]]], outs[j]);
+                    take(items[ch.idx[okk[j]]], outs[j], overview ? &ovs[j] : nullptr);
                     sdsp_result_free(&outs[j]);
+                    if (overview) sdsp_overview_free(&ovs[j]);
                 }
             }
             if (d_samples) sdsp_device_free(dev, d_samples);
@@ -298,6 +356,44 @@ int main(int argc, char** argv) {
             ptrs.push_back(items[i].samples.data());
             lens.push_back(items[i].samples.size());
         }
+        if (overview) {
+            // the overview entry reads device-resident tracks: upload each group to the first device of
+            // the mask in parts of at most 512 tracks or 2 Gi samples
+            int dev = 0;
+            while (dev < 31 && !(devices & (1u << dev))) dev++;
+            for (size_t k0 = 0; k0 < idx.size();) {
+                size_t k1 = k0;
+                uint64_t tot = 0;
+                while (k1 < idx.size() && k1 - k0 < 512 && (k1 == k0 || tot + lens[k1] <= ((uint64_t)2 << 30))) tot += lens[k1++];
+                const size_t n = k1 - k0;
+                std::vector<uint64_t> off(n);
+                std::vector<sdsp_result> outs(n);
+                std::vector<sdsp_overview> ovs(n);
+                void* d = nullptr;
+                bool up = sdsp_device_malloc(dev, std::max<uint64_t>(tot, 1) * sizeof(float), &d) == 0;
+                uint64_t o = 0;
+                for (size_t k = k0; k < k1 && up; k++) {
+                    off[k - k0] = o;
+                    if (lens[k]) up = sdsp_memcpy_h2d(dev, (float*)d + o, ptrs[k], lens[k] * sizeof(float)) == 0;
+                    o += lens[k];
+                }
+                if (up)
+                    (void)sdsp_analyze_batch_device_overview((const float*)d, off.data(), lens.data() + k0, n, kv.first, &cfg, dev,
+                                                             nullptr, SDSP_STAGES_FULL, outs.data(), &ovreq, ovs.data());
+                for (size_t k = k0; k < k1; k++) {
+                    if (up) {
+                        take(items[idx[k]], outs[k - k0], &ovs[k - k0]);
+                        sdsp_result_free(&outs[k - k0]);
+                        sdsp_overview_free(&ovs[k - k0]);
+                    } else {
+                        items[idx[k]].error = "analysis failed: Processing error: device upload failed";
+                    }
+                }
+                if (d) sdsp_device_free(dev, d);
+                k0 = k1;
+            }
+            continue;
+        }
         std::vector<sdsp_result> outs(idx.size());
         // a non-OK return means some chunk failed; every track's own status says which (tracks the
         // library did not analyse carry an error status), so each result is read and freed
@@ -315,12 +411,17 @@ int main(int argc, char** argv) {
                 std::printf("{\"file\":%s,\"bpm\":%.2f,\"bpm_confidence\":%.4f,\"key\":%s,\"key_confidence\":%.4f,"
                             "\"processing_time_ms\":%.2f,\"tempogram_multi_res_triggered\":%s,"
                             "\"tempogram_multi_res_used\":%s,\"tempogram_percussive_triggered\":%s,"
-                            "\"tempogram_percussive_used\":%s}\n",
+                            "\"tempogram_percussive_used\":%s",
                             json_str(o.path).c_str(), (double)o.bpm, (double)o.bpm_conf, json_str(o.key).c_str(),
                             (double)o.key_conf, (double)o.ms, tri(o.tr[0]), tri(o.tr[1]), tri(o.tr[2]), tri(o.tr[3]));
             else
-                std::printf("{\"file\":%s,\"error\":%s}\n", json_str(o.path).c_str(),
+                std::printf("{\"file\":%s,\"error\":%s", json_str(o.path).c_str(),
                             json_str(o.error.empty() ? "unknown error" : o.error).c_str());
+            if (!o.overview.empty()) {
+                std::fputs(",\"overview\":", stdout);
+                std::fputs(o.overview.c_str(), stdout);
+            }
+            std::fputs("}\n", stdout);
         } else {
             if (o.ok)
                 std::printf("[%zu/%zu] %s: BPM=%.2f (conf=%.3f) Key=%s (conf=%.3f) time=%.2fms\n", i + 1, items.size(),

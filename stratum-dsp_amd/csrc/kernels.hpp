@@ -380,4 +380,23 @@ void launch_synth(float* out, uint64_t n_tracks, uint64_t len, uint32_t sr, cons
                   uint64_t seed0, hipStream_t st);
 void launch_synth_normalize(float* out, uint64_t n_tracks, uint64_t len, unsigned int* peak_bits, hipStream_t st);
 
+// ---- k_overview ----
+constexpr int OV_PIECE = 64;  // frames per k_ov_columns unit at most (one segment per lane)
+struct OvParams {
+    int B, stride;    // bins per row and row stride of the base pass's spectrogram
+    uint32_t b1, b2;  // low [0, b1), mid [b1, b2), high [b2, B)
+    uint32_t columns, frames_per_column;  // the request's form (overview_plan.hpp)
+};
+// per hop segment (row g of the frame prefix) the keys of min and max of raw * gain
+void launch_overview_segments(const float* x, const uint64_t* src_off, const float* gain, const uint64_t* n_len,
+                              const uint64_t* frame_pfx, int T, uint64_t total, int hop, uint32_t* seg_lo,
+                              uint32_t* seg_hi, hipStream_t st);
+// out: 5 x n_cols, track i's smin, smax, low, mid, high back to back at 5 col_pfx[i], C_i each;
+// unit_pfx counts columns x pieces per track (ov_pieces with OV_PIECE); part: 5 x n_units, used
+// when `pieces`
+void launch_overview_columns(const float* mags, const uint64_t* frame_pfx, const uint64_t* col_pfx,
+                             const uint64_t* unit_pfx, int T, uint64_t n_units, uint64_t n_cols, bool pieces,
+                             const uint32_t* seg_lo, const uint32_t* seg_hi, const OvParams& P, float* out,
+                             uint32_t* part, hipStream_t st);
+
 }  // namespace sdsp

@@ -20,6 +20,7 @@
 // pipeline_params.hip maps the configuration to launch parameters, pipeline_debug.hip has the
 // debug_track_id dumps and the stage probes, pipeline_abi.hip the C ABI entry points.
 // No stage falls back to the CPU; host code only plans offsets and formats the result.
+#include "overview_plan.hpp"
 #include "pipeline.hpp"
 
 namespace sdsp {
@@ -61,6 +62,7 @@ void Pipeline::run(const float* d_samples, const std::vector<uint64_t>& in_off, 
                    std::vector<TrackRes>& res) {
     const size_t T = n_raw.size();
     res.assign(T, TrackRes{});
+    if (ov_out_) ov_out_->assign(T, TrackOv{});
     const std::string why = check_supported(cfg_, sr_);
     for (size_t i = 0; i < T; i++) {
         if (n_raw[i] == 0) {
@@ -211,6 +213,7 @@ void Pipeline::sub_batch(const float* d_samples, const std::vector<uint64_t>& in
     tempo_pass("B.", bin, bo);
     add_pass_times(bo);
     tm.mark(2);
+    const Overview ov = overview(d_samples, bin, bo, tm);  // (nothing without a request)
     const std::vector<TempoEst> best = c_.down(bo.est, (size_t)NR);
     const Hpss hp = hpss(bo, best, htr);
     const Onsets on = onsets(d_samples, f, bin, bo, hp);
@@ -234,6 +237,7 @@ void Pipeline::sub_batch(const float* d_samples, const std::vector<uint64_t>& in
             r.bpm = tp.fbpm_h[(size_t)i];
             r.bpm_conf = tp.fconf_h[(size_t)i];
         }
+        overview_results(ov, f, bin, bo, tm);
         htr("results (bpm only)");
         return;
     }
@@ -242,6 +246,7 @@ void Pipeline::sub_batch(const float* d_samples, const std::vector<uint64_t>& in
     tm.mark(5);
     std::vector<KeyOut> kout = join_key(d_samples, in_off, n_raw, f, kl, htr, res);  // empty: joined one sub-batch late
     const ResultsHost rh = download_results(bt, bin, bo);
+    overview_results(ov, f, bin, bo, tm);
     htr("D down");
     if (cfg_.enable_key_beat_synchronous && !cfg_.enable_key_log_frequency && !kl.K.empty()) {
         beat_sync_revote(kl, rh, kout);
@@ -530,6 +535,89 @@ ResultsHost Pipeline::download_results(const Beats& bt, const TempoPassIn& bin, 
     rh.downs_h = c_.down(d_cdowns, rh.bpfx[2 * NR + 1]);
     if (cfg_.emit_tempogram_candidates) rh.cand_h = c_.down(bo.cand, NR * (size_t)bin.cand_cap * 4);
     return rh;
+}
+
+// The overview envelopes (include/stratum_hip.h, sdsp_overview) of the surviving tracks, queued on
+// the main stream behind the base pass: the sample extrema per hop segment from the samples, then
+// per column those and the band maxima from the pass's rows (k_overview.hip).  The column plan is
+// overview_plan.hpp's; the kernels compute a column's frames from the same functions.
+Overview Pipeline::overview(const float* d_samples, const TempoPassIn& bin, const TempoPassOut& bo, Timers& tm) {
+    Overview ov;
+    if (!ov_out_) return ov;
+    ov.on = true;
+    const int NR = (int)bin.n_trim.size();
+    OvParams P{};
+    P.B = nb_;
+    P.stride = s2_;
+    P.columns = ov_req_.columns;
+    P.frames_per_column = ov_req_.frames_per_column;
+    ov_band_bins(ov_req_.low_max_hz, ov_req_.mid_max_hz, (uint64_t)fs_, sr_, &P.b1, &P.b2);
+    std::vector<uint64_t> upfx((size_t)NR + 1, 0);
+    ov.cpfx.assign((size_t)NR + 1, 0);
+    bool pieces = false;
+    for (int i = 0; i < NR; i++) {
+        const uint64_t F = bo.fpfx[(size_t)i + 1] - bo.fpfx[(size_t)i];
+        const uint64_t C = ov_columns(F, P.columns, P.frames_per_column);
+        const uint64_t np = ov_pieces(F, C, P.columns, P.frames_per_column, OV_PIECE);
+        pieces = pieces || np > 1;
+        ov.cpfx[(size_t)i + 1] = ov.cpfx[(size_t)i] + C;
+        upfx[(size_t)i + 1] = upfx[(size_t)i] + C * np;
+        ov.seg_bytes += 4.0 * (double)bin.n_trim[(size_t)i];
+        ov.col_bytes += 4.0 * (double)F * (double)nb_;
+    }
+    const uint64_t n_cols = ov.n_cols = ov.cpfx[(size_t)NR], n_units = upfx[(size_t)NR];
+    if (n_units / 4 >= 0x7FFFFFFFull) throw HipError("overview: too many columns for one launch");
+    if (n_cols == 0) return ov;  // no track has a frame
+    uint64_t* d_src = c_.up("O.src", bin.src_off);
+    float* d_gain = c_.up("O.gain", bin.gain_h);
+    uint64_t* d_n = c_.up("O.n", bin.n_trim);
+    uint64_t* d_cpfx = c_.up("O.cpfx", ov.cpfx);
+    uint64_t* d_upfx = c_.up("O.upfx", upfx);
+    uint32_t* d_lo = c_.dev<uint32_t>("O.seglo", bo.total);
+    uint32_t* d_hi = c_.dev<uint32_t>("O.seghi", bo.total);
+    ov.d_out = c_.dev<float>("O.out", 5 * n_cols);
+    uint32_t* d_part = c_.dev<uint32_t>("O.part", pieces ? 5 * n_units : 1);
+    tm.mark(6);
+    launch_overview_segments(d_samples, d_src, d_gain, d_n, bo.d_fpfx, NR, bo.total, bin.hop, d_lo, d_hi, d_.stream);
+    tm.mark(7);
+    launch_overview_columns(bo.mags, bo.d_fpfx, d_cpfx, d_upfx, NR, n_units, n_cols, pieces, d_lo, d_hi, P, ov.d_out,
+                            d_part, d_.stream);
+    tm.mark(8);
+    SDSP_HIP_CHECK(hipGetLastError());
+    return ov;
+}
+
+// The sub-batch's overviews read back with its results, into the call's per-track entries.
+void Pipeline::overview_results(const Overview& ov, const Front& f, const TempoPassIn& bin, const TempoPassOut& bo,
+                                Timers& tm) {
+    if (!ov.on) return;
+    const size_t NR = f.R.size();
+    // one download (not value-initialised: at one frame per column it is as long as the samples / 100)
+    std::shared_ptr<float[]> h;
+    if (ov.n_cols) {
+        h.reset(new float[5 * (size_t)ov.n_cols]);
+        SDSP_HIP_CHECK(hipMemcpyAsync(h.get(), ov.d_out, 5 * (size_t)ov.n_cols * sizeof(float), hipMemcpyDeviceToHost,
+                                      d_.stream));
+    }
+    c_.sync();
+    for (size_t i = 0; i < NR; i++) {
+        TrackOv& o = (*ov_out_)[f.slot[i]];
+        o.F = bo.fpfx[i + 1] - bo.fpfx[i];
+        o.C = ov.cpfx[i + 1] - ov.cpfx[i];
+        o.first = f.ts[(size_t)f.R[i]];
+        o.n = bin.n_trim[i];
+        o.blk = h;
+        o.at = 5 * (size_t)ov.cpfx[i];
+    }
+    sdsp_debug_overview_times& t = d_.last_ov;
+    if (ov.n_cols) {
+        t.sample_ms += tm.ms(6, 7);
+        t.band_ms += tm.ms(7, 8);
+    }
+    t.sample_bytes += ov.seg_bytes;
+    t.band_bytes += ov.col_bytes;
+    t.columns += ov.n_cols;
+    t.sub_batches++;
 }
 
 // Tempo, beat lists and candidate lists into the surviving tracks' results.

@@ -373,6 +373,22 @@ struct ResultsHost {
     std::vector<float> beats_h, downs_h, cand_h;
     float* d_cbeats = nullptr;
 };
+// The overview envelopes of the surviving tracks as queued after the base pass (Pipeline::overview);
+// nothing is queued without a request.
+struct Overview {
+    bool on = false;
+    std::vector<uint64_t> cpfx{0};  // column prefix over the surviving tracks
+    uint64_t n_cols = 0;
+    float* d_out = nullptr;  // track i's smin, smax, low, mid, high back to back at 5 cpfx[i]
+    double seg_bytes = 0, col_bytes = 0;  // algorithmic bytes of the two kernels
+};
+// One track's overview on the host (sdsp_overview without the config-wide fields): its five arrays
+// (smin, smax, low, mid, high, C each) back to back at blk + at, in its sub-batch's download.
+struct TrackOv {
+    uint64_t C = 0, F = 0, first = 0, n = 0;
+    std::shared_ptr<float[]> blk;
+    size_t at = 0;
+};
 
 }  // namespace detail
 using namespace detail;
@@ -391,6 +407,12 @@ class Pipeline {
 
     void run(const float* d_samples, const std::vector<uint64_t>& in_off, const std::vector<uint64_t>& n_raw,
              std::vector<TrackRes>& res);
+    // Before run(): also compute every track's overview envelope (include/stratum_hip.h) into
+    // *out, one entry per track of the call.  A pipeline without a request queues nothing for it.
+    void set_overview(const sdsp_overview_request& req, std::vector<TrackOv>* out) {
+        ov_req_ = req;
+        ov_out_ = out;
+    }
 
    private:
     Ctx c_;
@@ -425,6 +447,8 @@ class Pipeline {
     std::unique_ptr<KeyPending> key_pending_;
     std::unique_ptr<KeyPending> tail_;  // the last sub-batch's pending join, kept for rerun_tail
     int sb_parity_ = 0;
+    sdsp_overview_request ov_req_{};
+    std::vector<TrackOv>* ov_out_ = nullptr;  // the call's overviews (set_overview), else nullptr
 
     // force_legacy_bpm skips the tempogram estimate (src/lib.rs:337): no escalation, no
     // candidates, the flags stay None; the hop-512 pass still feeds the onset detectors
@@ -447,6 +471,8 @@ class Pipeline {
     Onsets onsets(const float* d_samples, const Front& f, const TempoPassIn& bin, const TempoPassOut& bo, const Hpss& hp);
     Beats beat_grid(const TempoPassIn& bin, const TempoPassOut& bo, const Onsets& on, const Tempo& tp);
     ResultsHost download_results(const Beats& bt, const TempoPassIn& bin, const TempoPassOut& bo);
+    Overview overview(const float* d_samples, const TempoPassIn& bin, const TempoPassOut& bo, Timers& tm);
+    void overview_results(const Overview& ov, const Front& f, const TempoPassIn& bin, const TempoPassOut& bo, Timers& tm);
     void fill_results(const Front& f, const TempoPassIn& bin, const std::vector<TempoEst>& best, const Tempo& tp,
                       const ResultsHost& rh, std::vector<TrackRes>& res);
 

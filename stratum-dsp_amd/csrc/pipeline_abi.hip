@@ -7,6 +7,7 @@
 #include <thread>
 
 #include "batch_sched.hpp"
+#include "overview_plan.hpp"
 #include "pipeline.hpp"
 
 namespace sdsp {
@@ -85,13 +86,37 @@ void fill_result(const TrackRes& r, uint32_t sr, float ms, sdsp_result* o) {
     o->tempogram_percussive_used = r.perc_used;
 }
 
+// one track's overview: the arrays for a track that is OK, the config-wide fields for every track
+void fill_overview(const TrackOv& t, int status, const sdsp_config& cfg, uint32_t sr, const sdsp_overview_request& req,
+                   sdsp_overview* o) {
+    std::memset(o, 0, sizeof(*o));
+    o->status = status;
+    o->frame_size = (uint32_t)cfg.frame_size;
+    o->hop_size = (uint32_t)cfg.hop_size;
+    ov_band_bins(req.low_max_hz, req.mid_max_hz, cfg.frame_size, sr, &o->band_bins[0], &o->band_bins[1]);
+    if (status != SDSP_OK) return;
+    o->n_columns = t.C;
+    o->n_frames = t.F;
+    o->first_sample = t.first;
+    o->n_samples = t.n;
+    if (t.C == 0) return;
+    // one block for the five arrays (sdsp_overview_free frees it through smin)
+    float* p = (float*)std::malloc(5 * (size_t)t.C * sizeof(float));
+    std::memcpy(p, t.blk.get() + t.at, 5 * (size_t)t.C * sizeof(float));
+    o->smin = p;
+    o->smax = p + t.C;
+    o->low = p + 2 * t.C;
+    o->mid = p + 3 * t.C;
+    o->high = p + 4 * t.C;
+}
+
 // One device-resident batch on `device`.  The engine's main stream first waits for `user_stream`
 // (everything queued on it so far) and for `wait_ev` (a copy's completion), whichever are given.
 // The batch on a context whose mutex the caller holds (run_device, and sdsp_analyze_audio's
 // direct path, which stages its one track into a context buffer under the same lock).
 int32_t run_locked(DeviceCtx& d, const float* d_samples, const uint64_t* offsets, const uint64_t* lens, uint64_t n,
                    uint32_t sr, const sdsp_config* cfg, void* user_stream, sdsp_result* outs, int stages,
-                   hipEvent_t wait_ev) {
+                   hipEvent_t wait_ev, const sdsp_overview_request* req = nullptr, sdsp_overview* ovs = nullptr) {
     if (stages != SDSP_STAGES_FULL && stages != SDSP_STAGES_BPM_ONLY) throw HipError("unknown stage mask");
     if (user_stream) {
         hipEvent_t ev;
@@ -104,7 +129,10 @@ int32_t run_locked(DeviceCtx& d, const float* d_samples, const uint64_t* offsets
     auto t0 = std::chrono::steady_clock::now();
     std::vector<uint64_t> off(offsets, offsets + n), ln(lens, lens + n);
     std::vector<TrackRes> res;
+    std::vector<TrackOv> ov;
     Pipeline p(d, *cfg, sr, stages);
+    d.last_ov = sdsp_debug_overview_times{};
+    if (req) p.set_overview(*req, &ov);
     try {
         p.run(d_samples, off, ln, res);
         // Certified block energies: a track whose key vote had an energy-dependent
@@ -150,16 +178,19 @@ int32_t run_locked(DeviceCtx& d, const float* d_samples, const uint64_t* offsets
     const float ms = (float)(std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count() /
                              (double)std::max<uint64_t>(n, 1));
     for (uint64_t i = 0; i < n; i++) fill_result(res[(size_t)i], sr, ms, &outs[i]);
+    if (req)
+        for (uint64_t i = 0; i < n; i++) fill_overview(ov[(size_t)i], res[(size_t)i].status, *cfg, sr, *req, &ovs[i]);
     return SDSP_OK;
 }
 
 int32_t run_device(int device, const float* d_samples, const uint64_t* offsets, const uint64_t* lens, uint64_t n,
                    uint32_t sr, const sdsp_config* cfg, void* user_stream, sdsp_result* outs,
-                   int stages = SDSP_STAGES_FULL, hipEvent_t wait_ev = nullptr) {
+                   int stages = SDSP_STAGES_FULL, hipEvent_t wait_ev = nullptr,
+                   const sdsp_overview_request* req = nullptr, sdsp_overview* ovs = nullptr) {
     DeviceCtx& d = device_ctx(device);
     std::lock_guard<std::mutex> lk(d.mu);
     SDSP_HIP_CHECK(hipSetDevice(device));
-    return run_locked(d, d_samples, offsets, lens, n, sr, cfg, user_stream, outs, stages, wait_ev);
+    return run_locked(d, d_samples, offsets, lens, n, sr, cfg, user_stream, outs, stages, wait_ev, req, ovs);
 }
 
 }  // namespace
@@ -273,6 +304,63 @@ int32_t sdsp_analyze_batch_device_ex(const float* d_samples, const uint64_t* off
             outs[i].status = SDSP_ERR_PROCESSING;
             std::snprintf(outs[i].error_message, sizeof outs[i].error_message, "Processing error: %s", e.what());
         }
+        return SDSP_ERR_PROCESSING;
+    }
+}
+
+// The device batch with per-track overview envelopes (include/stratum_hip.h).  The request is
+// checked before anything else; without one the call is sdsp_analyze_batch_device_ex.
+int32_t sdsp_analyze_batch_device_overview(const float* d_samples, const uint64_t* offsets, const uint64_t* lens,
+                                           uint64_t n_tracks, uint32_t sample_rate, const sdsp_config* cfg,
+                                           int32_t device, void* stream, int32_t stages, sdsp_result* outs,
+                                           const sdsp_overview_request* req, sdsp_overview* overviews) {
+    if (!req)
+        return sdsp_analyze_batch_device_ex(d_samples, offsets, lens, n_tracks, sample_rate, cfg, device, stream, stages,
+                                            outs);
+    auto fail_all = [&](int32_t status, const char* text) {
+        for (uint64_t i = 0; i < n_tracks; i++) {
+            std::memset(&outs[i], 0, sizeof(outs[i]));
+            outs[i].status = status;
+            std::snprintf(outs[i].error_message, sizeof outs[i].error_message, "%s", text);
+            if (overviews) {
+                std::memset(&overviews[i], 0, sizeof(overviews[i]));
+                overviews[i].status = status;
+            }
+        }
+        return status;
+    };
+    if (const char* why = overview_request_error(req->columns, req->frames_per_column, req->low_max_hz, req->mid_max_hz))
+        return fail_all(SDSP_ERR_INVALID_INPUT, why);
+    if (!overviews) return fail_all(SDSP_ERR_INVALID_INPUT, "Invalid input: overview request without an overviews array");
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
+        return fail_all(SDSP_ERR_PROCESSING, "Processing error: no HIP device");
+    try {
+        return run_device(device, d_samples, offsets, lens, n_tracks, sample_rate, cfg, stream, outs, stages, nullptr, req,
+                          overviews);
+    } catch (const std::exception& e) {
+        std::fprintf(stderr, "sdsp_analyze_batch_device_overview: %s\n", e.what());
+        char text[256];
+        std::snprintf(text, sizeof text, "Processing error: %s", e.what());
+        return fail_all(SDSP_ERR_PROCESSING, text);
+    }
+}
+
+void sdsp_overview_free(sdsp_overview* o) {
+    if (!o) return;
+    std::free(o->smin);  // the five arrays are one block (fill_overview)
+    o->smin = o->smax = o->low = o->mid = o->high = nullptr;
+    o->n_columns = 0;
+}
+
+int32_t sdsp_debug_last_overview_times(int32_t device, sdsp_debug_overview_times* out) {
+    try {
+        if (!out) return SDSP_ERR_INVALID_INPUT;
+        DeviceCtx& d = device_ctx(device);
+        std::lock_guard<std::mutex> lk(d.mu);
+        *out = d.last_ov;
+        return SDSP_OK;
+    } catch (const std::exception&) {
         return SDSP_ERR_PROCESSING;
     }
 }

@@ -11,7 +11,7 @@
 #include <string>
 #include <vector>
 
-#include "../../include/stratum_hip.h"
+#include "../../include/stratum_hip_debug.h"
 #include "sdsp_device.hpp"
 
 #define SDSP_HIP_CHECK(expr)                                                                              \
@@ -88,6 +88,7 @@ struct DeviceCtx {
     sdsp_stage_times last{};
     std::vector<uint8_t> last_near;  // per track of the last call: its key vote was near a decision (rerun)
     uint64_t last_tail_reruns = 0;   // tracks the last call reran in place (Pipeline::rerun_tail)
+    sdsp_debug_overview_times last_ov{};  // the last call with an overview request (Pipeline::overview)
     DevBuf& buf(const std::string& name) {
         auto& b = bufs[name];
         if (!b) {

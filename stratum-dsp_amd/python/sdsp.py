@@ -14,8 +14,9 @@ import subprocess
 
 import numpy as np
 
-from sdsp_abi import (ERROR_NAMES, FLAG_NAMES, SdspAudioDecodeStats, SdspConfidence, SdspConfig, SdspDecodeStats,
-                      SdspFlacDecodeStats, SdspResult, SdspStageTimes, result_to_dict)
+from sdsp_abi import (ERROR_NAMES, FLAG_NAMES, SdspAudioDecodeStats, SdspConfidence, SdspConfig, SdspDebugOverviewTimes,
+                      SdspDecodeStats, SdspFlacDecodeStats, SdspOverview, SdspOverviewRequest, SdspResult,
+                      SdspStageTimes, OVERVIEW_ARRAYS, result_to_dict)
 
 PKG = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LIB_PATH = os.environ.get("SDSP_LIB_PATH") or os.path.join(PKG, "lib", "libstratum_hip.so")  # override: layout/ablation builds
@@ -70,6 +71,15 @@ def _load(path):
                                                    C.POINTER(SdspResult)]
         L.sdsp_analyze_batch_device_ex.restype = C.c_int32
         L.sdsp_result_free.argtypes = [C.POINTER(SdspResult)]
+        L.sdsp_analyze_batch_device_overview.argtypes = [C.c_void_p, u64p, u64p, C.c_uint64, C.c_uint32,
+                                                         C.POINTER(SdspConfig), C.c_int32, C.c_void_p, C.c_int32,
+                                                         C.POINTER(SdspResult), C.POINTER(SdspOverviewRequest),
+                                                         C.POINTER(SdspOverview)]
+        L.sdsp_analyze_batch_device_overview.restype = C.c_int32
+        L.sdsp_overview_free.argtypes = [C.POINTER(SdspOverview)]
+        L.sdsp_overview_free.restype = None
+        L.sdsp_debug_last_overview_times.argtypes = [C.c_int32, C.POINTER(SdspDebugOverviewTimes)]
+        L.sdsp_debug_last_overview_times.restype = C.c_int32
         L.sdsp_generate_synthetic.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint64, C.c_int32,
                                               C.c_int32, C.c_void_p, fp, C.POINTER(C.c_int32)]
         L.sdsp_generate_synthetic.restype = C.c_int32
@@ -539,6 +549,63 @@ def analyze_batch_device(d_ptr, offsets, lens, sample_rate=44100, config=None, d
     res = [batch[i] for i in range(n)]
     batch.free()
     return res
+
+
+def overview_to_dict(o):
+    """The scalar fields and the five arrays (float32 copies) of one sdsp_overview."""
+    n = int(o.n_columns)
+    d = {"n_columns": n, "n_frames": int(o.n_frames), "first_sample": int(o.first_sample),
+         "n_samples": int(o.n_samples), "frame_size": int(o.frame_size), "hop_size": int(o.hop_size),
+         "band_bins": [int(o.band_bins[0]), int(o.band_bins[1])], "status": int(o.status)}
+    for k in OVERVIEW_ARRAYS:
+        p = getattr(o, k)
+        d[k] = np.ctypeslib.as_array(p, shape=(n,)).copy() if n and p else np.zeros(0, np.float32)
+    return d
+
+
+def overview_request(columns=0, frames_per_column=0, low_max_hz=250.0, mid_max_hz=4000.0):
+    """An sdsp_overview_request: `columns` columns per track, or one column per `frames_per_column`
+    frames (exactly one of the two), and the upper edges of the low and the mid band in Hz."""
+    return SdspOverviewRequest(columns, frames_per_column, low_max_hz, mid_max_hz)
+
+
+def analyze_batch_device_overview(d_ptr, offsets, lens, sample_rate=44100, config=None, device=0, stream=None,
+                                  stages=STAGES_FULL, request=None):
+    """sdsp_analyze_batch_device_overview: analyze_batch_device(raw=True) that also returns every
+    track's overview envelope.  `request` is an SdspOverviewRequest (overview_request()); None
+    passes NULL, which is sdsp_analyze_batch_device_ex itself.  Returns (ResultBatch, overviews):
+    overviews[i] is a dict of track i's scalar fields (n_columns, n_frames, first_sample, n_samples,
+    frame_size, hop_size, band_bins, status) and its five float32 arrays smin, smax, low, mid, high
+    (include/stratum_hip.h has the definition); [] without a request.  Raises AnalysisError when the
+    call as a whole fails (a bad request: InvalidInput, before any device is touched)."""
+    offs = np.ascontiguousarray(offsets, dtype=np.uint64)
+    ln = np.ascontiguousarray(lens, dtype=np.uint64)
+    n = ln.size
+    outs = (SdspResult * n)()
+    ovs = (SdspOverview * max(n, 1))() if request is not None else None
+    cfg = config if config is not None else default_config()
+    _schedule_from_env()
+    u64p = C.POINTER(C.c_uint64)
+    st = lib().sdsp_analyze_batch_device_overview(C.c_void_p(d_ptr), offs.ctypes.data_as(u64p), ln.ctypes.data_as(u64p),
+                                                  n, sample_rate, C.byref(cfg), device, C.c_void_p(stream or 0), stages,
+                                                  outs, C.byref(request) if request is not None else None, ovs)
+    if st != 0:
+        raise AnalysisError(st, _batch_error(outs, n, "device batch failed"))
+    overviews = []
+    if ovs is not None:
+        for i in range(n):
+            overviews.append(overview_to_dict(ovs[i]))
+            lib().sdsp_overview_free(C.byref(ovs[i]))
+    return ResultBatch(outs, n), overviews
+
+
+def overview_times(device=0):
+    """sdsp_debug_last_overview_times: the overview kernels' event times and bytes of the last call
+    with a request on `device`."""
+    t = SdspDebugOverviewTimes()
+    if lib().sdsp_debug_last_overview_times(device, C.byref(t)) != 0:
+        raise RuntimeError("sdsp_debug_last_overview_times failed")
+    return {k: getattr(t, k) for k, _ in SdspDebugOverviewTimes._fields_}
 
 
 def generate_synthetic(d_ptr, n_tracks, length, sample_rate=44100, seed0=0, bpm_mode=0, device=0, stream=None):

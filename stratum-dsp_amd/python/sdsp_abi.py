@@ -292,6 +292,53 @@ class SdspConfidence(C.Structure):
     ]
 
 
+class SdspOverviewRequest(C.Structure):
+    """sdsp_overview_request: exactly one of columns / frames_per_column is non-zero."""
+
+    _fields_ = [
+        ("columns", u32),
+        ("frames_per_column", u32),
+        ("low_max_hz", f32),
+        ("mid_max_hz", f32),
+    ]
+
+
+class SdspOverview(C.Structure):
+    """sdsp_overview: one track's overview envelope (library-owned arrays, n_columns each)."""
+
+    _fields_ = [
+        ("n_columns", u64),
+        ("n_frames", u64),
+        ("first_sample", u64),
+        ("n_samples", u64),
+        ("frame_size", u32),
+        ("hop_size", u32),
+        ("band_bins", u32 * 2),
+        ("smin", C.POINTER(f32)),
+        ("smax", C.POINTER(f32)),
+        ("low", C.POINTER(f32)),
+        ("mid", C.POINTER(f32)),
+        ("high", C.POINTER(f32)),
+        ("status", C.c_int32),
+    ]
+
+
+class SdspDebugOverviewTimes(C.Structure):
+    """sdsp_debug_overview_times (include/stratum_hip_debug.h)."""
+
+    _fields_ = [
+        ("sample_ms", C.c_double),
+        ("band_ms", C.c_double),
+        ("sample_bytes", C.c_double),
+        ("band_bytes", C.c_double),
+        ("columns", u64),
+        ("sub_batches", u64),
+    ]
+
+
+OVERVIEW_ARRAYS = ("smin", "smax", "low", "mid", "high")
+
+
 NOTE_NAMES = ["C", "C#", "D", "D#", "E", "F", "F#", "G", "G#", "A", "A#", "B"]
 FLAG_NAMES = ["MultimodalBpm", "WeakTonality", "TempoVariation", "OnsetDetectionAmbiguous"]
 ERROR_NAMES = {1: "InvalidInput", 2: "DecodingError", 3: "ProcessingError", 4: "NotImplemented", 5: "NumericalError"}
