@@ -356,6 +356,122 @@ int32_t sdsp_analyze_batch_device_overview(const float* d_samples, const uint64_
 void sdsp_overview_free(sdsp_overview* o);
 
 /*
+ * Key timeline: per-segment keys, a primary key and the key changes of every track, the reference's
+ * detect_key_changes (src/features/key/key_changes.rs:70) computed inside the analysis call from the
+ * smoothed chroma rows it already holds on the device.
+ *
+ * Scope: a track whose key path runs (SDSP_STAGES_FULL, trimmed length n >= frame_size and n >= the
+ * key STFT's frame size).  With kfs, khop the key STFT's frame and hop (the override's
+ * key_stft_frame_size / key_stft_hop_size, else frame_size / hop_size):
+ *   F = (n - kfs) / khop + 1 key frames
+ *   C[f][0..12), f in [0, F): the chroma rows the key decision reads: after sharpening (if
+ *       configured), after the 5-frame median smoothing (when F > 5), before the edge trim and
+ *       without frame weights (enable_key_edge_trim and the frame weighting do not reach the timeline)
+ *   fps = (f32)sample_rate / (f32)khop
+ * The request gives exactly one of two forms (a form is given when either of its fields is not 0):
+ *   seconds  L = (u64)(segment_seconds * fps), O = (u64)(overlap_seconds * fps), H = L - O
+ *            (f32 products, truncated: key_changes.rs:92-95)
+ *   frames   L = segment_frames, H = hop_frames
+ *   S = F < L ? 0 : (F - L) / H + 1 segments; segment s covers frames [s H, s H + L),
+ *   start_frame = s H, timestamp = (f32)(s H) / fps seconds after first_sample.
+ * Per segment, detect_key (key/detector.rs:68-313) with the Krumhansl-Kessler templates T:
+ *   raw[k] = the f32 sum from 0, over the segment's frames in ascending order, of the f32 dot
+ *            product from 0 over i ascending of C[f][i] * T[k][i]   (detector.rs:984-1001)
+ *   then per-mode normalisation when both maxima > 1e-9, the last maximum of each mode, the
+ *   0.20 / 0.10 circle-of-fifths bonus, and a stable descending sort (detector.rs:135-293)
+ *   key         the first key of the sorted table (mode * 12 + tonic: 0-11 major, 12-23 minor)
+ *   confidence  sorted[0] > 0 ? clamp((sorted[0] - sorted[1]) / sorted[0], 0, 1) : 0
+ *   clarity     compute_key_clarity over the sorted table (key_clarity.rs:51-93)
+ *   top_keys, top_scores   the first three entries of the sorted table
+ * Primary key: the key with the most segments; among keys with equally many, the one whose first
+ * segment is earliest (the reference takes max_by_key over a HashMap, so it returns any of them,
+ * differing from run to run; this is one of its outcomes).  primary_confidence is the f32 sum of
+ * that key's segment confidences in segment order over (f32)primary_count.  S = 0: primary_key -1,
+ * primary_confidence 0, primary_count 0.
+ * Changes: for i in [1, S) with key[i] != key[i-1]: confidence = (confidence[i-1] + confidence[i]) / 2.0f,
+ * timestamp = timestamp[i], segment = i; reported iff confidence > min_change_confidence.  The
+ * reference's fixed threshold is 0.2; a negative value reports every change.
+ *
+ * What these numbers are, as measured on tonal and noise tracks alike:
+ *   - The templates are always Krumhansl-Kessler (KeyTemplates::new()), whatever key_template_set
+ *     and enable_key_ensemble say.  Following the configured set is left for later.
+ *   - Whenever both modes score (> 1e-9), both within-mode maxima normalise to exactly 1.0 and each
+ *     takes its own full bonus, so the top major and the top minor key tie at exactly 1.2: the
+ *     stable sort puts the major key first, and confidence is exactly 0.  The reference's threshold
+ *     0.2 therefore reports no change on such input; min_change_confidence < 0 is the setting that
+ *     reports where the key moves.
+ *   - clarity is reported as the reference computes it; it does not separate tonal input from noise
+ *     (about 0.65 on cadences, about 0.75 on white noise) and is not a tonality measure.
+ * Non-finite input samples are out of scope.
+ *
+ * Per track: an analysis status other than SDSP_OK gives that status, zero segments and zero fields;
+ * a track whose key path is skipped (too short) gives n_frames 0, zero segments, primary_key -1 and
+ * leaves the status alone.  segment_frames (L), hop_frames (H), frame_size (kfs) and hop_size (khop)
+ * are filled for every track.  first_sample is the trim start in the caller's track, as in
+ * sdsp_overview: sample first_sample + start_frame * hop_size begins a segment.
+ */
+typedef struct sdsp_key_timeline_request {
+    float segment_seconds, overlap_seconds; /* the seconds form */
+    uint32_t segment_frames, hop_frames;    /* the frames form */
+    float min_change_confidence;
+} sdsp_key_timeline_request;
+
+typedef struct sdsp_key_segment {
+    uint64_t start_frame;
+    float timestamp;
+    int32_t key;
+    float confidence, clarity;
+    int32_t top_keys[3];
+    float top_scores[3];
+} sdsp_key_segment;
+
+typedef struct sdsp_key_change {
+    uint64_t segment; /* i: the change lies between segments i - 1 and i */
+    float timestamp;
+    int32_t from_key, to_key;
+    float confidence;
+} sdsp_key_change;
+
+typedef struct sdsp_key_timeline {
+    uint64_t n_segments, n_changes, n_frames; /* S, reported changes, F */
+    uint64_t first_sample;
+    uint32_t segment_frames, hop_frames; /* L, H */
+    uint32_t frame_size, hop_size;       /* kfs, khop */
+    int32_t primary_key;
+    float primary_confidence;
+    uint64_t primary_count;
+    sdsp_key_segment* segments; /* library-owned, n_segments (NULL for none) */
+    sdsp_key_change* changes;   /* library-owned, n_changes (NULL for none) */
+    int32_t status;             /* the track's sdsp_status */
+} sdsp_key_timeline;
+
+/*
+ * sdsp_analyze_batch_device_ex with both optional requests, so a caller who wants overviews and
+ * key timelines pays for one analysis: ov_req / overviews as in sdsp_analyze_batch_device_overview,
+ * kt_req / timelines (n_tracks entries, freed one by one with sdsp_key_timeline_free) as above.
+ * Both requests NULL is sdsp_analyze_batch_device_ex itself (the same launches, the same results).
+ * A request never changes an sdsp_result.  Checked before any device is touched, failing the whole
+ * call (every outs[i] carries the status and the reason, every requested overview and timeline is
+ * zeroed but for its status):
+ *   SDSP_ERR_INVALID_INPUT    an overview request sdsp_analyze_batch_device_overview refuses; both
+ *                             timeline forms given, or neither; seconds that are not finite or are
+ *                             negative; a NaN min_change_confidence; L == 0, O >= L or H == 0; L or
+ *                             H >= 2^31; a timeline request with SDSP_STAGES_BPM_ONLY (no key path);
+ *                             a request without its output array
+ *   SDSP_ERR_NOT_IMPLEMENTED  a timeline request with enable_key_beat_synchronous and not
+ *                             enable_key_log_frequency (the chroma rows are beats, not frames)
+ */
+int32_t sdsp_analyze_batch_device_requests(const float* d_samples, const uint64_t* offsets,
+                                           const uint64_t* lens, uint64_t n_tracks, uint32_t sample_rate,
+                                           const sdsp_config* cfg, int32_t device, void* stream,
+                                           int32_t stages, sdsp_result* outs,
+                                           const sdsp_overview_request* ov_req, sdsp_overview* overviews,
+                                           const sdsp_key_timeline_request* kt_req,
+                                           sdsp_key_timeline* timelines);
+/* Frees the arrays owned by one timeline (they share one allocation: never free() them one by one). */
+void sdsp_key_timeline_free(sdsp_key_timeline* t);
+
+/*
  * Synthetic track generator on device: writes n_tracks tracks of `len`
  * samples each, track i at d_out + i*len, seeds seed0 + i.  bpm_out/key_out (host, may be
  * NULL) receive the generated tempo and key (key = mode*12 + tonic).  bpm_mode 0 = uniform

@@ -114,6 +114,18 @@ typedef struct sdsp_debug_overview_times {
 int32_t sdsp_debug_last_overview_times(int32_t device, sdsp_debug_overview_times* out);
 
 /*
+ * Stage probe of the key timeline (include/stratum_hip.h, sdsp_key_timeline): the timeline kernel
+ * and the host's primary-key and change logic over uploaded chroma rows, taken as the smoothed rows
+ * C of the definition.  host_chroma: the tracks' rows back to back, frames[t] rows of 12 floats for
+ * track t (0 allowed).  out[t] (n_tracks entries, sdsp_key_timeline_free) is filled as an analysis
+ * call fills it, with first_sample 0 and status SDSP_OK.  SDSP_ERR_INVALID_INPUT for a request
+ * sdsp_analyze_batch_device_requests refuses.
+ */
+int32_t sdsp_debug_key_timeline(const float* host_chroma, const uint64_t* frames, uint64_t n_tracks,
+                                uint32_t sample_rate, const sdsp_config* cfg,
+                                const sdsp_key_timeline_request* req, sdsp_key_timeline* out, int32_t device);
+
+/*
  * Stage probe of the tempo path: the pipeline's own tempo pass (features, novelty, both tempograms;
  * the same parameter set-up and launches as an analysis call) over host magnitude spectrograms
  * instead of an STFT.  host_mags holds the tracks' rows back to back, frame_size / 2 + 1 values per

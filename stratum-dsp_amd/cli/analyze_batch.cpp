@@ -21,8 +21,15 @@
 // buffer with --gpu-decode, otherwise from the decoded tracks uploaded to the first device of
 // --devices, one call per sample rate and at most 512 tracks or 8 GB.
 //
+// --key-timeline SEC[:OVERLAP[:MINCONF]] (opt-in; JSONL only): each line's object gets a
+// "key_timeline" member (include/stratum_hip.h, sdsp_key_timeline): the key of every SEC-second
+// segment (overlapping by OVERLAP seconds, default SEC / 4), the primary key and the key changes
+// whose confidence exceeds MINCONF (default -1: every change; 0.2 is the reference's constant), with
+// key names.  It runs through sdsp_analyze_batch_device_requests like --overview and combines with it
+// in one analysis.
+//
 //   analyze_batch [--jobs N] [--devices MASK] [--json] [--gpu-decode] [--overview N | --overview-frames K]
-//                 <file1> <file2> ...
+//                 [--key-timeline SEC[:OVERLAP[:MINCONF]]] <file1> <file2> ...
 #include <algorithm>
 #include <atomic>
 #include <chrono>
@@ -49,6 +56,7 @@ struct Item {
     std::string key;
     int8_t tr[4] = {-1, -1, -1, -1};
     std::string overview;  // --overview: the "overview" member's value
+    std::string timeline;  // --key-timeline: the "key_timeline" member's value
 };
 
 // floats so that an f32 round-trips
@@ -75,6 +83,48 @@ std::string overview_json(const sdsp_overview& o) {
     json_floats(s, "mid", o.mid, o.n_columns);
     json_floats(s, "high", o.high, o.n_columns);
     return s + "}";
+}
+
+std::string key_index_name(int32_t key) {
+    char b[8] = "";
+    if (key >= 0 && key < 24) sdsp_key_name(key / 12, (uint32_t)(key % 12), b, sizeof b);
+    return b;
+}
+std::string key_timeline_json(const sdsp_key_timeline& t) {
+    char b[512];
+    std::snprintf(b, sizeof b,
+                  "{\"n_segments\":%llu,\"n_changes\":%llu,\"n_frames\":%llu,\"first_sample\":%llu,"
+                  "\"segment_frames\":%u,\"hop_frames\":%u,\"frame_size\":%u,\"hop_size\":%u,\"status\":%d,"
+                  "\"primary_key\":%d,\"primary_key_name\":%s,\"primary_confidence\":%.9g,\"primary_count\":%llu,"
+                  "\"segments\":[",
+                  (unsigned long long)t.n_segments, (unsigned long long)t.n_changes, (unsigned long long)t.n_frames,
+                  (unsigned long long)t.first_sample, t.segment_frames, t.hop_frames, t.frame_size, t.hop_size, t.status,
+                  t.primary_key, json_str(key_index_name(t.primary_key)).c_str(), (double)t.primary_confidence,
+                  (unsigned long long)t.primary_count);
+    std::string s = b;
+    for (uint64_t i = 0; i < t.n_segments; i++) {
+        const sdsp_key_segment& g = t.segments[i];
+        std::snprintf(b, sizeof b,
+                      "%s{\"start_frame\":%llu,\"timestamp\":%.9g,\"key\":%d,\"key_name\":%s,\"confidence\":%.9g,"
+                      "\"clarity\":%.9g,\"top_keys\":[%d,%d,%d],\"top_scores\":[%.9g,%.9g,%.9g]}",
+                      i ? "," : "", (unsigned long long)g.start_frame, (double)g.timestamp, g.key,
+                      json_str(key_index_name(g.key)).c_str(), (double)g.confidence, (double)g.clarity, g.top_keys[0],
+                      g.top_keys[1], g.top_keys[2], (double)g.top_scores[0], (double)g.top_scores[1],
+                      (double)g.top_scores[2]);
+        s += b;
+    }
+    s += "],\"changes\":[";
+    for (uint64_t i = 0; i < t.n_changes; i++) {
+        const sdsp_key_change& c = t.changes[i];
+        std::snprintf(b, sizeof b,
+                      "%s{\"segment\":%llu,\"timestamp\":%.9g,\"from_key\":%d,\"from_key_name\":%s,\"to_key\":%d,"
+                      "\"to_key_name\":%s,\"confidence\":%.9g}",
+                      i ? "," : "", (unsigned long long)c.segment, (double)c.timestamp, c.from_key,
+                      json_str(key_index_name(c.from_key)).c_str(), c.to_key, json_str(key_index_name(c.to_key)).c_str(),
+                      (double)c.confidence);
+        s += b;
+    }
+    return s + "]}";
 }
 
 // percentile as the example computes it: sort, index round((len-1) * p)
@@ -154,6 +204,8 @@ int main(int argc, char** argv) {
     uint32_t devices = 0;
     sdsp_overview_request ovreq{0, 0, 250.0f, 4000.0f};
     bool overview = false;
+    sdsp_key_timeline_request ktreq{0.0f, 0.0f, 0, 0, -1.0f};
+    bool timeline = false;
     std::vector<std::string> paths;
     for (size_t i = 0; i < a.size(); i++) {
         const std::string& s = a[i];
@@ -181,16 +233,45 @@ int main(int argc, char** argv) {
             (s == "--overview" ? ovreq.columns : ovreq.frames_per_column) = (uint32_t)v;
             overview = true;
             i++;
+        } else if (s == "--key-timeline") {
+            // SEC[:OVERLAP[:MINCONF]]
+            float v[3] = {0.0f, 0.0f, -1.0f};
+            int n = 0;
+            bool good = i + 1 < a.size() && !a[i + 1].empty();
+            for (size_t p0 = 0; good && n < 3;) {
+                const std::string& w = a[i + 1];
+                const size_t p1 = std::min(w.find(':', p0), w.size());
+                char* end = nullptr;
+                const std::string part = w.substr(p0, p1 - p0);
+                v[n] = std::strtof(part.c_str(), &end);
+                good = !part.empty() && end && *end == 0;
+                n++;
+                if (p1 == w.size()) break;
+                p0 = p1 + 1;
+                if (n == 3) good = false;  // a fourth part
+            }
+            if (!good || !(v[0] > 0.0f)) {
+                std::fprintf(stderr, "Error: --key-timeline requires SEC[:OVERLAP[:MINCONF]] with SEC > 0\n");
+                return 1;
+            }
+            ktreq.segment_seconds = v[0];
+            ktreq.overlap_seconds = n >= 2 ? v[1] : v[0] / 4.0f;
+            ktreq.min_change_confidence = v[2];
+            timeline = true;
+            i++;
         } else if (s == "--help" || s == "-h") {
             std::fprintf(stderr,
                          "Usage: analyze_batch [--jobs N] [--devices MASK] [--json] [--gpu-decode] [--overview N | "
-                         "--overview-frames K] <file1> <file2> ...\n\n"
+                         "--overview-frames K] [--key-timeline SEC[:OVERLAP[:MINCONF]]] <file1> <file2> ...\n\n"
                          "--jobs N        Decode workers (default: CPU-1)\n"
                          "--devices MASK  GPU bitmask (default: all visible GPUs)\n"
                          "--json          Emit one JSON object per line (JSONL)\n"
                          "--gpu-decode    Decode on the GPUs: FLAC, ALAC (M4A / CAF), WAV, AIFF and Ogg Vorbis by kernels (same output)\n"
                          "--overview N    With --json: add each track's overview envelope in N columns (\"overview\")\n"
-                         "--overview-frames K  ... or in one column per K analysis frames\n");
+                         "--overview-frames K  ... or in one column per K analysis frames\n"
+                         "--key-timeline SEC[:OVERLAP[:MINCONF]]  With --json: add each track's key per SEC-second segment,\n"
+                         "                primary key and key changes (\"key_timeline\"); OVERLAP defaults to SEC/4, MINCONF\n"
+                         "                to -1 (every change; 0.2 is the reference's threshold)\n");
             return 0;
         } else {
             paths.push_back(s);
@@ -201,6 +282,7 @@ int main(int argc, char** argv) {
         return 1;
     }
     if (overview && !json) std::fprintf(stderr, "Note: --overview / --overview-frames add to the --json lines only\n");
+    if (timeline && !json) std::fprintf(stderr, "Note: --key-timeline adds to the --json lines only\n");
     if (paths.empty()) {
         std::fprintf(stderr, "ERROR: Provide at least one audio file path. Use --help for usage.\n");
         return 2;
@@ -254,8 +336,10 @@ int main(int argc, char** argv) {
 
     sdsp_config cfg;
     sdsp_config_default(&cfg);
-    auto take = [](Item& it, const sdsp_result& r, const sdsp_overview* ov = nullptr) {
+    auto take = [](Item& it, const sdsp_result& r, const sdsp_overview* ov = nullptr,
+                   const sdsp_key_timeline* kt = nullptr) {
         if (ov) it.overview = overview_json(*ov);
+        if (kt) it.timeline = key_timeline_json(*kt);
         if (r.status != 0) {
             it.error = std::string("analysis failed: ") + r.error_message;
             return;
@@ -326,13 +410,16 @@ int main(int argc, char** argv) {
                 }
                 std::vector<sdsp_result> outs(okk.size());
                 std::vector<sdsp_overview> ovs(overview ? okk.size() : 0);  // (zeroed; without a request: the plain entry)
-                (void)sdsp_analyze_batch_device_overview(d_samples, o2.data(), l2.data(), okk.size(), kv.first, &cfg, dev,
+                std::vector<sdsp_key_timeline> kts(timeline ? okk.size() : 0);
+                (void)sdsp_analyze_batch_device_requests(d_samples, o2.data(), l2.data(), okk.size(), kv.first, &cfg, dev,
                                                          nullptr, SDSP_STAGES_FULL, outs.data(), overview ? &ovreq : nullptr,
-                                                         overview ? ovs.data() : nullptr);
+                                                         overview ? ovs.data() : nullptr, timeline ? &ktreq : nullptr,
+                                                         timeline ? kts.data() : nullptr);
                 for (size_t j = 0; j < okk.size(); j++) {
-                    take(items[ch.idx[okk[j]]], outs[j], overview ? &ovs[j] : nullptr);
+                    take(items[ch.idx[okk[j]]], outs[j], overview ? &ovs[j] : nullptr, timeline ? &kts[j] : nullptr);
                     sdsp_result_free(&outs[j]);
                     if (overview) sdsp_overview_free(&ovs[j]);
+                    if (timeline) sdsp_key_timeline_free(&kts[j]);
                 }
             }
             if (d_samples) sdsp_device_free(dev, d_samples);
@@ -356,8 +443,8 @@ int main(int argc, char** argv) {
             ptrs.push_back(items[i].samples.data());
             lens.push_back(items[i].samples.size());
         }
-        if (overview) {
-            // the overview entry reads device-resident tracks: upload each group to the first device of
+        if (overview || timeline) {
+            // the requests entry reads device-resident tracks: upload each group to the first device of
             // the mask in parts of at most 512 tracks or 2 Gi samples
             int dev = 0;
             while (dev < 31 && !(devices & (1u << dev))) dev++;
@@ -368,7 +455,8 @@ int main(int argc, char** argv) {
                 const size_t n = k1 - k0;
                 std::vector<uint64_t> off(n);
                 std::vector<sdsp_result> outs(n);
-                std::vector<sdsp_overview> ovs(n);
+                std::vector<sdsp_overview> ovs(overview ? n : 0);
+                std::vector<sdsp_key_timeline> kts(timeline ? n : 0);
                 void* d = nullptr;
                 bool up = sdsp_device_malloc(dev, std::max<uint64_t>(tot, 1) * sizeof(float), &d) == 0;
                 uint64_t o = 0;
@@ -378,13 +466,16 @@ int main(int argc, char** argv) {
                     o += lens[k];
                 }
                 if (up)
-                    (void)sdsp_analyze_batch_device_overview((const float*)d, off.data(), lens.data() + k0, n, kv.first, &cfg, dev,
-                                                             nullptr, SDSP_STAGES_FULL, outs.data(), &ovreq, ovs.data());
+                    (void)sdsp_analyze_batch_device_requests((const float*)d, off.data(), lens.data() + k0, n, kv.first, &cfg, dev,
+                                                             nullptr, SDSP_STAGES_FULL, outs.data(), overview ? &ovreq : nullptr,
+                                                             overview ? ovs.data() : nullptr, timeline ? &ktreq : nullptr,
+                                                             timeline ? kts.data() : nullptr);
                 for (size_t k = k0; k < k1; k++) {
                     if (up) {
-                        take(items[idx[k]], outs[k - k0], &ovs[k - k0]);
+                        take(items[idx[k]], outs[k - k0], overview ? &ovs[k - k0] : nullptr, timeline ? &kts[k - k0] : nullptr);
                         sdsp_result_free(&outs[k - k0]);
-                        sdsp_overview_free(&ovs[k - k0]);
+                        if (overview) sdsp_overview_free(&ovs[k - k0]);
+                        if (timeline) sdsp_key_timeline_free(&kts[k - k0]);
                     } else {
                         items[idx[k]].error = "analysis failed: Processing error: device upload failed";
                     }
@@ -420,6 +511,10 @@ int main(int argc, char** argv) {
             if (!o.overview.empty()) {
                 std::fputs(",\"overview\":", stdout);
                 std::fputs(o.overview.c_str(), stdout);
+            }
+            if (!o.timeline.empty()) {
+                std::fputs(",\"key_timeline\":", stdout);
+                std::fputs(o.timeline.c_str(), stdout);
             }
             std::fputs("}\n", stdout);
         } else {

@@ -399,4 +399,18 @@ void launch_overview_columns(const float* mags, const uint64_t* frame_pfx, const
                              const uint32_t* seg_lo, const uint32_t* seg_hi, const OvParams& P, float* out,
                              uint32_t* part, hipStream_t st);
 
+// ---- k_key_timeline ----
+constexpr int KT_SEGS = 8;  // segments per block, 24 lanes (one per key) each
+// one segment's detect_key result (sdsp_key_segment without the host-computed start and timestamp)
+struct KtSeg {
+    int key;  // mode * 12 + tonic
+    float conf, clarity;
+    int top_keys[3];
+    float top_scores[3];
+};
+// detect_key (Krumhansl-Kessler: tmpl rows 0-23) over every segment [s H, s H + L) of each track's
+// chroma_s rows; track t's segments at out + seg_pfx[t], kt_segments(F_t, L, H) of them
+void launch_key_timeline(const float* chroma_s, const uint64_t* frame_pfx, const uint64_t* seg_pfx, int n_tracks,
+                         uint64_t n_segs, uint32_t L, uint32_t H, const float* tmpl, KtSeg* out, hipStream_t st);
+
 }  // namespace sdsp

@@ -63,6 +63,7 @@ void Pipeline::run(const float* d_samples, const std::vector<uint64_t>& in_off, 
     const size_t T = n_raw.size();
     res.assign(T, TrackRes{});
     if (ov_out_) ov_out_->assign(T, TrackOv{});
+    if (kt_out_) kt_out_->assign(T, TrackKt{});
     const std::string why = check_supported(cfg_, sr_);
     for (size_t i = 0; i < T; i++) {
         if (n_raw[i] == 0) {
@@ -117,6 +118,7 @@ void Pipeline::run(const float* d_samples, const std::vector<uint64_t>& in_off, 
         if (cfg_.enable_hpss_onsets || cfg_.enable_tempogram_percussive_fallback)  // H, P ping-pong + a copy
             need[i] += n / hop * s2_ * 4.0 * 5.0;
         if (cfg_.enable_key_hpss_harmonic && !bpm_only_) need[i] += n / khop * 1024.0 * 4.0;
+        if (kt_out_ && !bpm_only_) need[i] += (n / khop / kt_H_ + 1.0) * 2.0 * sizeof(KtSeg);  // both parities' segments
         if (cfg_.enable_tempogram_multi_resolution && hop != 512) need[i] += n / 512 * s2_ * 4.0 * 1.3;
         total_need += need[i];
     }

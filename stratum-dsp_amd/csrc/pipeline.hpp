@@ -284,6 +284,15 @@ struct KeyTail {
     const float* d_tpl = nullptr;
     KeyParams kp{};
 };
+// The key timeline's segments of a sub-batch's key tracks as queued behind the vote
+// (Pipeline::launch_key); nothing is queued without a request.  The output and
+// the segment prefix are per-parity buffers like the vote's output: the late join reads them after
+// the next sub-batch has launched.
+struct KeyTimelineOut {
+    std::vector<uint64_t> spfx{0};  // segment prefix over the key tracks
+    std::vector<uint64_t> frames;   // F of each key track
+    KtSeg* d_out = nullptr;
+};
 // Late key join: a sub-batch's key results are read after the next sub-batch's tempo path is
 // queued, so the key stream's tail (mask, HPCP, vote) runs beside that tempo path instead of
 // holding the main stream back.  Uploads read by the key stream and the key output live in
@@ -292,7 +301,9 @@ struct KeyTail {
 struct KeyPending {
     std::unique_ptr<Timers> kt;
     KeyOut* d_kout = nullptr;
+    KeyTimelineOut ktl;
     std::vector<size_t> at;  // result slot of each key track
+    std::vector<uint64_t> first;  // its trim start in the caller's track (the key timeline's first_sample)
     KeyTail tail;
 };
 // what key_condition launched with
@@ -325,6 +336,7 @@ struct KeyLaunch {
     int* d_kid = nullptr;
     KeyOut* d_kout = nullptr;
     KeyDbg* d_kdbg = nullptr;
+    KeyTimelineOut ktl;
     // the key spectrogram, frame prefix, templates and vote parameters; with tail.ok the band
     // path's state for rerun_tail
     KeyTail tail;
@@ -382,6 +394,13 @@ struct Overview {
     float* d_out = nullptr;  // track i's smin, smax, low, mid, high back to back at 5 cpfx[i]
     double seg_bytes = 0, col_bytes = 0;  // algorithmic bytes of the two kernels
 };
+// One track's key timeline on the host (sdsp_key_timeline without the call-wide fields): its
+// segments as the kernel wrote them; `on` marks a track whose key path ran.
+struct TrackKt {
+    bool on = false;
+    uint64_t F = 0, first = 0;
+    std::vector<KtSeg> seg;
+};
 // One track's overview on the host (sdsp_overview without the config-wide fields): its five arrays
 // (smin, smax, low, mid, high, C each) back to back at blk + at, in its sub-batch's download.
 struct TrackOv {
@@ -412,6 +431,14 @@ class Pipeline {
     void set_overview(const sdsp_overview_request& req, std::vector<TrackOv>* out) {
         ov_req_ = req;
         ov_out_ = out;
+    }
+    // Before run(): also compute every track's key timeline (include/stratum_hip.h) with segments
+    // of L key frames every H (key_timeline_plan.hpp) into *out, one entry per track of the call.
+    // A pipeline without a request queues nothing for it; nested pipelines get none.
+    void set_key_timeline(uint32_t L, uint32_t H, std::vector<TrackKt>* out) {
+        kt_L_ = L;
+        kt_H_ = H;
+        kt_out_ = out;
     }
 
    private:
@@ -449,6 +476,8 @@ class Pipeline {
     int sb_parity_ = 0;
     sdsp_overview_request ov_req_{};
     std::vector<TrackOv>* ov_out_ = nullptr;  // the call's overviews (set_overview), else nullptr
+    uint32_t kt_L_ = 0, kt_H_ = 0;
+    std::vector<TrackKt>* kt_out_ = nullptr;  // the call's key timelines (set_key_timeline), else nullptr
 
     // force_legacy_bpm skips the tempogram estimate (src/lib.rs:337): no escalation, no
     // candidates, the flags stay None; the hop-512 pass still feeds the onset detectors
@@ -498,6 +527,7 @@ class Pipeline {
     KeyCond key_condition(const std::string& EP, float* mags8, const std::vector<uint64_t>& kpfx,
                           const std::vector<uint64_t>& ktile, uint64_t* d_kpfx, uint64_t* d_ktile, int* d_kid,
                           hipStream_t st2, Timers& kt);
+    void key_timeline_results(const KeyTimelineOut& ktl, const std::vector<size_t>& at, const std::vector<uint64_t>& first);
     void join_key_only(KeyLaunch& kl, const Front& f, std::vector<TrackRes>& res);
     std::vector<KeyOut> join_key(const float* d_samples, const std::vector<uint64_t>& in_off,
                                  const std::vector<uint64_t>& n_raw, const Front& f, KeyLaunch& kl, HostTrace& htr,

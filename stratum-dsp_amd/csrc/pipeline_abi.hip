@@ -7,6 +7,7 @@
 #include <thread>
 
 #include "batch_sched.hpp"
+#include "key_timeline_plan.hpp"
 #include "overview_plan.hpp"
 #include "pipeline.hpp"
 
@@ -110,13 +111,81 @@ void fill_overview(const TrackOv& t, int status, const sdsp_config& cfg, uint32_
     o->high = p + 4 * t.C;
 }
 
+// A checked key timeline request: L and H of key_timeline_plan, and where the timelines go.
+struct KtCall {
+    uint32_t L = 0, H = 0;
+    float min_conf = 0.0f;
+    sdsp_key_timeline* out = nullptr;
+};
+uint32_t kt_khop(const sdsp_config& c) {
+    return (uint32_t)std::min<uint64_t>(std::max<uint64_t>(key_hop(c), 1), INT32_MAX);
+}
+
+// One track's timeline from its segments as the kernel wrote them: starts, timestamps, the primary
+// key and the changes (key_timeline_plan.hpp) on the host; the call-wide fields for every track.
+void fill_key_timeline(const TrackKt& t, int status, const sdsp_config& cfg, uint32_t sr, const KtCall& kc,
+                       sdsp_key_timeline* o) {
+    std::memset(o, 0, sizeof(*o));
+    o->status = status;
+    o->segment_frames = kc.L;
+    o->hop_frames = kc.H;
+    o->frame_size = (uint32_t)std::min<uint64_t>(key_fft(cfg), STFT_GEN_MAX);
+    o->hop_size = kt_khop(cfg);
+    if (status != SDSP_OK) return;
+    o->primary_key = -1;
+    if (!t.on) return;  // the key path did not run (a short track)
+    o->n_frames = t.F;
+    o->first_sample = t.first;
+    const uint64_t S = t.seg.size();
+    if (S == 0) return;
+    const float fps = kt_fps(sr, o->hop_size);
+    std::vector<int32_t> key((size_t)S);
+    std::vector<float> conf((size_t)S);
+    for (uint64_t s = 0; s < S; s++) key[(size_t)s] = t.seg[(size_t)s].key, conf[(size_t)s] = t.seg[(size_t)s].conf;
+    kt_primary(key.data(), conf.data(), S, &o->primary_key, &o->primary_confidence, &o->primary_count);
+    std::vector<sdsp_key_change> ch;
+    for (uint64_t i = 1; i < S; i++) {
+        float cc;
+        if (!kt_change(key.data(), conf.data(), i, kc.min_conf, &cc)) continue;
+        sdsp_key_change c{};
+        c.segment = i;
+        c.timestamp = kt_timestamp(i, kc.H, fps);
+        c.from_key = key[(size_t)i - 1];
+        c.to_key = key[(size_t)i];
+        c.confidence = cc;
+        ch.push_back(c);
+    }
+    // one block for both arrays (sdsp_key_timeline_free frees it through segments)
+    static_assert(sizeof(sdsp_key_segment) % alignof(sdsp_key_change) == 0, "changes follow the segments");
+    char* p = (char*)std::malloc((size_t)S * sizeof(sdsp_key_segment) + ch.size() * sizeof(sdsp_key_change));
+    o->segments = (sdsp_key_segment*)p;
+    for (uint64_t s = 0; s < S; s++) {
+        const KtSeg& g = t.seg[(size_t)s];
+        sdsp_key_segment& e = o->segments[s];
+        std::memset(&e, 0, sizeof e);
+        e.start_frame = kt_start(s, kc.H);
+        e.timestamp = kt_timestamp(s, kc.H, fps);
+        e.key = g.key;
+        e.confidence = g.conf;
+        e.clarity = g.clarity;
+        for (int j = 0; j < 3; j++) e.top_keys[j] = g.top_keys[j], e.top_scores[j] = g.top_scores[j];
+    }
+    o->n_segments = S;
+    if (!ch.empty()) {
+        o->changes = (sdsp_key_change*)(p + (size_t)S * sizeof(sdsp_key_segment));
+        std::memcpy(o->changes, ch.data(), ch.size() * sizeof(sdsp_key_change));
+        o->n_changes = ch.size();
+    }
+}
+
 // One device-resident batch on `device`.  The engine's main stream first waits for `user_stream`
 // (everything queued on it so far) and for `wait_ev` (a copy's completion), whichever are given.
 // The batch on a context whose mutex the caller holds (run_device, and sdsp_analyze_audio's
 // direct path, which stages its one track into a context buffer under the same lock).
 int32_t run_locked(DeviceCtx& d, const float* d_samples, const uint64_t* offsets, const uint64_t* lens, uint64_t n,
                    uint32_t sr, const sdsp_config* cfg, void* user_stream, sdsp_result* outs, int stages,
-                   hipEvent_t wait_ev, const sdsp_overview_request* req = nullptr, sdsp_overview* ovs = nullptr) {
+                   hipEvent_t wait_ev, const sdsp_overview_request* req = nullptr, sdsp_overview* ovs = nullptr,
+                   const KtCall* ktc = nullptr) {
     if (stages != SDSP_STAGES_FULL && stages != SDSP_STAGES_BPM_ONLY) throw HipError("unknown stage mask");
     if (user_stream) {
         hipEvent_t ev;
@@ -133,6 +202,8 @@ int32_t run_locked(DeviceCtx& d, const float* d_samples, const uint64_t* offsets
     Pipeline p(d, *cfg, sr, stages);
     d.last_ov = sdsp_debug_overview_times{};
     if (req) p.set_overview(*req, &ov);
+    std::vector<TrackKt> ktl;
+    if (ktc) p.set_key_timeline(ktc->L, ktc->H, &ktl);
     try {
         p.run(d_samples, off, ln, res);
         // Certified block energies: a track whose key vote had an energy-dependent
@@ -180,17 +251,21 @@ int32_t run_locked(DeviceCtx& d, const float* d_samples, const uint64_t* offsets
     for (uint64_t i = 0; i < n; i++) fill_result(res[(size_t)i], sr, ms, &outs[i]);
     if (req)
         for (uint64_t i = 0; i < n; i++) fill_overview(ov[(size_t)i], res[(size_t)i].status, *cfg, sr, *req, &ovs[i]);
+    if (ktc)
+        for (uint64_t i = 0; i < n; i++)
+            fill_key_timeline(ktl[(size_t)i], res[(size_t)i].status, *cfg, sr, *ktc, &ktc->out[i]);
     return SDSP_OK;
 }
 
 int32_t run_device(int device, const float* d_samples, const uint64_t* offsets, const uint64_t* lens, uint64_t n,
                    uint32_t sr, const sdsp_config* cfg, void* user_stream, sdsp_result* outs,
                    int stages = SDSP_STAGES_FULL, hipEvent_t wait_ev = nullptr,
-                   const sdsp_overview_request* req = nullptr, sdsp_overview* ovs = nullptr) {
+                   const sdsp_overview_request* req = nullptr, sdsp_overview* ovs = nullptr,
+                   const KtCall* ktc = nullptr) {
     DeviceCtx& d = device_ctx(device);
     std::lock_guard<std::mutex> lk(d.mu);
     SDSP_HIP_CHECK(hipSetDevice(device));
-    return run_locked(d, d_samples, offsets, lens, n, sr, cfg, user_stream, outs, stages, wait_ev, req, ovs);
+    return run_locked(d, d_samples, offsets, lens, n, sr, cfg, user_stream, outs, stages, wait_ev, req, ovs, ktc);
 }
 
 }  // namespace
@@ -344,6 +419,120 @@ int32_t sdsp_analyze_batch_device_overview(const float* d_samples, const uint64_
         std::snprintf(text, sizeof text, "Processing error: %s", e.what());
         return fail_all(SDSP_ERR_PROCESSING, text);
     }
+}
+
+// The device batch with both optional requests (include/stratum_hip.h): the overview envelopes
+// and the key timelines from one analysis.  Both are checked before any device is touched.
+int32_t sdsp_analyze_batch_device_requests(const float* d_samples, const uint64_t* offsets, const uint64_t* lens,
+                                           uint64_t n_tracks, uint32_t sample_rate, const sdsp_config* cfg,
+                                           int32_t device, void* stream, int32_t stages, sdsp_result* outs,
+                                           const sdsp_overview_request* ov_req, sdsp_overview* overviews,
+                                           const sdsp_key_timeline_request* kt_req, sdsp_key_timeline* timelines) {
+    if (!ov_req && !kt_req)
+        return sdsp_analyze_batch_device_ex(d_samples, offsets, lens, n_tracks, sample_rate, cfg, device, stream, stages,
+                                            outs);
+    auto fail_all = [&](int32_t status, const char* text) {
+        for (uint64_t i = 0; i < n_tracks; i++) {
+            std::memset(&outs[i], 0, sizeof(outs[i]));
+            outs[i].status = status;
+            std::snprintf(outs[i].error_message, sizeof outs[i].error_message, "%s", text);
+            if (ov_req && overviews) {
+                std::memset(&overviews[i], 0, sizeof(overviews[i]));
+                overviews[i].status = status;
+            }
+            if (kt_req && timelines) {
+                std::memset(&timelines[i], 0, sizeof(timelines[i]));
+                timelines[i].status = status;
+            }
+        }
+        return status;
+    };
+    if (!cfg) return fail_all(SDSP_ERR_INVALID_INPUT, "Invalid input: no configuration");
+    if (ov_req) {
+        if (const char* why = overview_request_error(ov_req->columns, ov_req->frames_per_column, ov_req->low_max_hz,
+                                                     ov_req->mid_max_hz))
+            return fail_all(SDSP_ERR_INVALID_INPUT, why);
+        if (!overviews) return fail_all(SDSP_ERR_INVALID_INPUT, "Invalid input: overview request without an overviews array");
+    }
+    KtCall kc;
+    if (kt_req) {
+        if (const char* why = key_timeline_plan(kt_req->segment_seconds, kt_req->overlap_seconds, kt_req->segment_frames,
+                                                kt_req->hop_frames, kt_req->min_change_confidence, sample_rate,
+                                                kt_khop(*cfg), &kc.L, &kc.H))
+            return fail_all(SDSP_ERR_INVALID_INPUT, why);
+        if (!timelines)
+            return fail_all(SDSP_ERR_INVALID_INPUT, "Invalid input: key timeline request without a timelines array");
+        if (stages == SDSP_STAGES_BPM_ONLY)
+            return fail_all(SDSP_ERR_INVALID_INPUT, "Invalid input: key timeline request with SDSP_STAGES_BPM_ONLY (no key path)");
+        if (cfg->enable_key_beat_synchronous && !cfg->enable_key_log_frequency)
+            return fail_all(SDSP_ERR_NOT_IMPLEMENTED,
+                            "Not implemented: key timeline with beat-synchronous chroma (the rows are beats, not frames)");
+        kc.min_conf = kt_req->min_change_confidence;
+        kc.out = timelines;
+    }
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
+        return fail_all(SDSP_ERR_PROCESSING, "Processing error: no HIP device");
+    try {
+        return run_device(device, d_samples, offsets, lens, n_tracks, sample_rate, cfg, stream, outs, stages, nullptr,
+                          ov_req, overviews, kt_req ? &kc : nullptr);
+    } catch (const std::exception& e) {
+        std::fprintf(stderr, "sdsp_analyze_batch_device_requests: %s\n", e.what());
+        char text[256];
+        std::snprintf(text, sizeof text, "Processing error: %s", e.what());
+        return fail_all(SDSP_ERR_PROCESSING, text);
+    }
+}
+
+void sdsp_key_timeline_free(sdsp_key_timeline* t) {
+    if (!t) return;
+    std::free(t->segments);  // both arrays are one block (fill_key_timeline)
+    t->segments = nullptr;
+    t->changes = nullptr;
+    t->n_segments = t->n_changes = 0;
+}
+
+// The key timeline kernel and host logic over uploaded chroma rows (include/stratum_hip_debug.h).
+int32_t sdsp_debug_key_timeline(const float* host_chroma, const uint64_t* frames, uint64_t n_tracks,
+                                uint32_t sample_rate, const sdsp_config* cfg, const sdsp_key_timeline_request* req,
+                                sdsp_key_timeline* out, int32_t device) {
+    if (!frames || !cfg || !req || !out || n_tracks == 0 || n_tracks > (1u << 20)) return SDSP_ERR_INVALID_INPUT;
+    KtCall kc;
+    if (key_timeline_plan(req->segment_seconds, req->overlap_seconds, req->segment_frames, req->hop_frames,
+                          req->min_change_confidence, sample_rate, kt_khop(*cfg), &kc.L, &kc.H))
+        return SDSP_ERR_INVALID_INPUT;
+    kc.min_conf = req->min_change_confidence;
+    kc.out = out;
+    std::vector<uint64_t> kpfx(1, 0), spfx(1, 0);
+    for (uint64_t t = 0; t < n_tracks; t++) {
+        if (frames[t] > (1u << 24)) return SDSP_ERR_INVALID_INPUT;
+        kpfx.push_back(kpfx.back() + frames[t]);
+        spfx.push_back(spfx.back() + kt_segments(frames[t], kc.L, kc.H));
+    }
+    if (kpfx.back() > 0 && !host_chroma) return SDSP_ERR_INVALID_INPUT;
+    if (spfx.back() / KT_SEGS >= 0x7FFFFFFFull) return SDSP_ERR_INVALID_INPUT;
+    return run_stage_probe("sdsp_debug_key_timeline", device, [&](DeviceCtx& d) {
+        Ctx c(d);
+        c.pre = "D.";
+        const std::vector<float> rows(host_chroma, host_chroma + kpfx.back() * 12);
+        std::vector<float> tpl(576);
+        key_templates(tpl.data());
+        float* d_cs = c.up("kt_chroma", rows);
+        uint64_t* d_kpfx = c.up("kt_kpfx", kpfx);
+        uint64_t* d_spfx = c.up("kt_spfx", spfx);
+        float* d_tpl = c.up("kt_tpl", tpl);
+        KtSeg* d_out = c.dev<KtSeg>("kt_out", (size_t)std::max<uint64_t>(spfx.back(), 1));
+        launch_key_timeline(d_cs, d_kpfx, d_spfx, (int)n_tracks, spfx.back(), kc.L, kc.H, d_tpl, d_out, d.stream);
+        SDSP_HIP_CHECK(hipGetLastError());
+        const std::vector<KtSeg> seg = c.down(d_out, (size_t)spfx.back());
+        for (uint64_t t = 0; t < n_tracks; t++) {
+            TrackKt k;
+            k.on = true;
+            k.F = frames[t];
+            k.seg.assign(seg.begin() + (ptrdiff_t)spfx[(size_t)t], seg.begin() + (ptrdiff_t)spfx[(size_t)t + 1]);
+            fill_key_timeline(k, SDSP_OK, *cfg, sample_rate, kc, &out[t]);
+        }
+    });
 }
 
 void sdsp_overview_free(sdsp_overview* o) {

@@ -1,6 +1,7 @@
 // pipeline_key.hip — the key path of a sub-batch (stage E of pipeline.hip's overview): its launch
 // on the key and vote streams, the spectrogram conditioning and chroma, the join (late by default),
 // the exact reruns of near-decision tracks and the beat-synchronous re-vote.
+#include "key_timeline_plan.hpp"
 #include "pipeline.hpp"
 
 namespace sdsp {
@@ -84,6 +85,18 @@ KeyLaunch Pipeline::launch_key(const float* d_samples, const TempoPassIn& bin) {
         t.d_w = d_w;
         t.d_sscr = d_sscr;
     }
+    // the key timeline's segment prefix (a request only): uploaded on the main stream like the templates
+    uint64_t* d_kspfx = nullptr;
+    if (kt_out_) {
+        KeyTimelineOut& o = kl.ktl;
+        for (int k = 0; k < NK; k++) {
+            o.frames.push_back(t.kpfx[(size_t)k + 1] - t.kpfx[(size_t)k]);
+            o.spfx.push_back(o.spfx.back() + kt_segments(o.frames.back(), kt_L_, kt_H_));
+        }
+        if (o.spfx.back() / KT_SEGS >= 0x7FFFFFFFull) throw HipError("key timeline: too many segments for one launch");
+        d_kspfx = c_.up(EP + "kt_spfx", o.spfx);
+        o.d_out = c_.dev<KtSeg>(EP + "kt_out", (size_t)std::max<uint64_t>(o.spfx.back(), 1));
+    }
     // the template upload above is on the main stream too; the vote follows the chroma on st2
     kt.mark(8);
     kt.mark(11, st2);
@@ -95,6 +108,14 @@ KeyLaunch Pipeline::launch_key(const float* d_samples, const TempoPassIn& bin) {
     launch_key_vote(kl.d_kid, NK, t.d_kpfx, kc.d_chroma, kc.d_energy, d_cs, d_w, d_sscr, d_kseg, t.d_tpl, t.kp,
                     kl.d_kout, st3, kl.d_kdbg, kc.d_edel, d_wdel, last_sub_ || nested_ || key_only_);
     SDSP_HIP_CHECK(hipGetLastError());
+    // The key timeline (include/stratum_hip.h) reads the rows the vote just smoothed, behind it on the
+    // vote stream and before ev[2], so both joins wait for it; the next sub-batch's vote, which
+    // rewrites E.chroma_s, follows in stream order.  rerun_tail does not touch it: the chroma rows are
+    // exact on the band path (only the frame energies are not), and the timeline uses no energies.
+    if (d_kspfx) {
+        launch_key_timeline(d_cs, t.d_kpfx, d_kspfx, NK, kl.ktl.spfx.back(), kt_L_, kt_H_, t.d_tpl, kl.ktl.d_out, st3);
+        SDSP_HIP_CHECK(hipGetLastError());
+    }
     kt.mark(2, st3);
     if (!nested_) SDSP_HIP_CHECK(hipEventRecord(d_.vote_done, st3));
     times_.stft8192_launches += 1;
@@ -244,15 +265,38 @@ std::vector<KeyOut> Pipeline::join_key(const float* d_samples, const std::vector
         key_pending_->kt = std::move(kl.kt);
         key_pending_->d_kout = kl.d_kout;
         for (int i : kl.K) key_pending_->at.push_back(f.slot[(size_t)i]);
+        for (int i : kl.K) key_pending_->first.push_back(f.ts[(size_t)f.R[(size_t)i]]);
+        key_pending_->ktl = std::move(kl.ktl);
         key_pending_->tail = std::move(kl.tail);
     } else if (NK > 0) {  // join the key stream
         SDSP_HIP_CHECK(hipStreamWaitEvent(d_.stream, kl.kt->ev[2], 0));
         kout = c_.down(kl.d_kout, NK);
+        if (kt_out_) {
+            std::vector<size_t> at;
+            std::vector<uint64_t> first;
+            for (int i : kl.K) at.push_back(f.slot[(size_t)i]), first.push_back(f.ts[(size_t)f.R[(size_t)i]]);
+            key_timeline_results(kl.ktl, at, first);
+        }
         htr("E join");
         times_.stft8192_ms += kl.kt->ms(0, 1);
         times_.key_ms += kl.kt->ms(1, 2);
     }
     return kout;
+}
+
+// A joined sub-batch's key timeline segments (downloaded with its key results) into the call's
+// per-track entries: `at` the result slot and `first` the trim start of each key track.
+void Pipeline::key_timeline_results(const KeyTimelineOut& ktl, const std::vector<size_t>& at,
+                                    const std::vector<uint64_t>& first) {
+    if (!kt_out_ || ktl.frames.empty()) return;
+    const std::vector<KtSeg> seg = c_.down(ktl.d_out, (size_t)ktl.spfx.back());
+    for (size_t k = 0; k < at.size(); k++) {
+        TrackKt& o = (*kt_out_)[at[k]];
+        o.on = true;
+        o.F = ktl.frames[k];
+        o.first = first[k];
+        o.seg.assign(seg.begin() + (ptrdiff_t)ktl.spfx[k], seg.begin() + (ptrdiff_t)ktl.spfx[k + 1]);
+    }
 }
 
 // The pending key results (the previous sub-batch's, or at the end of run() the last one's) into
@@ -263,6 +307,7 @@ std::vector<size_t> Pipeline::finish_key(std::vector<TrackRes>& res, bool keep_t
     std::unique_ptr<KeyPending> kp = std::move(key_pending_);
     SDSP_HIP_CHECK(hipStreamWaitEvent(d_.stream, kp->kt->ev[2], 0));
     const std::vector<KeyOut> kout = c_.down(kp->d_kout, kp->at.size());
+    key_timeline_results(kp->ktl, kp->at, kp->first);
     for (size_t k = 0; k < kp->at.size(); k++) {
         TrackRes& r = res[kp->at[k]];
         const KeyOut& ko = kout[k];

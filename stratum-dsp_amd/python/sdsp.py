@@ -16,7 +16,8 @@ import numpy as np
 
 from sdsp_abi import (ERROR_NAMES, FLAG_NAMES, SdspAudioDecodeStats, SdspConfidence, SdspConfig, SdspDebugOverviewTimes,
                       SdspDecodeStats, SdspFlacDecodeStats, SdspOverview, SdspOverviewRequest, SdspResult,
-                      SdspStageTimes, OVERVIEW_ARRAYS, result_to_dict)
+                      SdspStageTimes, OVERVIEW_ARRAYS, result_to_dict, SdspKeyChange, SdspKeySegment, SdspKeyTimeline,
+                      SdspKeyTimelineRequest)
 
 PKG = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LIB_PATH = os.environ.get("SDSP_LIB_PATH") or os.path.join(PKG, "lib", "libstratum_hip.so")  # override: layout/ablation builds
@@ -76,6 +77,17 @@ def _load(path):
                                                          C.POINTER(SdspResult), C.POINTER(SdspOverviewRequest),
                                                          C.POINTER(SdspOverview)]
         L.sdsp_analyze_batch_device_overview.restype = C.c_int32
+        L.sdsp_analyze_batch_device_requests.argtypes = [C.c_void_p, u64p, u64p, C.c_uint64, C.c_uint32,
+                                                         C.POINTER(SdspConfig), C.c_int32, C.c_void_p, C.c_int32,
+                                                         C.POINTER(SdspResult), C.POINTER(SdspOverviewRequest),
+                                                         C.POINTER(SdspOverview), C.POINTER(SdspKeyTimelineRequest),
+                                                         C.POINTER(SdspKeyTimeline)]
+        L.sdsp_analyze_batch_device_requests.restype = C.c_int32
+        L.sdsp_key_timeline_free.argtypes = [C.POINTER(SdspKeyTimeline)]
+        L.sdsp_key_timeline_free.restype = None
+        L.sdsp_debug_key_timeline.argtypes = [C.POINTER(C.c_float), u64p, C.c_uint64, C.c_uint32, C.POINTER(SdspConfig),
+                                              C.POINTER(SdspKeyTimelineRequest), C.POINTER(SdspKeyTimeline), C.c_int32]
+        L.sdsp_debug_key_timeline.restype = C.c_int32
         L.sdsp_overview_free.argtypes = [C.POINTER(SdspOverview)]
         L.sdsp_overview_free.restype = None
         L.sdsp_debug_last_overview_times.argtypes = [C.c_int32, C.POINTER(SdspDebugOverviewTimes)]
@@ -597,6 +609,92 @@ def analyze_batch_device_overview(d_ptr, offsets, lens, sample_rate=44100, confi
             overviews.append(overview_to_dict(ovs[i]))
             lib().sdsp_overview_free(C.byref(ovs[i]))
     return ResultBatch(outs, n), overviews
+
+
+KEY_SEGMENT_FIELDS = ("start_frame", "timestamp", "key", "confidence", "clarity", "top_keys", "top_scores")
+KEY_CHANGE_FIELDS = ("segment", "timestamp", "from_key", "to_key", "confidence")
+
+
+def _records(ptr, n, ctype):
+    """n library-owned structs as a numpy record array (a copy)."""
+    dt = np.dtype(ctype)
+    if not n or not ptr:
+        return np.zeros(0, dt)
+    return np.frombuffer(C.string_at(ptr, n * C.sizeof(ctype)), dtype=dt).copy()
+
+
+def key_timeline_to_dict(t):
+    """One sdsp_key_timeline: its scalar fields, and `segments` / `changes` as dicts of numpy
+    arrays, one per field (KEY_SEGMENT_FIELDS, KEY_CHANGE_FIELDS; top_keys / top_scores (S, 3))."""
+    d = {k: int(getattr(t, k)) for k in ("n_segments", "n_changes", "n_frames", "first_sample", "segment_frames",
+                                         "hop_frames", "frame_size", "hop_size", "primary_key", "primary_count", "status")}
+    d["primary_confidence"] = np.float32(t.primary_confidence)
+    seg = _records(t.segments, d["n_segments"], SdspKeySegment)
+    chg = _records(t.changes, d["n_changes"], SdspKeyChange)
+    d["segments"] = {k: seg[k].copy() for k in KEY_SEGMENT_FIELDS}
+    d["changes"] = {k: chg[k].copy() for k in KEY_CHANGE_FIELDS}
+    return d
+
+
+def key_timeline_request(segment_seconds=0.0, overlap_seconds=0.0, segment_frames=0, hop_frames=0,
+                         min_change_confidence=-1.0):
+    """An sdsp_key_timeline_request: segments of segment_seconds overlapping by overlap_seconds, or
+    of segment_frames key frames every hop_frames (exactly one form).  min_change_confidence: the
+    reference's fixed value is 0.2; a negative one (the default here) reports every change."""
+    return SdspKeyTimelineRequest(segment_seconds, overlap_seconds, segment_frames, hop_frames, min_change_confidence)
+
+
+def analyze_batch_device_requests(d_ptr, offsets, lens, sample_rate=44100, config=None, device=0, stream=None,
+                                  stages=STAGES_FULL, overview=None, key_timeline=None):
+    """sdsp_analyze_batch_device_requests: analyze_batch_device(raw=True) with both optional
+    requests, an SdspOverviewRequest and an SdspKeyTimelineRequest (key_timeline_request()); None
+    passes NULL.  Returns (ResultBatch, overviews, timelines): overviews as
+    analyze_batch_device_overview returns them, timelines[i] a key_timeline_to_dict(); each [] without
+    its request.  Raises AnalysisError when the call as a whole fails (a refused request)."""
+    offs = np.ascontiguousarray(offsets, dtype=np.uint64)
+    ln = np.ascontiguousarray(lens, dtype=np.uint64)
+    n = ln.size
+    outs = (SdspResult * n)()
+    ovs = (SdspOverview * max(n, 1))() if overview is not None else None
+    kts = (SdspKeyTimeline * max(n, 1))() if key_timeline is not None else None
+    cfg = config if config is not None else default_config()
+    _schedule_from_env()
+    u64p = C.POINTER(C.c_uint64)
+    st = lib().sdsp_analyze_batch_device_requests(C.c_void_p(d_ptr), offs.ctypes.data_as(u64p), ln.ctypes.data_as(u64p),
+                                                  n, sample_rate, C.byref(cfg), device, C.c_void_p(stream or 0), stages,
+                                                  outs, C.byref(overview) if overview is not None else None, ovs,
+                                                  C.byref(key_timeline) if key_timeline is not None else None, kts)
+    if st != 0:
+        raise AnalysisError(st, _batch_error(outs, n, "device batch failed"))
+    overviews, timelines = [], []
+    for i in range(n):
+        if ovs is not None:
+            overviews.append(overview_to_dict(ovs[i]))
+            lib().sdsp_overview_free(C.byref(ovs[i]))
+        if kts is not None:
+            timelines.append(key_timeline_to_dict(kts[i]))
+            lib().sdsp_key_timeline_free(C.byref(kts[i]))
+    return ResultBatch(outs, n), overviews, timelines
+
+
+def debug_key_timeline(chroma_list, request, sample_rate=44100, config=None, device=0):
+    """sdsp_debug_key_timeline: the timeline kernel and host logic over host chroma rows, one (F, 12)
+    array per track (F = 0 allowed), taken as the smoothed rows of the definition.  Returns one
+    key_timeline_to_dict() per track."""
+    cfg = config if config is not None else default_config()
+    rows = [np.ascontiguousarray(c, np.float32).reshape(-1, 12) for c in chroma_list]
+    frames = np.array([r.shape[0] for r in rows], np.uint64)
+    flat = np.ascontiguousarray(np.concatenate(rows, axis=0) if rows else np.zeros((0, 12), np.float32))
+    out = (SdspKeyTimeline * max(len(rows), 1))()
+    st = lib().sdsp_debug_key_timeline(_fp(flat), frames.ctypes.data_as(C.POINTER(C.c_uint64)), len(rows), sample_rate,
+                                       C.byref(cfg), C.byref(request), out, device)
+    if st != 0:
+        raise AnalysisError(st, "debug_key_timeline failed")
+    res = []
+    for i in range(len(rows)):
+        res.append(key_timeline_to_dict(out[i]))
+        lib().sdsp_key_timeline_free(C.byref(out[i]))
+    return res
 
 
 def overview_times(device=0):

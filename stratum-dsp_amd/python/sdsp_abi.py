@@ -336,6 +336,65 @@ class SdspDebugOverviewTimes(C.Structure):
     ]
 
 
+class SdspKeyTimelineRequest(C.Structure):
+    """sdsp_key_timeline_request: the seconds form or the frames form, exactly one."""
+
+    _fields_ = [
+        ("segment_seconds", f32),
+        ("overlap_seconds", f32),
+        ("segment_frames", u32),
+        ("hop_frames", u32),
+        ("min_change_confidence", f32),
+    ]
+
+
+class SdspKeySegment(C.Structure):
+    """sdsp_key_segment: detect_key over one segment of the smoothed chroma rows."""
+
+    _fields_ = [
+        ("start_frame", u64),
+        ("timestamp", f32),
+        ("key", C.c_int32),
+        ("confidence", f32),
+        ("clarity", f32),
+        ("top_keys", C.c_int32 * 3),
+        ("top_scores", f32 * 3),
+    ]
+
+
+class SdspKeyChange(C.Structure):
+    """sdsp_key_change: a reported change between segments segment - 1 and segment."""
+
+    _fields_ = [
+        ("segment", u64),
+        ("timestamp", f32),
+        ("from_key", C.c_int32),
+        ("to_key", C.c_int32),
+        ("confidence", f32),
+    ]
+
+
+class SdspKeyTimeline(C.Structure):
+    """sdsp_key_timeline: one track's segments, primary key and changes (library-owned arrays)."""
+
+    _fields_ = [
+        ("n_segments", u64),
+        ("n_changes", u64),
+        ("n_frames", u64),
+        ("first_sample", u64),
+        ("segment_frames", u32),
+        ("hop_frames", u32),
+        ("frame_size", u32),
+        ("hop_size", u32),
+        ("primary_key", C.c_int32),
+        ("primary_confidence", f32),
+        ("primary_count", u64),
+        ("segments", C.POINTER(SdspKeySegment)),
+        ("changes", C.POINTER(SdspKeyChange)),
+        ("status", C.c_int32),
+    ]
+
+
 OVERVIEW_ARRAYS = ("smin", "smax", "low", "mid", "high")
 
 
