@@ -47,15 +47,33 @@ typedef const __attribute__((address_space(4))) MelChunk* ConstMC;
 // KK > 0: compile-time SuperFlux half width (the default 4) -- the previous frame's logs for
 // the chunk's windows are read once into registers and every bin's window max is taken from
 // them; KK = 0: runtime P.K with the per-bin window loop.
-template <int CW, int W, int KK>
-__global__ __launch_bounds__(FT_FRAMES) __attribute__((amdgpu_waves_per_eu(KK > 0 ? 3 : 1))) void k_features(const RowMap rm,
-                                                        const uint64_t* __restrict__ frame_pfx,
-                                                        const uint64_t* __restrict__ tile_pfx, int T, FeatParams P,
-                                                        const MelPlan* __restrict__ mel, float* __restrict__ E,
-                                                        float* __restrict__ H, float* __restrict__ SFX,
-                                                        float* __restrict__ SFO, float* __restrict__ MEL,
-                                                        uint64_t total) {
+//
+// The escalation passes (Pipeline::escalate) run the same walk with two compile-time switches:
+// FLUX = false drops the spectral flux (SFO and everything that only feeds it: only the base pass's
+// SFO is ever read), and X4 = true makes the hop-256 walk also produce the hop-1024 pass's SFX.
+// Hop-1024 frame j is hop-256 frame 4 j, so its previous frame is the row of lane - 4: each wave
+// then has 4 helper rows (60 frames per wave, FT_STEP_X4 per workgroup).  A lane's window maxima Wm
+// are taken over the row of lane - 1, so the maxima over the row of lane - 4 (Wm4) are lane - 3's
+// Wm, fetched across lanes (ds_bpermute) per chunk; only the band-edge bins of the general walk
+// read that row's logs from LDS.  A second set of SuperFlux accumulators is folded in the same bin
+// order, with the same band-edge clipping and the same cur / flush runs as the hop-1024 launch's own.
+struct FeatX4 {
+    const uint64_t* frame_pfx4;  // the hop-1024 pass's frame prefix over the same tracks
+    float* SFX4;                 // its SFX[v][total4]
+    uint64_t total4;
+};
+
+template <int CW, int W, int KK, bool FLUX, bool X4>
+__device__ __forceinline__ void features_body(const RowMap rm, const uint64_t* __restrict__ frame_pfx,
+                                              const uint64_t* __restrict__ tile_pfx, int T, FeatParams P,
+                                              const MelPlan* __restrict__ mel, float* __restrict__ E,
+                                              float* __restrict__ H, float* __restrict__ SFX,
+                                              float* __restrict__ SFO, float* __restrict__ MEL, uint64_t total,
+                                              const FeatX4 x4) {
     static_assert((W & (W - 1)) == 0, "W must be a power of two");
+    static_assert(!X4 || (KK > 0 && 2 * KK == CW), "the fused hop-1024 SuperFlux is built for the split window maxima");
+    constexpr int HR = X4 ? 4 : 1;  // helper rows per wave
+    constexpr int WF = 64 - HR;     // frames per wave
     constexpr int ROWS = FT_FRAMES;  // row i: lane i's frame (each wave stages its own 64 rows)
     constexpr int LS = W + 1;
     // slot s of row r: {magnitude, ln(1 + max(magnitude, 0))} side by side, so the walk reads both
@@ -73,14 +91,14 @@ __global__ __launch_bounds__(FT_FRAMES) __attribute__((amdgpu_waves_per_eu(KK > 
     const uint64_t gb = blockIdx.x;
     const int trk = find_track(tile_pfx, T, gb);
     const int64_t F = (int64_t)(frame_pfx[trk + 1] - frame_pfx[trk]);
-    const int64_t f0 = (int64_t)(gb - tile_pfx[trk]) * FT_STEP;
+    const int64_t f0 = (int64_t)(gb - tile_pfx[trk]) * (X4 ? FT_STEP_X4 : FT_STEP);
     const uint64_t g0 = frame_pfx[trk];
     const int i = threadIdx.x;
-    const bool helper = (i & 63) == 0;
+    const bool helper = (i & 63) < HR;
     const int ro = i;  // this lane's LDS row
-    const int64_t f = f0 - 1 + 63 * (i >> 6) + (i & 63);
+    const int64_t f = f0 - HR + WF * (i >> 6) + (i & 63);
     const bool own_ok = f >= 0 && f < F;
-    const bool valid = !helper && f < F;  // ro >= 1 here, so f >= 0
+    const bool valid = !helper && f < F;  // ro >= HR here, so f >= 0
     const bool has_prev = valid && f >= 1;
     const int K = KK > 0 ? KK : P.K, B = P.B;
     const uint64_t g = g0 + (uint64_t)f;
@@ -93,6 +111,7 @@ __global__ __launch_bounds__(FT_FRAMES) __attribute__((amdgpu_waves_per_eu(KK > 
     // band, and the band's SuperFlux term is the full band's (same product) except within K
     // bins of a band edge.
     float eb = 0.0f, hb = 0.0f, sb = 0.0f;
+    float sx4[4] = {0, 0, 0, 0}, sb4 = 0.0f;  // X4: the hop-1024 SuperFlux sums
     int cur = 0;
     auto band_of = [&](int b) {
         int v = 0;
@@ -102,10 +121,10 @@ __global__ __launch_bounds__(FT_FRAMES) __attribute__((amdgpu_waves_per_eu(KK > 
         return v;
     };
     auto flush = [&]() {
-        if (cur == 1) e[1] = eb, h[1] = hb, sx[1] = sb;
-        else if (cur == 2) e[2] = eb, h[2] = hb, sx[2] = sb;
-        else if (cur == 3) e[3] = eb, h[3] = hb, sx[3] = sb;
-        eb = hb = sb = 0.0f;
+        if (cur == 1) e[1] = eb, h[1] = hb, sx[1] = sb, sx4[1] = sb4;
+        else if (cur == 2) e[2] = eb, h[2] = hb, sx[2] = sb, sx4[2] = sb4;
+        else if (cur == 3) e[3] = eb, h[3] = hb, sx[3] = sb, sx4[3] = sb4;
+        eb = hb = sb = sb4 = 0.0f;
     };
     float accA = 0.0f, accB = 0.0f;
     int mA = 0;
@@ -127,7 +146,7 @@ __global__ __launch_bounds__(FT_FRAMES) __attribute__((amdgpu_waves_per_eu(KK > 
         const uint64_t r = row_of(fr, &odd);
         return odd ? rm.fmaxB[r] : rm.fmaxA[r];
     };
-    const float mx_c = own_ok ? fmax_of(f) : 0.0f;
+    const float mx_c = FLUX && own_ok ? fmax_of(f) : 0.0f;
     const bool cn = mx_c > EPS;
     // X / max by one correctly rounded reciprocal per frame and an FMA correction per bin:
     // q0 = m yr, q = q0 + (m - max q0) yr is the correctly rounded m / max for normal operands whose
@@ -171,7 +190,7 @@ __global__ __launch_bounds__(FT_FRAMES) __attribute__((amdgpu_waves_per_eu(KK > 
     // program order.  (The helper row duplicates the previous wave's last row: 1/64 extra loads.)
     const int lane = i & 63, wrow = i & ~63;
     const int sub = lane / CW, jj = lane % CW;
-    const int64_t fw = f0 - 1 + 63 * (i >> 6);  // frame of the wave's row 0
+    const int64_t fw = f0 - HR + WF * (i >> 6);  // frame of the wave's row 0
 
     // stage bins [b0, b0+CW) (columns beyond B or rows outside the track read as 0); the loads
     // of the next step are in flight while the current step is walked
@@ -271,6 +290,18 @@ __global__ __launch_bounds__(FT_FRAMES) __attribute__((amdgpu_waves_per_eu(KK > 
                 for (int q = 0; q < CW; q++) Wm[q] = max_bnn(suf[q], pre[q]);
             }
         }
+        // X4: the same window maxima of the hop-1024 frame's previous frame, the row of lane - 4.
+        // Lane l's Wm is taken over the row of lane l - 1, so those are lane l - 3's Wm: one
+        // cross-lane read per bin instead of a second register window and its maxima (every lane
+        // computes Wm; the helper lanes' own Wm4 is never used)
+        const int rp4 = lane >= 4 ? ro - 4 : ro;
+        float Wm4[X4 ? CW : 1];
+        if constexpr (X4) {
+            const int src = ((lane - 3) & 63) * 4;
+#pragma unroll
+            for (int q = 0; q < CW; q++)
+                Wm4[q] = __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute(src, __builtin_bit_cast(int, Wm[q])));
+        }
         if constexpr (VHK) {
             // fast chunk (most bins: above the mel and sub-band ranges, or inside one band away
             // from its edges): the same per-bin arithmetic with the band and mel bookkeeping
@@ -316,11 +347,13 @@ __global__ __launch_bounds__(FT_FRAMES) __attribute__((amdgpu_waves_per_eu(KK > 
                         e[0] += ee;
                         h[0] += hh;
                         const float lc = ml.y;
-                        const float cv = quot(m);
-                        const float pv = __builtin_bit_cast(
-                            float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, cv), 0x138, 0xf, 0xf, true));
-                        const float d = max_bnn(cv - pv, 0.0f);
-                        so += d * d;
+                        if constexpr (FLUX) {
+                            const float cv = quot(m);
+                            const float pv = __builtin_bit_cast(
+                                float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, cv), 0x138, 0xf, 0xf, true));
+                            const float d = max_bnn(cv - pv, 0.0f);
+                            so += d * d;
+                        }
                         const float df = max_bnn(lc - Wm[j], 0.0f);
                         const float df2 = df * df;
                         sx[0] += df2;
@@ -328,6 +361,12 @@ __global__ __launch_bounds__(FT_FRAMES) __attribute__((amdgpu_waves_per_eu(KK > 
                             eb += ee;
                             hb += hh;
                             sb += df2;
+                        }
+                        if constexpr (X4) {
+                            const float d4 = max_bnn(lc - Wm4[j], 0.0f);
+                            const float d42 = d4 * d4;
+                            sx4[0] += d42;
+                            if (!NOBAND && vbc) sb4 += d42;
                         }
                         if constexpr (MEL) {
                             const uint32_t pb = mc.bits >> (4 * j);
@@ -363,7 +402,7 @@ __global__ __launch_bounds__(FT_FRAMES) __attribute__((amdgpu_waves_per_eu(KK > 
                     walk(std::false_type{}, std::false_type{}, std::true_type{});
                 else
                     walk(std::false_type{}, std::false_type{}, std::false_type{});
-                quot_redo(c0, CW, so_start);
+                if constexpr (FLUX) quot_redo(c0, CW, so_start);
                 continue;
             }
         }
@@ -393,7 +432,7 @@ __global__ __launch_bounds__(FT_FRAMES) __attribute__((amdgpu_waves_per_eu(KK > 
             const float lc = ml.y;
             // X/max of this lane's frame, and of the previous frame from lane - 1 (its frame is
             // f - 1 for every lane that reads it: lanes 1-63; the helper's value is unused)
-            const float cv = quot(m);
+            const float cv = FLUX ? quot(m) : 0.0f;
             const float pv = __builtin_bit_cast(
                 float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, cv), 0x138 /* wave_shr:1 */, 0xf, 0xf, true));
             if (P.n_mels > 0) {
@@ -418,8 +457,10 @@ __global__ __launch_bounds__(FT_FRAMES) __attribute__((amdgpu_waves_per_eu(KK > 
                 }
             }
             {
-                const float d = max_bnn(cv - pv, 0.0f);
-                so += d * d;
+                if constexpr (FLUX) {
+                    const float d = max_bnn(cv - pv, 0.0f);
+                    so += d * d;
+                }
                 // SuperFlux, full band window [b-K, b+K] clipped to [0, B).  Every L >= +0 and
                 // max is an exact selection, so the max over the register window (entries
                 // outside [0, B) are +0) equals the reference's max from 0 over the clipped range.
@@ -459,9 +500,32 @@ __global__ __launch_bounds__(FT_FRAMES) __attribute__((amdgpu_waves_per_eu(KK > 
                         sb += df2;
                     }
                 }
+                if constexpr (X4) {
+                    // the hop-1024 term of the same bin: the window of the row of lane - 4, clipped
+                    // alike (read per use: these chunks are the few at a band edge or past B)
+                    const float d4 = max_bnn(lc - Wm4[j], 0.0f);
+                    const float d42 = d4 * d4;
+                    sx4[0] += d42;
+                    if (vb) {
+                        const int bsv = P.bs[vb], bev = P.be[vb];
+                        if (lo < bsv || hi > bev) {
+                            const int lb = lo < bsv ? bsv : lo;
+                            const int hbd = hi > bev ? bev : hi;
+                            float pmb = 0.0f;
+#pragma unroll
+                            for (int q = 0; q <= 2 * KK; q++)
+                                if (b - KK + q >= lb && b - KK + q < hbd)
+                                    pmb = max_bnn(pmb, ML[rp4][(b - KK + q) & (W - 1)].y);
+                            const float db = max_bnn(lc - pmb, 0.0f);
+                            sb4 += db * db;
+                        } else {
+                            sb4 += d42;
+                        }
+                    }
+                }
             }
         }
-        quot_redo(c0, nb, so_start);
+        if constexpr (FLUX) quot_redo(c0, nb, so_start);
     }
     flush();
     if (!valid) return;
@@ -477,10 +541,63 @@ __global__ __launch_bounds__(FT_FRAMES) __attribute__((amdgpu_waves_per_eu(KK > 
     }
     if (has_prev) {
         const uint64_t gp = g - 1;  // pair (t-1, t) stored at t-1
-        SFO[gp] = __builtin_sqrtf(so);
+        if constexpr (FLUX) SFO[gp] = __builtin_sqrtf(so);
 #pragma unroll
         for (int v = 0; v < 4; v++) SFX[(uint64_t)v * total + gp] = __builtin_sqrtf(sx[v]);
     }
+    if constexpr (X4) {
+        // hop-1024 frame f / 4 with a previous one; pair (t-1, t) stored at t-1
+        if (f >= 4 && (f & 3) == 0) {
+            const uint64_t g4 = x4.frame_pfx4[trk] + (uint64_t)(f >> 2) - 1;
+#pragma unroll
+            for (int v = 0; v < 4; v++) x4.SFX4[(uint64_t)v * x4.total4 + g4] = __builtin_sqrtf(sx4[v]);
+        }
+    }
+}
+
+template <int CW, int W, int KK>
+__global__ __launch_bounds__(FT_FRAMES) __attribute__((amdgpu_waves_per_eu(KK > 0 ? 3 : 1))) void k_features(const RowMap rm,
+                                                        const uint64_t* __restrict__ frame_pfx,
+                                                        const uint64_t* __restrict__ tile_pfx, int T, FeatParams P,
+                                                        const MelPlan* __restrict__ mel, float* __restrict__ E,
+                                                        float* __restrict__ H, float* __restrict__ SFX,
+                                                        float* __restrict__ SFO, float* __restrict__ MEL,
+                                                        uint64_t total) {
+    features_body<CW, W, KK, true, false>(rm, frame_pfx, tile_pfx, T, P, mel, E, H, SFX, SFO, MEL, total, FeatX4{});
+}
+
+// the escalation passes' walk (<8, 16, 4> only): no spectral flux; X4: also the hop-1024 SFX
+template <bool X4>
+__global__ __launch_bounds__(FT_FRAMES) __attribute__((amdgpu_waves_per_eu(3))) void k_features_esc(
+    const RowMap rm, const uint64_t* __restrict__ frame_pfx, const uint64_t* __restrict__ tile_pfx, int T, FeatParams P,
+    const MelPlan* __restrict__ mel, float* __restrict__ E, float* __restrict__ H, float* __restrict__ SFX,
+    float* __restrict__ MEL, uint64_t total, FeatX4 x4) {
+    features_body<8, 16, 4, false, X4>(rm, frame_pfx, tile_pfx, T, P, mel, E, H, SFX, nullptr, MEL, total, x4);
+}
+
+// E, H (4 variants) and MEL (n_mels rows) of the hop-1024 pass from the hop-512 pass of the same
+// tracks: hop-1024 frame j is hop-512 frame 2 j (the same row, the same folds), so its values are
+// copied.  One workgroup row per (track, 256 frames); blockIdx.y = the array row.
+__global__ __launch_bounds__(256) void k_features_gather2(const uint64_t* __restrict__ frame_pfx4,
+                                                          const uint64_t* __restrict__ row0, int T,
+                                                          const uint64_t* __restrict__ tile_pfx,
+                                                          const float* __restrict__ E2, const float* __restrict__ H2,
+                                                          const float* __restrict__ MEL2, uint64_t total2,
+                                                          float* __restrict__ E4, float* __restrict__ H4,
+                                                          float* __restrict__ MEL4, uint64_t total4) {
+    const uint64_t gb = blockIdx.x;
+    const int trk = find_track(tile_pfx, T, gb);
+    const uint64_t F = frame_pfx4[trk + 1] - frame_pfx4[trk];
+    const uint64_t j = (gb - tile_pfx[trk]) * 256u + threadIdx.x;
+    if (j >= F) return;
+    const uint64_t src = row0[trk] + 2 * j, dst = frame_pfx4[trk] + j;
+    const int r = blockIdx.y;
+    if (r < 4)
+        E4[(uint64_t)r * total4 + dst] = E2[(uint64_t)r * total2 + src];
+    else if (r < 8)
+        H4[(uint64_t)(r - 4) * total4 + dst] = H2[(uint64_t)(r - 4) * total2 + src];
+    else
+        MEL4[(uint64_t)(r - 8) * total4 + dst] = MEL2[(uint64_t)(r - 8) * total2 + src];
 }
 
 void launch_features(const RowMap& mags, const uint64_t* frame_pfx, const uint64_t* tile_pfx,
@@ -499,6 +616,30 @@ void launch_features(const RowMap& mags, const uint64_t* frame_pfx, const uint64
     else
         hipLaunchKernelGGL((k_features<16, 32, 0>), dim3((unsigned)n_tiles), dim3(FT_FRAMES), 0, st, mags,
                            frame_pfx, tile_pfx, T, P, mel, E, H, SFX, SFO, MEL, total);
+}
+
+
+void launch_features_esc(const RowMap& mags, const uint64_t* frame_pfx, const uint64_t* tile_pfx, int T, uint64_t n_tiles,
+                         const FeatParams& P, const MelPlan* mel, float* E, float* H, float* SFX, float* MEL, uint64_t total,
+                         const uint64_t* frame_pfx4, float* SFX4, uint64_t total4, hipStream_t st) {
+    if (n_tiles == 0) return;
+    if (total >= (1ull << 30)) throw std::runtime_error("launch_features_esc: too many frames for one launch");
+    if (P.K != 4) throw std::runtime_error("launch_features_esc: built for a SuperFlux half width of 4");
+    const FeatX4 x4{frame_pfx4, SFX4, total4};
+    if (SFX4)
+        hipLaunchKernelGGL(k_features_esc<true>, dim3((unsigned)n_tiles), dim3(FT_FRAMES), 0, st, mags, frame_pfx,
+                           tile_pfx, T, P, mel, E, H, SFX, MEL, total, x4);
+    else
+        hipLaunchKernelGGL(k_features_esc<false>, dim3((unsigned)n_tiles), dim3(FT_FRAMES), 0, st, mags, frame_pfx,
+                           tile_pfx, T, P, mel, E, H, SFX, MEL, total, x4);
+}
+
+void launch_features_gather2(const uint64_t* frame_pfx4, const uint64_t* row0, int T, const uint64_t* tile_pfx,
+                             uint64_t n_tiles, int n_mels, const float* E2, const float* H2, const float* MEL2,
+                             uint64_t total2, float* E4, float* H4, float* MEL4, uint64_t total4, hipStream_t st) {
+    if (n_tiles == 0) return;
+    hipLaunchKernelGGL(k_features_gather2, dim3((unsigned)n_tiles, (unsigned)(8 + n_mels)), dim3(256), 0, st, frame_pfx4,
+                       row0, T, tile_pfx, E2, H2, MEL2, total2, E4, H4, MEL4, total4);
 }
 
 }  // namespace sdsp

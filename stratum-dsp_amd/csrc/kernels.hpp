@@ -52,6 +52,9 @@ constexpr int FT_FRAMES = 256;
 // frames per k_features tile: lane 0 of each wave is a helper that computes the normalised
 // magnitudes of the frame before the wave's first (k_features.hip)
 constexpr int FT_STEP = FT_FRAMES - FT_FRAMES / 64;
+// the hop-256 escalation launch that also folds the hop-1024 SuperFlux (launch_features_esc with
+// SFX4): 4 helper lanes per wave, the frames before the wave's first back to the hop-1024 previous
+constexpr int FT_STEP_X4 = FT_FRAMES - 4 * (FT_FRAMES / 64);
 // Where k_features finds frame f of item k: row (f even ? A : B) r0 + (f >> 1) * step, with
 // rB0 = rowB0[k] or rowA0[k] + offB.  Compact spectrogram: A = B, rowA0 = frame prefix, offB = 1,
 // steps 2.  The escalation hops reuse the hop-512 rows: hop 1024 frame v is hop-512 frame 2v;
@@ -316,6 +319,17 @@ void launch_consensus(const uint32_t* energy, const uint64_t* e_off, const int* 
 void launch_features(const RowMap& mags, const uint64_t* frame_pfx, const uint64_t* tile_pfx,
                      int T, uint64_t n_tiles, const FeatParams& P, const MelPlan* mel, float* E, float* H, float* SFX,
                      float* SFO, float* MEL, uint64_t total, hipStream_t st);
+// the escalation passes' features (P.K = 4 only): no SFO.  With SFX4 the launch is a hop-256 pass
+// whose tiles step FT_STEP_X4 frames and which also stores the hop-1024 pass's SFX (frame prefix
+// frame_pfx4 over the same tracks, total4 frames); without, tiles step FT_STEP as launch_features'
+void launch_features_esc(const RowMap& mags, const uint64_t* frame_pfx, const uint64_t* tile_pfx, int T, uint64_t n_tiles,
+                         const FeatParams& P, const MelPlan* mel, float* E, float* H, float* SFX, float* MEL, uint64_t total,
+                         const uint64_t* frame_pfx4, float* SFX4, uint64_t total4, hipStream_t st);
+// E, H and MEL of a hop-1024 pass (frame prefix frame_pfx4, 256-frame tile prefix tile_pfx) copied
+// from the hop-512 pass of the same tracks: frame j from frame row0[track] + 2 j
+void launch_features_gather2(const uint64_t* frame_pfx4, const uint64_t* row0, int T, const uint64_t* tile_pfx,
+                             uint64_t n_tiles, int n_mels, const float* E2, const float* H2, const float* MEL2,
+                             uint64_t total2, float* E4, float* H4, float* MEL4, uint64_t total4, hipStream_t st);
 void launch_novelty(const float* E, const float* H, const float* SFX, const uint64_t* frame_pfx, int T, uint64_t total,
                     const NovParams& P, float* scratch, float* nov, float* nov_sum, const float* MEL, int n_mels,
                     int mel_k, bool mel_on, unsigned int* mel_max, hipStream_t st);

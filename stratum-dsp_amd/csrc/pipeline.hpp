@@ -196,6 +196,7 @@ struct TempoStageDbg {
 
 // One "tempo pass": STFT (2048, hop) -> features -> novelty -> tempograms -> candidate scoring,
 // for a dense list of tracks.  Used for hop 512 (all tracks) and the escalation hops.
+struct TempoPassOut;
 struct TempoPassIn {
     int hop = 0;
     const float* samples = nullptr;
@@ -216,6 +217,19 @@ struct TempoPassIn {
     // also the hop-512 novelty multi_resolution.rs:680-694 gates its folds with (the combined
     // novelty with the configured weights, whatever the band-fusion setting; out.nov_mr)
     bool mr_nov = false;
+    // What the escalation's hop-256 and hop-1024 passes share (Pipeline::escalate; the defaults are
+    // a complete pass).  no_flux: features without the spectral flux (out.SFO stays null; only the
+    // base pass's is read) and the hop-256 odd-frame STFT without frame maxima.
+    bool no_flux = false;
+    // hop 256: its feature walk also stores the hop-1024 pass's SFX of the same tracks (that pass's
+    // frame prefix on the device and its frame total)
+    float* sfx4_out = nullptr;
+    const uint64_t* sfx4_fpfx = nullptr;
+    uint64_t sfx4_total = 0;
+    // hop 1024: no feature launch; SFX as the hop-256 walk stored it, and E / H / MEL copied from the
+    // hop-512 pass feat512 (frame j from its frame base_row0[t] + 2 j)
+    float* sfx_in = nullptr;
+    const TempoPassOut* feat512 = nullptr;
     TempoStageDbg* dbg = nullptr;  // the stage probe's record (never set by an analysis call)
 };
 // the pass input of a subset of another pass's tracks (its hop and samples; no gate)
@@ -508,7 +522,7 @@ class Pipeline {
     // pipeline_tempo.hip
     void tempo_pass(const std::string& tag, const TempoPassIn& in, TempoPassOut& out);
     PassPlan pass_stft(const std::string& tag, const TempoPassIn& in, TempoPassOut& o, Timers& tm);
-    PassFeat pass_features(const std::string& tag, const PassPlan& pl, TempoPassOut& o);
+    PassFeat pass_features(const std::string& tag, const TempoPassIn& in, const PassPlan& pl, TempoPassOut& o);
     void pass_novelty(const std::string& tag, const TempoPassIn& in, const PassPlan& pl, const PassFeat& pf,
                       TempoPassOut& o);
     PassTg pass_tempograms(const std::string& tag, const TempoPassIn& in, const PassPlan& pl, const PassFeat& pf,

@@ -39,7 +39,7 @@ void Pipeline::tempo_pass(const std::string& tag, const TempoPassIn& in, TempoPa
     tm.init(d_);
     const PassPlan pl = pass_stft(tag, in, o, tm);
     tm.mark(1);
-    const PassFeat pf = pass_features(tag, pl, o);
+    const PassFeat pf = pass_features(tag, in, pl, o);
     pass_novelty(tag, in, pl, pf, o);
     tm.mark(2);
     const PassTg tg = pass_tempograms(tag, in, pl, pf, o);
@@ -61,6 +61,8 @@ PassPlan Pipeline::pass_stft(const std::string& tag, const TempoPassIn& in, Temp
     PassPlan pl;
     const int P_T = pl.P_T = (int)in.src_off.size();
     const int FS = fs_, hop = in.hop;
+    // frames per feature tile: the walk's, or the gather's 256 when the pass has no walk of its own
+    const uint64_t tstep = in.sfx_in ? 256 : in.sfx4_out ? FT_STEP_X4 : FT_STEP;
     o.fpfx.assign((size_t)P_T + 1, 0);
     pl.tpfx.assign((size_t)P_T + 1, 0);
     o.active_h.assign((size_t)P_T, 0);
@@ -68,7 +70,7 @@ PassPlan Pipeline::pass_stft(const std::string& tag, const TempoPassIn& in, Temp
         const uint64_t n = in.n_trim[(size_t)t];
         const uint64_t F = n >= (uint64_t)FS ? (n - FS) / (uint64_t)hop + 1 : 0;
         o.fpfx[(size_t)t + 1] = o.fpfx[(size_t)t] + F;
-        pl.tpfx[(size_t)t + 1] = pl.tpfx[(size_t)t] + (F + FT_STEP - 1) / FT_STEP;
+        pl.tpfx[(size_t)t + 1] = pl.tpfx[(size_t)t] + (F + tstep - 1) / tstep;
         o.active_h[(size_t)t] = F >= 2;
     }
     const uint64_t total = o.total = o.fpfx[(size_t)P_T];
@@ -96,11 +98,14 @@ PassPlan Pipeline::pass_stft(const std::string& tag, const TempoPassIn& in, Temp
         }
         stft_frames = opfx[(size_t)P_T];
         o.mags = c_.dev<float>(tag + "mags", std::max<uint64_t>(stft_frames, 1) * s2_);
-        o.fmax = c_.dev<float>(tag + "fmax", std::max<uint64_t>(stft_frames, 1));
+        // no frame maxima without the spectral flux, unless they also select the kernel (at a frame
+        // size of 8192 the tempo path's STFT is the general kernel only with them)
+        const bool fm = !in.no_flux || stft_general(FS, true) != stft_general(FS, false);
+        o.fmax = fm ? c_.dev<float>(tag + "fmax", std::max<uint64_t>(stft_frames, 1)) : nullptr;
         uint64_t* d_opfx = c_.up(tag + "opfx", opfx);
         const std::vector<uint64_t> ostr = stft_strips(opfx);
-        launch_stft(FS, true, in.samples, d_opfx, P_T, stft_frames, c_.up(tag + "osrc", osrc), d_gain, 2 * hop,
-                    tb.window.as<float>(), stft_twp(tb, FS, true), stft_rtp(tb, FS, true), o.mags, d_opfx, s2_, o.fmax,
+        launch_stft(FS, fm, in.samples, d_opfx, P_T, stft_frames, c_.up(tag + "osrc", osrc), d_gain, 2 * hop,
+                    tb.window.as<float>(), stft_twp(tb, FS, fm), stft_rtp(tb, FS, fm), o.mags, d_opfx, s2_, o.fmax,
                     d_.stream, c_.up(tag + "ostrip", ostr), ostr.back(), c_.dev<uint32_t>(tag + "redo", stft_frames + 1));
         SDSP_HIP_CHECK(hipGetLastError());
         pl.rm = RowMap{in.base_mags, o.mags, in.base_fmax, o.fmax, c_.up(tag + "brow", in.base_row0), d_opfx, 0, 1, 1};
@@ -125,13 +130,24 @@ PassPlan Pipeline::pass_stft(const std::string& tag, const TempoPassIn& in, Temp
     return pl;
 }
 
-PassFeat Pipeline::pass_features(const std::string& tag, const PassPlan& pl, TempoPassOut& o) {
+PassFeat Pipeline::pass_features(const std::string& tag, const TempoPassIn& in, const PassPlan& pl, TempoPassOut& o) {
     PassFeat pf;
     const int B = nb_;
     const uint64_t total = o.total;
     pf.configured = band_configured(cfg_);
     pf.mel_on = pf.configured && cfg_.enable_tempogram_mel_novelty;
     FeatParams& fp = pf.fp = feat_params(cfg_, sr_, B, s2_);
+    if (in.sfx_in) {  // escalation hop 1024: nothing to walk (TempoPassIn)
+        const TempoPassOut& b = *in.feat512;
+        o.E = c_.dev<float>(tag + "E", 4 * total);
+        o.H = c_.dev<float>(tag + "H", 4 * total);
+        o.SFX = in.sfx_in;
+        o.MEL = c_.dev<float>(tag + "MEL", std::max<uint64_t>(total * (uint64_t)std::max(fp.n_mels, 1), 1));
+        launch_features_gather2(o.d_fpfx, pl.rm.rowA0, pl.P_T, pl.d_tpfx, pl.tpfx[(size_t)pl.P_T], fp.n_mels, b.E, b.H, b.MEL,
+                                b.total, o.E, o.H, o.MEL, total, d_.stream);
+        SDSP_HIP_CHECK(hipGetLastError());
+        return pf;
+    }
     std::string merr;
     MelTable mt = mel_table(sr_, B, (int)cfg_.tempogram_mel_n_mels, cfg_.tempogram_mel_fmin_hz, cfg_.tempogram_mel_fmax_hz,
                             &merr);
@@ -147,8 +163,14 @@ PassFeat Pipeline::pass_features(const std::string& tag, const PassPlan& pl, Tem
     o.E = c_.dev<float>(tag + "E", 4 * total);
     o.H = c_.dev<float>(tag + "H", 4 * total);
     o.SFX = c_.dev<float>(tag + "SFX", 4 * total);
-    o.SFO = c_.dev<float>(tag + "SFO", total);
     o.MEL = c_.dev<float>(tag + "MEL", std::max<uint64_t>(total * (uint64_t)std::max(fp.n_mels, 1), 1));
+    if (in.no_flux) {
+        launch_features_esc(pl.rm, o.d_fpfx, pl.d_tpfx, pl.P_T, pl.tpfx[(size_t)pl.P_T], fp, d_mplan, o.E, o.H, o.SFX, o.MEL,
+                            total, in.sfx4_fpfx, in.sfx4_out, in.sfx4_total, d_.stream);
+        SDSP_HIP_CHECK(hipGetLastError());
+        return pf;
+    }
+    o.SFO = c_.dev<float>(tag + "SFO", total);
     launch_features(pl.rm, o.d_fpfx, pl.d_tpfx, pl.P_T, pl.tpfx[(size_t)pl.P_T], fp, d_mplan, o.E, o.H, o.SFX, o.SFO,
                     o.MEL, total, d_.stream);
     SDSP_HIP_CHECK(hipGetLastError());
@@ -351,11 +373,33 @@ void Pipeline::escalate(const Front& f, const TempoPassIn& bin, const TempoPassO
         ein.top_n = aux_k;
         ein.cand_cap = aux_k;
         const bool reuse_on = test_hooks().no_row_reuse.load() == 0;  // the tests' control (sdsp_debug_set_schedule)
+        // With the shared rows, the hop-256 feature walk also folds the hop-1024 SuperFlux (its
+        // frame j is hop-256 frame 4 j) and the hop-1024 pass takes E / H / MEL from the hop-512
+        // pass (frame 2 j), so it launches no features; neither computes the spectral flux, which
+        // only the base pass's onsets read.  The complete passes stay as the control, for the
+        // debug dumps, and for a SuperFlux width the fused walk is not built for.
+        const bool fused = reuse_on && !dbg_on() && feat_params(cfg_, sr_, nb_, s2_).K == 4;
         ein.hop = 256;
         ein.reuse = reuse_on ? 2 : 0;
+        if (fused) {
+            std::vector<uint64_t> fpfx4((size_t)NE + 1, 0);
+            for (int k = 0; k < NE; k++) {
+                const uint64_t n = ein.n_trim[(size_t)k];
+                fpfx4[(size_t)k + 1] = fpfx4[(size_t)k] + (n >= (uint64_t)fs_ ? (n - (uint64_t)fs_) / 1024 + 1 : 0);
+            }
+            ein.no_flux = true;
+            ein.sfx4_total = fpfx4[(size_t)NE];
+            ein.sfx4_fpfx = c_.up("C256.fpfx4", fpfx4);
+            ein.sfx4_out = c_.dev<float>("C1024.SFX", 4 * ein.sfx4_total);
+        }
         tempo_pass("C256.", ein, o256);
         ein.hop = 1024;
         ein.reuse = reuse_on ? 1 : 0;
+        if (fused) {
+            ein.sfx_in = ein.sfx4_out;
+            ein.sfx4_out = nullptr;
+            ein.feat512 = &b512;
+        }
         tempo_pass("C1024.", ein, o1024);
         add_pass_times(o256);
         add_pass_times(o1024);
