@@ -171,6 +171,54 @@ int32_t sdsp_debug_key_stages(const float* host_mags, const uint64_t* frames, ui
                               float* edel, int32_t info[4], int32_t device);
 
 /*
+ * Stage probe of the onset detectors and their consensus: the pipeline's own buffer set-up and
+ * launches (k_energy_onsets, k_flux_onsets, k_consensus, as an analysis call makes them after its
+ * frame RMS) over uploaded per-frame curves instead of samples and a spectrogram.  Every curve
+ * holds the tracks' frames back to back, frames[t] >= 1 values for track t (total = their sum):
+ *   rms   the frame RMS of the trimmed signal (the energy-flux detector's input)
+ *   hfc   the full-band HFC per frame (E/H/SFX variant 0 of sdsp_debug_tempo_stages)
+ *   sfo   the spectral-flux onset curve, the pair (f, f + 1) at f; a track's last value is not read
+ *   hpe   the frame energy of the percussive spectrogram; NULL allowed (then, with
+ *         enable_hpss_onsets, the HPSS lists are empty, as for a pass without frames)
+ * n_trim[t] is the trimmed length in samples (an onset at frame f is kept when f * hop < n_trim);
+ * hop >= 1 with frames[t] * hop < 2^32.  cfg supplies onset_threshold_percentile, the consensus
+ * switch, tolerance and weights and enable_hpss_onsets.  The caller allocates `out`: energy,
+ * spectral, hfc and hpss hold `total` sample positions each, track t's list at its frame prefix;
+ * chosen holds 4 x total, track t's at 4 x its frame prefix; n_* (n_tracks each) the entries
+ * written.  hpss counts are 0 without HPSS onsets.  Allocates only buffers of its own, released
+ * before it returns.
+ */
+typedef struct sdsp_debug_onset_out {
+    uint32_t *energy, *spectral, *hfc, *hpss, *chosen;
+    int32_t *n_energy, *n_spectral, *n_hfc, *n_hpss, *n_chosen;
+} sdsp_debug_onset_out;
+int32_t sdsp_debug_onset_stages(const float* rms, const float* hfc, const float* sfo, const float* hpe,
+                                const uint64_t* frames, const uint64_t* n_trim, uint64_t n_tracks, uint32_t sample_rate,
+                                uint32_t hop, const sdsp_config* cfg, sdsp_debug_onset_out* out, int32_t device);
+
+/*
+ * Stage probe of the beat grid: the pipeline's own beat stage (k_beat with its capacity formula,
+ * then the compaction kernel its track count selects, and the download) over uploaded consensus
+ * onsets and tempo estimates instead of an analysis.  onsets holds the tracks' ascending sample
+ * positions back to back, n_onsets[t] of them for track t; frames[t] >= 1 and n_trim[t] are the
+ * track's base-pass frame count and trimmed length, from which the pipeline sizes its lists: the
+ * consensus list holds lists x frames[t] entries (lists = 4 with HPSS onsets, else 3) and the beat
+ * lists cap[t] = max(12 (n_trim[t] / sample_rate + 1) + 64, 3 frames[t] + 8).  An onset list longer
+ * than either is refused with SDSP_ERR_INVALID_INPUT (the analysis call cannot produce one).  bpm[t], conf[t]:
+ * the final tempo estimate.  The caller allocates `out`: ok (1 a grid, 0 none, -1 a list outgrew
+ * cap[t]), n_beats, n_down and stability per track as k_beat wrote them, and the beats and
+ * downbeats of the tracks with ok = 1 back to back in track order (the sum of cap[t] entries
+ * suffices).  Allocates only buffers of its own, released before it returns.
+ */
+typedef struct sdsp_debug_beat_out {
+    int32_t *ok, *n_beats, *n_down;
+    float *stability, *beats, *downs;
+} sdsp_debug_beat_out;
+int32_t sdsp_debug_beat_grid(const uint32_t* onsets, const uint64_t* n_onsets, const uint64_t* frames,
+                             const uint64_t* n_trim, const float* bpm, const float* conf, uint64_t n_tracks,
+                             uint32_t sample_rate, const sdsp_config* cfg, sdsp_debug_beat_out* out, int32_t device);
+
+/*
  * Isolated STFT kernel timing: `reps` launches over n_tracks device-resident noise tracks of len
  * samples; mean launch time (HIP events on the launch stream) and algorithmic bytes per launch
  * (4 N_in + 4 F (nfft/2 + 1) per track).  stride 0 = the pipeline's row stride.

@@ -274,6 +274,7 @@ bool generate_beat_grid(float bpm, float conf, const std::vector<float>& onsets_
         std::vector<BeatPos> pos;
         if (!hmm_track(bpm, on, &pos)) return false;
         if (pos.empty()) return false;  // ProcessingError
+        dg.hmm_beats = (uint32_t)pos.size();
         std::vector<float> bt;
         for (auto& p : pos) bt.push_back(p.t);
         auto segs = tempo_variations(bt, bpm);
@@ -383,14 +384,31 @@ using namespace orc;
 
 extern "C" {
 
+int32_t sdsp_oracle_beat_grid_diag(float bpm, float conf, const float* on, uint64_t n, uint32_t sr, float* beats,
+                                   float* downs, uint64_t cap, uint64_t* counts, float* stability, int32_t* diag);
+
 // generate_beat_grid (mod.rs:108-247): the reference returns Err for bpm <= 0 or > 300, empty
 // onsets and a failed HMM; the oracle maps every such case to "no grid" (-1 here).
 // counts = (beats, downbeats); bars == downbeats (mod.rs:316)
 int32_t sdsp_oracle_beat_grid(float bpm, float conf, const float* on, uint64_t n, uint32_t sr, float* beats,
                               float* downs, uint64_t cap, uint64_t* counts, float* stability) {
+    return sdsp_oracle_beat_grid_diag(bpm, conf, on, n, sr, beats, downs, cap, counts, stability, nullptr);
+}
+
+// The same with generate_beat_grid's branch record: diag (NULL allowed) = BeatDiag's variable,
+// refined, beats_per_bar and the whole-track HMM's beat count (tests/beat_cases.py)
+int32_t sdsp_oracle_beat_grid_diag(float bpm, float conf, const float* on, uint64_t n, uint32_t sr, float* beats,
+                                   float* downs, uint64_t cap, uint64_t* counts, float* stability, int32_t* diag) {
     std::vector<float> o(on, on + n), b, d;
     float st = 0.0f;
-    if (!generate_beat_grid(bpm, conf, o, sr, &b, &d, &st)) return -1;
+    BeatDiag dg;
+    if (!generate_beat_grid(bpm, conf, o, sr, &b, &d, &st, &dg)) return -1;
+    if (diag) {
+        diag[0] = dg.variable;
+        diag[1] = dg.refined;
+        diag[2] = (int32_t)dg.beats_per_bar;
+        diag[3] = (int32_t)dg.hmm_beats;
+    }
     for (size_t i = 0; i < b.size() && i < cap; i++) beats[i] = b[i];
     for (size_t i = 0; i < d.size() && i < cap; i++) downs[i] = d[i];
     counts[0] = b.size();

@@ -169,6 +169,15 @@ std::vector<size_t> energy_flux_onsets(const float* s, size_t n, size_t frame, s
         for (size_t k = st; k < en; k++) sum += s[k] * s[k];
         e[i] = __builtin_sqrtf(sum / (float)(en - st));
     }
+    return energy_onsets_from_rms(e, hop, n, thr_db);
+}
+
+// energy_flux.rs:133-243 over the frame RMS e (at least two frames) of a signal of n samples: the
+// half-wave flux, the threshold relative to its maximum, the three peak rules and (i + 1) * hop < n
+std::vector<size_t> energy_onsets_from_rms(const std::vector<float>& e, size_t hop, size_t n, float thr_db) {
+    std::vector<size_t> on;
+    const size_t nf = e.size();
+    if (nf < 2) return on;
     std::vector<float> flux(nf - 1);
     for (size_t i = 1; i < nf; i++) flux[i - 1] = sd_maxf(e[i] - e[i - 1], 0.0f);
     float mx = 0.0f;
@@ -406,8 +415,14 @@ std::vector<size_t> hpss_onsets(const Spec& p, float pct) {
         for (size_t b = 0; b < p.bins; b++) s += r[b] * r[b];
         e[t] = s;
     }
-    std::vector<float> flux(p.frames - 1);
-    for (size_t i = 1; i < p.frames; i++) flux[i - 1] = sd_maxf(e[i] - e[i - 1], 0.0f);
+    return hpss_onsets_from_energy(e, pct);
+}
+
+// hpss.rs:311-372 over the percussive frame energies e (at least two frames): their half-wave
+// flux, then the percentile peaks
+std::vector<size_t> hpss_onsets_from_energy(const std::vector<float>& e, float pct) {
+    std::vector<float> flux(e.size() - 1);
+    for (size_t i = 1; i < e.size(); i++) flux[i - 1] = sd_maxf(e[i] - e[i - 1], 0.0f);
     return peaks_over_percentile(flux, pct);
 }
 
@@ -478,6 +493,32 @@ const char* sdsp_oracle_probe_error(void) { return g_probe_err.c_str(); }
 int64_t sdsp_oracle_energy_flux_onsets(const float* s, uint64_t n, uint64_t frame, uint64_t hop, float thr_db,
                                        uint64_t* out, uint64_t cap) {
     return probe_call([&]() -> int64_t { return put_list(energy_flux_onsets(s, n, frame, hop, thr_db), out, cap); });
+}
+
+// The detectors' tails over their curves (tests/test_gpu_onset_stages.py feeds the same curves to
+// sdsp_debug_onset_stages).  Energy: onset sample positions from the frame RMS of an n-sample signal.
+int64_t sdsp_oracle_energy_onsets_rms(const float* e, uint64_t nf, uint64_t hop, uint64_t n, float thr_db, uint64_t* out,
+                                      uint64_t cap) {
+    return probe_call([&]() -> int64_t {
+        return put_list(energy_onsets_from_rms(std::vector<float>(e, e + nf), hop, n, thr_db), out, cap);
+    });
+}
+
+// peaks_over_percentile behind its callers' percentile check -> onset frame indices
+int64_t sdsp_oracle_peaks_over_percentile(const float* flux, uint64_t L, float pct, uint64_t* out, uint64_t cap) {
+    return probe_call([&]() -> int64_t {
+        if (!(pct >= 0.0f && pct <= 1.0f)) fail(SDSP_ERR_INVALID_INPUT, "Threshold percentile must be in [0, 1]");
+        return put_list(peaks_over_percentile(std::vector<float>(flux, flux + L), pct), out, cap);
+    });
+}
+
+// detect_hpss_onsets from the percussive frame energies -> onset frame indices
+int64_t sdsp_oracle_hpss_energy_onsets(const float* e, uint64_t frames, float pct, uint64_t* out, uint64_t cap) {
+    return probe_call([&]() -> int64_t {
+        if (!(pct >= 0.0f && pct <= 1.0f)) fail(SDSP_ERR_INVALID_INPUT, "Threshold percentile must be in [0, 1]");
+        if (frames < 2) return 0;
+        return put_list(hpss_onsets_from_energy(std::vector<float>(e, e + frames), pct), out, cap);
+    });
 }
 
 // the spectral-flux onset feature curve (frames - 1 values; 0 below two frames)

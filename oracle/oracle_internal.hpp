@@ -72,6 +72,9 @@ void detect_and_trim(const std::vector<float>& x, uint32_t sr, float threshold_d
                      size_t frame_size, size_t* trim_start, size_t* trim_end,
                      std::vector<std::pair<size_t, size_t>>* silence_map = nullptr);
 std::vector<size_t> energy_flux_onsets(const float* s, size_t n, size_t frame, size_t hop, float thr_db);
+// its tail over the frame RMS, and detect_hpss_onsets' over the percussive frame energies
+std::vector<size_t> energy_onsets_from_rms(const std::vector<float>& e, size_t hop, size_t n, float thr_db);
+std::vector<size_t> hpss_onsets_from_energy(const std::vector<float>& e, float pct);
 std::vector<float> spectral_flux_curve(const Spec& m);  // the flux spectral_flux_onsets thresholds (frames >= 2)
 std::vector<size_t> spectral_flux_onsets(const Spec& m, float pct);
 std::vector<size_t> hfc_onsets(const Spec& m, uint32_t sr, float pct);
@@ -130,6 +133,7 @@ struct BeatDiag {            // which branches generate_beat_grid took (test pro
     bool variable = false;   // detect_tempo_variations flagged a variable segment (mod.rs:152-154)
     bool refined = false;    // the Bayesian / per-segment HMM beats replaced the HMM beats (:205-219)
     uint32_t beats_per_bar = 4;
+    uint32_t hmm_beats = 0;  // beats of the whole-track HMM (before any refinement)
 };
 bool generate_beat_grid(float bpm, float conf, const std::vector<float>& onsets_s, uint32_t sr,
                         std::vector<float>* beats, std::vector<float>* downbeats, float* stability,

@@ -58,6 +58,8 @@ def lib():
         L.sdsp_oracle_multi_resolution_analysis.restype = C.c_int32
         L.sdsp_oracle_beat_grid.argtypes = [C.c_float, C.c_float, fp, C.c_uint64, C.c_uint32, fp, fp, C.c_uint64, u64p, fp]
         L.sdsp_oracle_beat_grid.restype = C.c_int32
+        L.sdsp_oracle_beat_grid_diag.argtypes = L.sdsp_oracle_beat_grid.argtypes + [i32p]
+        L.sdsp_oracle_beat_grid_diag.restype = C.c_int32
         L.sdsp_oracle_downbeats.argtypes = [fp, C.c_uint64, C.c_float, C.c_uint32, fp]
         L.sdsp_oracle_downbeats.restype = C.c_int64
         L.sdsp_oracle_grid_stability.argtypes = [fp, C.c_uint64, C.c_float, fp]
@@ -225,6 +227,67 @@ def generate_beat_grid(bpm, bpm_confidence, onsets_s, sample_rate):
         raise AnalysisError(1, "generate_beat_grid failed")
     beats, downs = b[:int(counts[0])].tolist(), d[:int(counts[1])].tolist()
     return beats, downs, list(downs), st.value
+
+
+def beat_grid_diag(bpm, bpm_confidence, onsets_s, sample_rate):
+    """generate_beat_grid with its branch record: None where the reference returns Err, else a dict of
+    beats, downbeats (float32 arrays), stability (float32) and BeatDiag's variable, refined,
+    beats_per_bar and hmm_beats (the whole-track HMM's beat count)."""
+    on = _f32(onsets_s)
+    cap = 8 * on.size + 64
+    b, d = np.zeros(cap, np.float32), np.zeros(cap, np.float32)
+    counts = np.zeros(2, np.uint64)
+    st = C.c_float(0)
+    diag = np.zeros(4, np.int32)
+    rc = lib().sdsp_oracle_beat_grid_diag(bpm, bpm_confidence, _p(on), on.size, sample_rate, _p(b), _p(d), cap,
+                                          _u64(counts), C.byref(st), diag.ctypes.data_as(i32p))
+    if rc != 0:
+        return None
+    assert int(counts[0]) <= cap
+    return dict(beats=b[:int(counts[0])].copy(), downbeats=d[:int(counts[1])].copy(), stability=np.float32(st.value),
+                variable=bool(diag[0]), refined=bool(diag[1]), beats_per_bar=int(diag[2]), hmm_beats=int(diag[3]))
+
+
+# ---- the onset detectors' tails over their curves (tests/test_gpu_onset_stages.py) ----
+def energy_onsets_from_rms(rms, hop, n, threshold_db=-20.0):
+    """detect_energy_flux_onsets after its frame RMS: onset sample positions of an n-sample signal."""
+    L = lib()
+    L.sdsp_oracle_energy_onsets_rms.argtypes = [fp, C.c_uint64, C.c_uint64, C.c_uint64, C.c_float, u64p, C.c_uint64]
+    L.sdsp_oracle_energy_onsets_rms.restype = C.c_int64
+    e = _f32(rms)
+    return _list_call(L.sdsp_oracle_energy_onsets_rms, _p(e), e.size, hop, n, threshold_db, cap=e.size + 1)
+
+
+def peaks_over_percentile(flux, percentile):
+    """The shared tail of the spectral-flux, HFC and HPSS detectors: onset frame indices (i + 1 for a
+    peak at flux index i); AnalysisError for a percentile outside [0, 1], as its callers raise."""
+    L = lib()
+    L.sdsp_oracle_peaks_over_percentile.argtypes = [fp, C.c_uint64, C.c_float, u64p, C.c_uint64]
+    L.sdsp_oracle_peaks_over_percentile.restype = C.c_int64
+    f = _f32(flux)
+    return _list_call(L.sdsp_oracle_peaks_over_percentile, _p(f), f.size, percentile, cap=f.size + 1)
+
+
+def hpss_onsets_from_energy(energy, percentile):
+    """detect_hpss_onsets after its percussive frame energies: onset frame indices."""
+    L = lib()
+    L.sdsp_oracle_hpss_energy_onsets.argtypes = [fp, C.c_uint64, C.c_float, u64p, C.c_uint64]
+    L.sdsp_oracle_hpss_energy_onsets.restype = C.c_int64
+    e = _f32(energy)
+    return _list_call(L.sdsp_oracle_hpss_energy_onsets, _p(e), e.size, percentile, cap=e.size + 1)
+
+
+def consensus_select(lists, weights, tol_ms, sample_rate):
+    """The onsets the analysis hands to the legacy estimator and the beat tracker (src/lib.rs:258-291):
+    vote_onsets over the four lists, then the centres of the clusters at least two methods voted for,
+    or every centre when there is none, sorted and deduplicated; the energy list (lists[0]) when the
+    vote fails (zero tolerance, a negative weight) or nothing clustered."""
+    cands = oracle.vote_onsets(lists, weights, tol_ms, sample_rate)
+    if isinstance(cands, int):  # Err
+        return [int(v) for v in lists[0]]
+    strong = sorted({t for t, voted, _ in cands if voted >= 2})
+    chosen = strong if strong else sorted({t for t, _, _ in cands})
+    return chosen if chosen else [int(v) for v in lists[0]]
 
 
 def detect_downbeats(beats, bpm, beats_per_bar=4):

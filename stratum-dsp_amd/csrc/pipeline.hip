@@ -436,10 +436,8 @@ Hpss Pipeline::hpss(const TempoPassOut& bo, const std::vector<TempoEst>& best, H
 // onsets: energy flux (frame FS, hop HOP; same framing as the STFT), spectral flux, HFC, HPSS, consensus
 Onsets Pipeline::onsets(const float* d_samples, const Front& f, const TempoPassIn& bin, const TempoPassOut& bo,
                         const Hpss& hp) {
-    Onsets on;
     const int NR = (int)f.R.size(), FS = fs_, HOP = bin.hop;
     hipStream_t st = d_.stream;
-    const bool hpss_on = cfg_.enable_hpss_onsets && cfg_.enable_onset_consensus;
     uint64_t* d_src = c_.up("B.src2", bin.src_off);
     float* d_g = c_.up("B.gain2", bin.gain_h);
     uint64_t* d_nt = c_.up("B.ntrim", bin.n_trim);
@@ -455,6 +453,19 @@ Onsets Pipeline::onsets(const float* d_samples, const Front& f, const TempoPassI
                                   FS, HOP, d_erms, st);
     else
         launch_frame_rms(d_samples, d_src, d_g, d_nt, bo.d_fpfx, NR, bo.total, FS, HOP, d_erms, st);
+    return onset_lists(d_erms, d_nt, HOP, bo, hp);
+}
+
+// The onset lists and their consensus from the device curves of a pass's tracks: the frame RMS
+// d_erms, bo.SFO, bo.H (its full-band quarter) and, with HPSS onsets, hp.d_hpe, at bo's frame
+// prefix.  The analysis call (Pipeline::onsets) and the stage probe (debug_onset_stages) both
+// launch from here.
+Onsets Pipeline::onset_lists(const float* d_erms, const uint64_t* d_nt, int HOP, const TempoPassOut& bo,
+                             const Hpss& hp) {
+    Onsets on;
+    const int NR = (int)bo.fpfx.size() - 1;
+    hipStream_t st = d_.stream;
+    const bool hpss_on = cfg_.enable_hpss_onsets && cfg_.enable_onset_consensus;
     uint32_t* d_eon = c_.dev<uint32_t>("B.eon", std::max<uint64_t>(bo.total, 1));
     int* d_en = c_.dev<int>("B.en", (size_t)NR);
     launch_energy_onsets(d_erms, bo.d_fpfx, d_nt, HOP, sd_powf(10.0f, -20.0f / 20.0f), d_eon, bo.d_fpfx, d_en, NR, st);
@@ -488,6 +499,11 @@ Onsets Pipeline::onsets(const float* d_samples, const Front& f, const TempoPassI
     launch_consensus(d_eon, bo.d_fpfx, d_en, d_fon, bo.d_fpfx, d_fn, bo.total, NR, tol, cons_ok, d_hm, on.d_chosen,
                      on.d_coff, on.d_cn, d_cscr, st, hpss_on ? 1 : 0);
     SDSP_HIP_CHECK(hipGetLastError());
+    on.d_eon = d_eon;
+    on.d_en = d_en;
+    on.d_fon = d_fon;
+    on.d_fn = d_fn;
+    on.lists = (int)lists;
     on.en_h = c_.down(d_en, (size_t)NR);
     return on;
 }

@@ -365,6 +365,12 @@ struct Onsets {
     uint64_t* d_coff = nullptr;
     int* d_cn = nullptr;
     std::vector<int> en_h;  // energy-flux onset counts
+    // the lists the consensus merged (read by the stage probe only): energy onsets at the frame
+    // prefix with counts d_en; flux onsets in kind-major parts (spectral, HFC, HPSS) of the pass's
+    // frame total each, counts d_fn kind-major; `lists` of them in all (3, or 4 with HPSS onsets)
+    uint32_t *d_eon = nullptr, *d_fon = nullptr;
+    int *d_en = nullptr, *d_fn = nullptr;
+    int lists = 0;
 };
 // The tempo estimates of the surviving tracks.  The one hand-off that is not read-only: seeded from
 // the base pass (seed_tempo), then refined in turn by the escalation, the percussive fallback and
@@ -437,6 +443,12 @@ class Pipeline {
                             sdsp_debug_tempo_out* out);
     void debug_key_stages(const float* host_mags, const uint64_t* frames, uint64_t n_tracks, int mode, float* masked,
                           float* chroma, float* energy, float* edel, int32_t info[4]);
+    void debug_onset_stages(const float* rms, const float* hfc, const float* sfo, const float* hpe,
+                            const uint64_t* frames, const uint64_t* n_trim, uint64_t n_tracks, int hop,
+                            sdsp_debug_onset_out* out);
+    void debug_beat_grid(const uint32_t* onsets, const uint64_t* n_onsets, const uint64_t* frames,
+                         const uint64_t* n_trim, const float* bpm, const float* conf, uint64_t n_tracks,
+                         sdsp_debug_beat_out* out);
 
     void run(const float* d_samples, const std::vector<uint64_t>& in_off, const std::vector<uint64_t>& n_raw,
              std::vector<TrackRes>& res);
@@ -512,6 +524,7 @@ class Pipeline {
     TempoPassIn base_pass_in(const float* d_samples, const Front& f) const;
     Hpss hpss(const TempoPassOut& bo, const std::vector<TempoEst>& best, HostTrace& htr);
     Onsets onsets(const float* d_samples, const Front& f, const TempoPassIn& bin, const TempoPassOut& bo, const Hpss& hp);
+    Onsets onset_lists(const float* d_erms, const uint64_t* d_nt, int HOP, const TempoPassOut& bo, const Hpss& hp);
     Beats beat_grid(const TempoPassIn& bin, const TempoPassOut& bo, const Onsets& on, const Tempo& tp);
     ResultsHost download_results(const Beats& bt, const TempoPassIn& bin, const TempoPassOut& bo);
     Overview overview(const float* d_samples, const TempoPassIn& bin, const TempoPassOut& bo, Timers& tm);

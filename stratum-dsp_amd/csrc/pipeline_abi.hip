@@ -615,6 +615,46 @@ int32_t sdsp_debug_key_stages(const float* host_mags, const uint64_t* frames, ui
     });
 }
 
+int32_t sdsp_debug_onset_stages(const float* rms, const float* hfc, const float* sfo, const float* hpe,
+                                const uint64_t* frames, const uint64_t* n_trim, uint64_t n_tracks, uint32_t sample_rate,
+                                uint32_t hop, const sdsp_config* cfg, sdsp_debug_onset_out* out, int32_t device) {
+    if (!rms || !hfc || !sfo || !frames || !n_trim || !cfg || !out || n_tracks == 0 || n_tracks > (1u << 20) ||
+        sample_rate == 0 || hop == 0 || hop > (1u << 24))
+        return SDSP_ERR_INVALID_INPUT;
+    if (!out->energy || !out->spectral || !out->hfc || !out->hpss || !out->chosen || !out->n_energy ||
+        !out->n_spectral || !out->n_hfc || !out->n_hpss || !out->n_chosen)
+        return SDSP_ERR_INVALID_INPUT;
+    for (uint64_t t = 0; t < n_tracks; t++)
+        if (frames[t] == 0 || frames[t] > (1u << 24) || frames[t] * (uint64_t)hop >= (1ull << 32))
+            return SDSP_ERR_INVALID_INPUT;
+    return run_stage_probe("sdsp_debug_onset_stages", device, [&](DeviceCtx& d) {
+        Pipeline p(d, *cfg, sample_rate, SDSP_STAGES_FULL, false, false, false, true);
+        p.debug_onset_stages(rms, hfc, sfo, hpe, frames, n_trim, n_tracks, (int)hop, out);
+    });
+}
+
+int32_t sdsp_debug_beat_grid(const uint32_t* onsets, const uint64_t* n_onsets, const uint64_t* frames,
+                             const uint64_t* n_trim, const float* bpm, const float* conf, uint64_t n_tracks,
+                             uint32_t sample_rate, const sdsp_config* cfg, sdsp_debug_beat_out* out, int32_t device) {
+    if (!onsets || !n_onsets || !frames || !n_trim || !bpm || !conf || !cfg || !out || n_tracks == 0 ||
+        n_tracks > (1u << 20) || sample_rate == 0)
+        return SDSP_ERR_INVALID_INPUT;
+    if (!out->ok || !out->n_beats || !out->n_down || !out->stability || !out->beats || !out->downs)
+        return SDSP_ERR_INVALID_INPUT;
+    for (uint64_t t = 0; t < n_tracks; t++) {
+        if (frames[t] == 0 || frames[t] > (1u << 24) || n_trim[t] > (1ull << 40)) return SDSP_ERR_INVALID_INPUT;
+    }
+    for (uint64_t t = 0, at = 0; t < n_tracks; at += n_onsets[t], t++) {
+        if (n_onsets[t] > (1u << 26)) return SDSP_ERR_INVALID_INPUT;
+        for (uint64_t k = 1; k < n_onsets[t]; k++)
+            if (onsets[at + k] < onsets[at + k - 1]) return SDSP_ERR_INVALID_INPUT;  // ascending, as the consensus leaves them
+    }
+    return run_stage_probe("sdsp_debug_beat_grid", device, [&](DeviceCtx& d) {
+        Pipeline p(d, *cfg, sample_rate, SDSP_STAGES_FULL, false, false, false, true);
+        p.debug_beat_grid(onsets, n_onsets, frames, n_trim, bpm, conf, n_tracks, out);
+    });
+}
+
 // Host buffers: chunks of whole tracks (up to SDSP_BATCH_CHUNK_TRACKS tracks, default
 // 512, and about 8 GB) pulled from a shared counter by one worker per device; per device a copier
 // thread stages the next chunk into the second of two HBM slots (its own stream, completion

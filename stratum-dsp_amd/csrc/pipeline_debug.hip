@@ -366,4 +366,86 @@ void Pipeline::debug_key_stages(const float* host_mags, const uint64_t* frames, 
     c_.sync();
 }
 
+// sdsp_debug_onset_stages: onset_lists over uploaded curves, then every list back to the host.
+void Pipeline::debug_onset_stages(const float* rms, const float* hfc, const float* sfo, const float* hpe,
+                                  const uint64_t* frames, const uint64_t* n_trim, uint64_t n_tracks, int hop,
+                                  sdsp_debug_onset_out* out) {
+    if (const std::string why = check_supported(cfg_, sr_); !why.empty()) throw HipError(why);
+    TempoPassOut bo;
+    bo.fpfx.assign(1, 0);
+    for (uint64_t t = 0; t < n_tracks; t++) bo.fpfx.push_back(bo.fpfx.back() + frames[t]);
+    const uint64_t total = bo.total = bo.fpfx.back();
+    bo.d_fpfx = c_.up("O.fpfx", bo.fpfx);
+    auto curve = [&](const char* name, const float* h) { return c_.up(name, std::vector<float>(h, h + total)); };
+    float* d_erms = curve("O.rms", rms);
+    bo.H = curve("O.hfc", hfc);
+    bo.SFO = curve("O.sfo", sfo);
+    Hpss hp;
+    if (hpe) hp.d_hpe = curve("O.hpe", hpe);
+    const uint64_t* d_nt = c_.up("B.ntrim", std::vector<uint64_t>(n_trim, n_trim + n_tracks));
+    const Onsets on = onset_lists(d_erms, d_nt, hop, bo, hp);
+    const size_t T = (size_t)n_tracks;
+    const int kinds = on.lists - 1;
+    const std::vector<uint32_t> eon = c_.down(on.d_eon, (size_t)total), fon = c_.down(on.d_fon, (size_t)(kinds * total)),
+                                ch = c_.down(on.d_chosen, (size_t)on.lists * (size_t)total);
+    const std::vector<int> fn = c_.down(on.d_fn, (size_t)kinds * T), cn = c_.down(on.d_cn, T);
+    uint32_t* const lists[3] = {out->spectral, out->hfc, out->hpss};
+    int32_t* const counts[3] = {out->n_spectral, out->n_hfc, out->n_hpss};
+    for (size_t t = 0; t < T; t++) {
+        const size_t f0 = (size_t)bo.fpfx[t];
+        out->n_energy[t] = on.en_h[t];
+        std::copy_n(eon.begin() + (ptrdiff_t)f0, on.en_h[t], out->energy + f0);
+        for (int k = 0; k < 3; k++) {
+            counts[k][t] = k < kinds ? fn[(size_t)k * T + t] : 0;
+            std::copy_n(fon.begin() + (ptrdiff_t)((size_t)k * (size_t)total + f0), counts[k][t], lists[k] + f0);
+        }
+        out->n_chosen[t] = cn[t];
+        std::copy_n(ch.begin() + (ptrdiff_t)((size_t)on.lists * f0), cn[t], out->chosen + 4 * f0);
+    }
+}
+
+// sdsp_debug_beat_grid: beat_grid and download_results over uploaded consensus onsets and tempo
+// estimates, laid out as Pipeline::onset_lists and seed_tempo leave them.
+void Pipeline::debug_beat_grid(const uint32_t* onsets, const uint64_t* n_onsets, const uint64_t* frames,
+                               const uint64_t* n_trim, const float* bpm, const float* conf, uint64_t n_tracks,
+                               sdsp_debug_beat_out* out) {
+    if (const std::string why = check_supported(cfg_, sr_); !why.empty()) throw HipError(why);
+    const size_t T = (size_t)n_tracks;
+    const uint64_t lists = hpss_on() ? 4 : 3;
+    TempoPassIn bin;
+    bin.n_trim.assign(n_trim, n_trim + T);
+    TempoPassOut bo;
+    bo.fpfx.assign(1, 0);
+    std::vector<uint64_t> coff(T);
+    std::vector<int> cn(T);
+    for (size_t t = 0; t < T; t++) {
+        const uint64_t cap = std::max<uint64_t>(12 * (n_trim[t] / std::max<uint32_t>(sr_, 1) + 1) + 64, 3 * frames[t] + 8);
+        if (n_onsets[t] > lists * frames[t] || n_onsets[t] > cap) throw std::invalid_argument("onset list too long");
+        coff[t] = lists * bo.fpfx.back();
+        cn[t] = (int)n_onsets[t];
+        bo.fpfx.push_back(bo.fpfx.back() + frames[t]);
+    }
+    bo.total = bo.fpfx.back();
+    std::vector<uint32_t> chosen((size_t)(lists * bo.total), 0);
+    for (size_t t = 0, at = 0; t < T; at += (size_t)n_onsets[t], t++)
+        std::copy_n(onsets + at, (size_t)n_onsets[t], chosen.begin() + (ptrdiff_t)coff[t]);
+    Onsets on;
+    on.d_chosen = c_.up("B.chosen", chosen);
+    on.d_coff = c_.up("B.coff", coff);
+    on.d_cn = c_.up("B.cn", cn);
+    Tempo tp;
+    tp.d_fbpm = c_.up("C.fbpm", std::vector<float>(bpm, bpm + T));
+    tp.d_fconf = c_.up("C.fconf", std::vector<float>(conf, conf + T));
+    const Beats bt = beat_grid(bin, bo, on, tp);
+    const ResultsHost rh = download_results(bt, bin, bo);
+    for (size_t t = 0; t < T; t++) {
+        out->ok[t] = rh.bout[t].ok;
+        out->n_beats[t] = rh.bout[t].n_beats;
+        out->n_down[t] = rh.bout[t].n_down;
+        out->stability[t] = rh.bout[t].stability;
+    }
+    std::copy(rh.beats_h.begin(), rh.beats_h.end(), out->beats);
+    std::copy(rh.downs_h.begin(), rh.downs_h.end(), out->downs);
+}
+
 }  // namespace sdsp

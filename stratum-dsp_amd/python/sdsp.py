@@ -897,6 +897,110 @@ def debug_key_stages(specs, sample_rate=44100, config=None, mode=0, device=0):
     return meta, tracks
 
 
+class SdspDebugOnsetOut(C.Structure):
+    """sdsp_debug_onset_out (include/stratum_hip_debug.h)."""
+    _fields_ = ([(n, C.POINTER(C.c_uint32)) for n in ("energy", "spectral", "hfc", "hpss", "chosen")] +
+                [(n, C.POINTER(C.c_int32)) for n in ("n_energy", "n_spectral", "n_hfc", "n_hpss", "n_chosen")])
+
+
+def debug_onset_stages(tracks, sample_rate=44100, hop=512, config=None, device=0):
+    """The onset detectors and their consensus over per-frame curves (sdsp_debug_onset_stages).
+    tracks: dicts of rms, hfc, sfo (F >= 1 values each; sfo may have F - 1), optionally hpe, and
+    n_trim.  Returns per track a dict of the energy, spectral, hfc, hpss and chosen lists (uint32
+    sample positions)."""
+    cfg = config if config is not None else default_config()
+    frames = np.array([np.asarray(t["rms"]).size for t in tracks], np.uint64)
+    T, total = len(tracks), int(frames.sum())
+
+    def curve(key):
+        parts = []
+        for t, F in zip(tracks, frames):
+            a = np.asarray(t[key], dtype=np.float32).ravel()
+            if key == "sfo" and a.size == int(F) - 1:
+                a = np.concatenate([a, np.zeros(1, np.float32)])
+            if a.size != int(F):
+                raise ValueError(f"{key}: {int(F)} values expected")
+            parts.append(a)
+        return np.ascontiguousarray(np.concatenate(parts))
+
+    rms, hfc, sfo = curve("rms"), curve("hfc"), curve("sfo")
+    with_hpe = [t.get("hpe") is not None for t in tracks]
+    if any(with_hpe) and not all(with_hpe):
+        raise ValueError("hpe: for every track or none")
+    hpe = curve("hpe") if all(with_hpe) and T else None
+    n_trim = np.array([int(t["n_trim"]) for t in tracks], np.uint64)
+    names = ("energy", "spectral", "hfc", "hpss", "chosen")
+    u32p, i32p, u64p = C.POINTER(C.c_uint32), C.POINTER(C.c_int32), C.POINTER(C.c_uint64)
+    lists = {k: np.zeros((4 if k == "chosen" else 1) * max(total, 1), np.uint32) for k in names}
+    counts = {k: np.full(max(T, 1), -1, np.int32) for k in names}
+    o = SdspDebugOnsetOut()
+    for k in names:
+        setattr(o, k, lists[k].ctypes.data_as(u32p))
+        setattr(o, "n_" + k, counts[k].ctypes.data_as(i32p))
+    f = lib().sdsp_debug_onset_stages
+    fp = C.POINTER(C.c_float)
+    f.argtypes = [fp, fp, fp, fp, u64p, u64p, C.c_uint64, C.c_uint32, C.c_uint32, C.POINTER(SdspConfig),
+                  C.POINTER(SdspDebugOnsetOut), C.c_int32]
+    f.restype = C.c_int32
+    st = f(_fp(rms), _fp(hfc), _fp(sfo), _fp(hpe) if hpe is not None else None, frames.ctypes.data_as(u64p),
+           n_trim.ctypes.data_as(u64p), T, sample_rate, hop, C.byref(cfg), C.byref(o), device)
+    if st != 0:
+        raise AnalysisError(st, "debug_onset_stages failed")
+    out, g0 = [], 0
+    for t in range(T):
+        d = {}
+        for k in names:
+            at = (4 if k == "chosen" else 1) * g0
+            d[k] = lists[k][at:at + int(counts[k][t])].copy()
+        out.append(d)
+        g0 += int(frames[t])
+    return out
+
+
+class SdspDebugBeatOut(C.Structure):
+    """sdsp_debug_beat_out (include/stratum_hip_debug.h)."""
+    _fields_ = ([(n, C.POINTER(C.c_int32)) for n in ("ok", "n_beats", "n_down")] +
+                [(n, C.POINTER(C.c_float)) for n in ("stability", "beats", "downs")])
+
+
+def debug_beat_grid(tracks, sample_rate=44100, config=None, device=0):
+    """The beat stage over consensus onsets and tempo estimates (sdsp_debug_beat_grid).  tracks: dicts
+    of onsets (ascending uint32 sample positions), frames, n_trim, bpm, conf.  Returns per track a dict
+    of ok, beats, downbeats (float32 arrays; empty unless ok = 1) and stability (float32)."""
+    cfg = config if config is not None else default_config()
+    T = len(tracks)
+    ons = [np.ascontiguousarray(t["onsets"], dtype=np.uint32).ravel() for t in tracks]
+    n_on = np.array([a.size for a in ons], np.uint64)
+    allon = np.ascontiguousarray(np.concatenate(ons + [np.zeros(1, np.uint32)]))
+    frames = np.array([int(t["frames"]) for t in tracks], np.uint64)
+    n_trim = np.array([int(t["n_trim"]) for t in tracks], np.uint64)
+    bpm = np.array([t["bpm"] for t in tracks], np.float32)
+    conf = np.array([t["conf"] for t in tracks], np.float32)
+    cap = sum(max(12 * (int(n) // sample_rate + 1) + 64, 3 * int(F) + 8) for n, F in zip(n_trim, frames))
+    ok, nb, nd = (np.zeros(max(T, 1), np.int32) for _ in range(3))
+    stab, beats, downs = np.zeros(max(T, 1), np.float32), np.zeros(max(cap, 1), np.float32), np.zeros(max(cap, 1), np.float32)
+    i32p, u64p = C.POINTER(C.c_int32), C.POINTER(C.c_uint64)
+    o = SdspDebugBeatOut(ok.ctypes.data_as(i32p), nb.ctypes.data_as(i32p), nd.ctypes.data_as(i32p), _fp(stab), _fp(beats),
+                         _fp(downs))
+    f = lib().sdsp_debug_beat_grid
+    fp = C.POINTER(C.c_float)
+    f.argtypes = [C.POINTER(C.c_uint32), u64p, u64p, u64p, fp, fp, C.c_uint64, C.c_uint32, C.POINTER(SdspConfig),
+                  C.POINTER(SdspDebugBeatOut), C.c_int32]
+    f.restype = C.c_int32
+    st = f(allon.ctypes.data_as(C.POINTER(C.c_uint32)), n_on.ctypes.data_as(u64p), frames.ctypes.data_as(u64p),
+           n_trim.ctypes.data_as(u64p), _fp(bpm), _fp(conf), T, sample_rate, C.byref(cfg), C.byref(o), device)
+    if st != 0:
+        raise AnalysisError(st, "debug_beat_grid failed")
+    out, b0, d0 = [], 0, 0
+    for t in range(T):
+        kb, kd = (int(nb[t]), int(nd[t])) if ok[t] > 0 else (0, 0)
+        out.append(dict(ok=int(ok[t]), beats=beats[b0:b0 + kb].copy(), downbeats=downs[d0:d0 + kd].copy(),
+                        stability=stab[t].copy()))
+        b0 += kb
+        d0 += kd
+    return out
+
+
 def key_fft_bins(cfg):
     """Bins per row of the key spectrogram: the override's frame size (>= 256), else frame_size."""
     n = max(int(cfg.key_stft_frame_size), 256) if cfg.enable_key_stft_override else int(cfg.frame_size)
