@@ -171,6 +171,58 @@ int32_t sdsp_debug_key_stages(const float* host_mags, const uint64_t* frames, ui
                               float* edel, int32_t info[4], int32_t device);
 
 /*
+ * Stage probe of the key vote: the pipeline's own vote launch (k_key_vote through its launcher, with
+ * the parameters, templates and segment scratch sizing of an analysis call) over uploaded chroma rows
+ * and frame energies instead of a spectrogram.  host_chroma holds the tracks' raw rows back to back,
+ * frames[t] >= 1 rows of 12 floats for track t (total = their sum); host_energy one value per row;
+ * host_edel (NULL allowed) the per-frame relative energy bound of the band path.  With host_edel the
+ * launch is the band path's (near_check = 1, edel and wdel passed: the near-decision certificate
+ * runs, rigorous unless cert_fixed != 0); without it the exact path's (near_check = 0, no bounds).
+ * sel / n_sel: NULL / 0 votes on every track in order; otherwise the listed track indices (a subset,
+ * in any order, no repeats), launched as the in-place rerun launches its selection: the item list
+ * is `sel`, the segment scratch offsets are compact by item and the frame prefix stays by track.
+ * threads: 0 the launcher's own choice from the item count and `alone` (the flag an analysis call
+ * sets for a launch with nothing beside it); 256, 512 or 1024 force that instantiation.
+ * The caller allocates every array of `out`:
+ *   key        n_tracks records as the kernel wrote them; the probe uploads the caller's contents
+ *              first, so the records of tracks outside `sel` come back untouched
+ *   chroma_s   total x 12, the sharpened and smoothed rows (zero for tracks outside `sel`)
+ *   weights    total, the frame weights over the voted slice (zero elsewhere)
+ *   wdel       total, the certificate's per-frame weight bounds; written only with host_edel
+ *   seg_rows   the segment scratch, 128 floats per row (24 sorted scores, 24 key indices, clarity at
+ *              [48], gate decision at [49], clarity x scale weight at [50], the certificate's columns
+ *              from [64]); item i's rows start at row seg_row_pfx[i] (n_items + 1 entries written),
+ *              sized as the pipeline sizes them; seg_rows_cap rows must hold seg_row_pfx[n_items]
+ *   dbg        n_items records: the final sorted table, its key indices, the chosen key, the
+ *              weighted pitch-class summary, slice frames and used frames
+ * n_items = n_sel, or n_tracks without a selection.  SDSP_ERR_INVALID_INPUT for a bad selection or
+ * a capacity too small.  Allocates only buffers of its own, released before it returns.
+ */
+typedef struct sdsp_debug_key_out {
+    int32_t mode, tonic;
+    float conf, clarity;
+    int32_t ok, used_segments, weights_used, near;
+} sdsp_debug_key_out;
+typedef struct sdsp_debug_key_dbg {
+    float tab[24];
+    int32_t order[24];
+    int32_t key;
+    float agg[12];
+    int32_t frames, used;
+} sdsp_debug_key_dbg;
+typedef struct sdsp_debug_key_vote_out {
+    sdsp_debug_key_out* key;
+    float *chroma_s, *weights, *wdel, *seg_rows;
+    uint64_t* seg_row_pfx;
+    uint64_t seg_rows_cap;
+    sdsp_debug_key_dbg* dbg;
+} sdsp_debug_key_vote_out;
+int32_t sdsp_debug_key_vote(const float* host_chroma, const float* host_energy, const float* host_edel,
+                            const uint64_t* frames, uint64_t n_tracks, const int32_t* sel, uint64_t n_sel,
+                            uint32_t sample_rate, const sdsp_config* cfg, int32_t threads, int32_t alone,
+                            int32_t cert_fixed, sdsp_debug_key_vote_out* out, int32_t device);
+
+/*
  * Stage probe of the onset detectors and their consensus: the pipeline's own buffer set-up and
  * launches (k_energy_onsets, k_flux_onsets, k_consensus, as an analysis call makes them after its
  * frame RMS) over uploaded per-frame curves instead of samples and a spectrogram.  Every curve

@@ -204,6 +204,168 @@ std::string fmt2(float v) {
     return b;
 }
 
+}  // namespace
+
+namespace orc {
+// The key decision over raw chroma rows and frame energies (src/lib.rs:1200-1470): analyze's own
+// vote, and the sdsp_oracle_key_vote export's.
+void key_vote(std::vector<float> chroma, std::vector<float> energies, const sdsp_config& c, KeyVote* kv) {
+    const size_t F_all = energies.size();
+    if (c.chroma_sharpening_power > 1.0f)  // :1200-1208
+        for (size_t f = 0; f < F_all; f++) sharpen_chroma_inplace(chroma.data() + f * 12, c.chroma_sharpening_power);
+    if (F_all > 5) smooth_chroma_inplace(chroma, F_all, 5);  // :1211-1213
+    kv->chroma = chroma;
+    // optional edge trim (:1215-1232): the middle of the frames
+    size_t t0 = 0, F = F_all;
+    if (c.enable_key_edge_trim && energies.size() == F_all && F_all >= 200) {
+        const float frac = sd_clampf(c.key_edge_trim_fraction, 0.0f, 0.49f);
+        const size_t st = (size_t)sd_roundf((float)F_all * frac);
+        const size_t en = (size_t)sd_roundf((float)F_all * (1.0f - frac));
+        if (en > st + 50 && en <= F_all) {
+            t0 = st;
+            F = en - st;
+        }
+    }
+    if (t0 > 0 || F != F_all) {
+        chroma.erase(chroma.begin(), chroma.begin() + (long)(t0 * 12));
+        chroma.resize(F * 12);
+        energies.erase(energies.begin(), energies.begin() + (long)t0);
+        energies.resize(F);
+    }
+    kv->t0 = t0;
+    kv->frames = F;
+    // frame weights (:1236-1287)
+    std::vector<float> weights;
+    bool use_w = false;
+    if (c.enable_key_frame_weighting && F > 0 && energies.size() == F) {
+        std::vector<float> sorted(energies);
+        std::stable_sort(sorted.begin(), sorted.end(), [](float a, float b) { return a < b; });
+        const float median = sd_maxf(sorted[sorted.size() / 2], 1e-12f);
+        weights.resize(F);
+        for (size_t f = 0; f < F; f++) {
+            const float* ch = chroma.data() + f * 12;
+            float sum = 0.0f;
+            for (int i = 0; i < 12; i++) sum += ch[i];
+            float tonal = 0.0f;
+            if (!(sum <= 1e-12f)) {
+                float ent = 0.0f;
+                for (int i = 0; i < 12; i++) {
+                    const float p = ch[i] / sum;
+                    if (p > 1e-12f) ent -= p * sd_logf(p);
+                }
+                const float maxent = sd_logf(12.0f);
+                tonal = sd_clampf(1.0f - (ent / maxent), 0.0f, 1.0f);
+            }
+            if (tonal < c.key_min_tonalness) tonal = 0.0f;
+            const float e_norm = sd_maxf(energies[f] / median, 0.0f);
+            const float w_t = sd_powf(tonal, sd_maxf(c.key_tonalness_power, 0.0f));
+            const float w_e = sd_powf(e_norm, sd_maxf(c.key_energy_power, 0.0f));
+            weights[f] = sd_maxf(w_t * w_e, 0.0f);
+        }
+        use_w = true;
+        float sw = 0.0f;
+        size_t used = 0;
+        for (float w : weights) {
+            sw += w;
+            used += w > 0.0f;
+        }
+        if (sw <= 1e-12f || used < 10) use_w = false;
+    }
+    kv->weights = weights;
+    kv->weights_used = use_w;
+    float maj[12][12], mnr[12][12];
+    key_templates(maj, mnr, c.key_template_set == SDSP_TEMPLATES_TEMPERLEY ? 1 : 0);
+    ModeHeuristic mh;
+    mh.on = c.enable_key_mode_heuristic || c.enable_key_minor_harmonic_bonus;
+    mh.third_margin = c.key_mode_third_ratio_margin;
+    mh.flip_ratio = c.enable_key_mode_heuristic ? c.key_mode_flip_min_score_ratio : 0.0f;
+    mh.bonus = c.enable_key_minor_harmonic_bonus;
+    mh.bonus_w = c.key_minor_leading_tone_bonus_weight;
+    std::vector<size_t> ms_len;
+    for (uint64_t i = 0; i < c.key_multi_scale_lengths_len; i++) ms_len.push_back((size_t)c.key_multi_scale_lengths[i]);
+    std::vector<float> ms_w(c.key_multi_scale_weights, c.key_multi_scale_weights + c.key_multi_scale_weights_len);
+    const float* wp = use_w ? weights.data() : nullptr;
+    auto detect_full = [&]() {
+        return mh.on ? detect_key_weighted_mode_heuristic(chroma.data(), F, wp, maj, mnr, mh)
+                     : detect_key_weighted(chroma.data(), F, wp, maj, mnr);
+    };
+    auto table = [&](const KeyResult& r) {
+        for (int i = 0; i < 24; i++) kv->scores[i] = r.scores[i], kv->order[i] = r.order[i];
+    };
+    try {
+        KeyResult kr;
+        float clarity;
+        const size_t seg_len_cfg = (size_t)c.key_segment_len_frames;
+        const size_t ms_min = ms_len.empty() ? 1 : *std::min_element(ms_len.begin(), ms_len.end());
+        if (c.enable_key_ensemble) {  // :1289-1299
+            kr = detect_key_ensemble(chroma.data(), F, wp, c.key_ensemble_kk_weight, c.key_ensemble_temperley_weight);
+            clarity = key_clarity(kr.scores, 24);
+            table(kr);
+        } else if (c.enable_key_multi_scale && !ms_len.empty() && F >= ms_min) {  // :1304-1330
+            int used = 0;
+            if (!detect_key_multi_scale(chroma.data(), F, wp, maj, mnr, ms_len, (size_t)c.key_multi_scale_hop,
+                                        sd_clampf(c.key_multi_scale_min_clarity, 0.0f, 1.0f),
+                                        ms_w.empty() ? nullptr : &ms_w, mh, &kr, &used, &kv->n_segments))
+                kr = detect_full();
+            kv->used_segments = used;
+            clarity = key_clarity(kr.scores, 24);
+            table(kr);
+        } else if (c.enable_key_segment_voting && F >= std::max<size_t>(seg_len_cfg, 1) && seg_len_cfg >= 120 &&
+            c.key_segment_hop_frames >= 1) {
+            const size_t seg_len = std::min(seg_len_cfg, F);
+            const size_t hop = std::max<size_t>(std::min<size_t>((size_t)c.key_segment_hop_frames, seg_len), 1);
+            const float min_cl = sd_clampf(c.key_segment_min_clarity, 0.0f, 1.0f);
+            float acc[24] = {0};
+            int used = 0;
+            for (size_t st = 0; st + seg_len <= F; st += hop) {
+                KeyResult sr_ = mh.on ? detect_key_weighted_mode_heuristic(chroma.data() + st * 12, seg_len,
+                                                                           wp ? wp + st : nullptr, maj, mnr, mh)
+                                      : detect_key_weighted(chroma.data() + st * 12, seg_len, wp ? wp + st : nullptr,
+                                                            maj, mnr);
+                const float cl = key_clarity(sr_.scores, 24);
+                if (g_key_trace) g_key_trace->push_back(cl);
+                kv->n_segments++;
+                if (cl >= min_cl) {
+                    used++;
+                    for (int i = 0; i < 24; i++) acc[sr_.order[i]] += sr_.scores[i] * cl;
+                }
+            }
+            kv->used_segments = used;
+            if (used == 0) {
+                kr = detect_full();
+                clarity = key_clarity(kr.scores, 24);
+                table(kr);
+            } else {
+                int idx[24];
+                for (int i = 0; i < 24; i++) idx[i] = i;
+                std::stable_sort(idx, idx + 24, [&](int a, int b) { return acc[b] < acc[a]; });
+                float sorted[24];
+                for (int i = 0; i < 24; i++) sorted[i] = acc[idx[i]];
+                kr.mode = idx[0] < 12 ? 0 : 1;
+                kr.tonic = (uint32_t)(idx[0] % 12);
+                const float bs = sorted[0], ss = sorted[1];
+                kr.confidence = bs > 0.0f ? sd_clampf((bs - ss) / bs, 0.0f, 1.0f) : 0.0f;
+                clarity = key_clarity(sorted, 24);
+                for (int i = 0; i < 24; i++) kv->scores[i] = sorted[i], kv->order[i] = idx[i];
+            }
+        } else {
+            kr = detect_full();
+            clarity = key_clarity(kr.scores, 24);
+            table(kr);
+        }
+        kv->mode = kr.mode;
+        kv->tonic = kr.tonic;
+        kv->conf = kr.confidence;
+        kv->clarity = clarity;
+    } catch (const AErr&) {
+        kv->err = true;
+        kv->mode = 0, kv->tonic = 0, kv->conf = 0.0f, kv->clarity = 0.0f;
+    }
+}
+}  // namespace orc
+
+namespace {
+
 void analyze(const float* samples, size_t n, uint32_t sr, const sdsp_config& c, Out& o, Trace& tr) {
     if (n == 0) fail(SDSP_ERR_INVALID_INPUT, "Empty audio samples");  // lib.rs:100-110
     if (sr == 0) fail(SDSP_ERR_INVALID_INPUT, "Invalid sample rate");
@@ -550,146 +712,18 @@ void analyze(const float* samples, size_t n, uint32_t sr, const sdsp_config& c, 
             const float t = (c.enable_key_tuning_compensation && sd_absf(tuning) > 1e-6f) ? tuning : 0.0f;
             chroma_frames(ks, sr, kfft, c.soft_chroma_mapping != 0, c.soft_mapping_sigma, t, &chroma, &energies);
         }
-        const size_t F_all = energies.size();
-        if (c.chroma_sharpening_power > 1.0f)  // :1200-1208
-            for (size_t f = 0; f < F_all; f++) sharpen_chroma_inplace(chroma.data() + f * 12, c.chroma_sharpening_power);
-        if (F_all > 5) smooth_chroma_inplace(chroma, F_all, 5);  // :1211-1213
-        tr.chroma = chroma;
+        // sharpening, smoothing, trim, weights and the vote (:1200-1470)
+        KeyVote kv;
+        key_vote(chroma, energies, c, &kv);
+        tr.chroma = kv.chroma;
         tr.energies = energies;
-        // optional edge trim (:1215-1232): the middle of the frames
-        size_t t0 = 0, F = F_all;
-        if (c.enable_key_edge_trim && energies.size() == F_all && F_all >= 200) {
-            const float frac = sd_clampf(c.key_edge_trim_fraction, 0.0f, 0.49f);
-            const size_t st = (size_t)sd_roundf((float)F_all * frac);
-            const size_t en = (size_t)sd_roundf((float)F_all * (1.0f - frac));
-            if (en > st + 50 && en <= F_all) {
-                t0 = st;
-                F = en - st;
-            }
-        }
-        if (t0 > 0 || F != F_all) {
-            chroma.erase(chroma.begin(), chroma.begin() + (long)(t0 * 12));
-            chroma.resize(F * 12);
-            energies.erase(energies.begin(), energies.begin() + (long)t0);
-            energies.resize(F);
-        }
-        // frame weights (:1236-1287)
-        std::vector<float> weights;
-        bool use_w = false;
-        if (c.enable_key_frame_weighting && F > 0 && energies.size() == F) {
-            std::vector<float> sorted(energies);
-            std::stable_sort(sorted.begin(), sorted.end(), [](float a, float b) { return a < b; });
-            const float median = sd_maxf(sorted[sorted.size() / 2], 1e-12f);
-            weights.resize(F);
-            for (size_t f = 0; f < F; f++) {
-                const float* ch = chroma.data() + f * 12;
-                float sum = 0.0f;
-                for (int i = 0; i < 12; i++) sum += ch[i];
-                float tonal = 0.0f;
-                if (!(sum <= 1e-12f)) {
-                    float ent = 0.0f;
-                    for (int i = 0; i < 12; i++) {
-                        const float p = ch[i] / sum;
-                        if (p > 1e-12f) ent -= p * sd_logf(p);
-                    }
-                    const float maxent = sd_logf(12.0f);
-                    tonal = sd_clampf(1.0f - (ent / maxent), 0.0f, 1.0f);
-                }
-                if (tonal < c.key_min_tonalness) tonal = 0.0f;
-                const float e_norm = sd_maxf(energies[f] / median, 0.0f);
-                const float w_t = sd_powf(tonal, sd_maxf(c.key_tonalness_power, 0.0f));
-                const float w_e = sd_powf(e_norm, sd_maxf(c.key_energy_power, 0.0f));
-                weights[f] = sd_maxf(w_t * w_e, 0.0f);
-            }
-            use_w = true;
-            float sw = 0.0f;
-            size_t used = 0;
-            for (float w : weights) {
-                sw += w;
-                used += w > 0.0f;
-            }
-            if (sw <= 1e-12f || used < 10) use_w = false;
-        }
-        tr.weights = weights;
-        tr.weights_used = use_w;
-        float maj[12][12], mnr[12][12];
-        key_templates(maj, mnr, c.key_template_set == SDSP_TEMPLATES_TEMPERLEY ? 1 : 0);
-        ModeHeuristic mh;
-        mh.on = c.enable_key_mode_heuristic || c.enable_key_minor_harmonic_bonus;
-        mh.third_margin = c.key_mode_third_ratio_margin;
-        mh.flip_ratio = c.enable_key_mode_heuristic ? c.key_mode_flip_min_score_ratio : 0.0f;
-        mh.bonus = c.enable_key_minor_harmonic_bonus;
-        mh.bonus_w = c.key_minor_leading_tone_bonus_weight;
-        std::vector<size_t> ms_len;
-        for (uint64_t i = 0; i < c.key_multi_scale_lengths_len; i++) ms_len.push_back((size_t)c.key_multi_scale_lengths[i]);
-        std::vector<float> ms_w(c.key_multi_scale_weights, c.key_multi_scale_weights + c.key_multi_scale_weights_len);
-        const float* wp = use_w ? weights.data() : nullptr;
-        auto detect_full = [&]() {
-            return mh.on ? detect_key_weighted_mode_heuristic(chroma.data(), F, wp, maj, mnr, mh)
-                         : detect_key_weighted(chroma.data(), F, wp, maj, mnr);
-        };
-        try {
-            KeyResult kr;
-            float clarity;
-            const size_t seg_len_cfg = (size_t)c.key_segment_len_frames;
-            const size_t ms_min = ms_len.empty() ? 1 : *std::min_element(ms_len.begin(), ms_len.end());
-            if (c.enable_key_ensemble) {  // :1289-1299
-                kr = detect_key_ensemble(chroma.data(), F, wp, c.key_ensemble_kk_weight, c.key_ensemble_temperley_weight);
-                clarity = key_clarity(kr.scores, 24);
-            } else if (c.enable_key_multi_scale && !ms_len.empty() && F >= ms_min) {  // :1304-1330
-                int used = 0;
-                if (!detect_key_multi_scale(chroma.data(), F, wp, maj, mnr, ms_len, (size_t)c.key_multi_scale_hop,
-                                            sd_clampf(c.key_multi_scale_min_clarity, 0.0f, 1.0f),
-                                            ms_w.empty() ? nullptr : &ms_w, mh, &kr, &used))
-                    kr = detect_full();
-                tr.used_segments = used;
-                clarity = key_clarity(kr.scores, 24);
-            } else if (c.enable_key_segment_voting && F >= std::max<size_t>(seg_len_cfg, 1) && seg_len_cfg >= 120 &&
-                c.key_segment_hop_frames >= 1) {
-                const size_t seg_len = std::min(seg_len_cfg, F);
-                const size_t hop = std::max<size_t>(std::min<size_t>((size_t)c.key_segment_hop_frames, seg_len), 1);
-                const float min_cl = sd_clampf(c.key_segment_min_clarity, 0.0f, 1.0f);
-                float acc[24] = {0};
-                int used = 0;
-                for (size_t st = 0; st + seg_len <= F; st += hop) {
-                    KeyResult sr_ = mh.on ? detect_key_weighted_mode_heuristic(chroma.data() + st * 12, seg_len,
-                                                                               wp ? wp + st : nullptr, maj, mnr, mh)
-                                          : detect_key_weighted(chroma.data() + st * 12, seg_len, wp ? wp + st : nullptr,
-                                                                maj, mnr);
-                    const float cl = key_clarity(sr_.scores, 24);
-                    if (g_key_trace) g_key_trace->push_back(cl);
-                    if (cl >= min_cl) {
-                        used++;
-                        for (int i = 0; i < 24; i++) acc[sr_.order[i]] += sr_.scores[i] * cl;
-                    }
-                }
-                tr.used_segments = used;
-                if (used == 0) {
-                    kr = detect_full();
-                    clarity = key_clarity(kr.scores, 24);
-                } else {
-                    int idx[24];
-                    for (int i = 0; i < 24; i++) idx[i] = i;
-                    std::stable_sort(idx, idx + 24, [&](int a, int b) { return acc[b] < acc[a]; });
-                    float sorted[24];
-                    for (int i = 0; i < 24; i++) sorted[i] = acc[idx[i]];
-                    kr.mode = idx[0] < 12 ? 0 : 1;
-                    kr.tonic = (uint32_t)(idx[0] % 12);
-                    const float bs = sorted[0], ss = sorted[1];
-                    kr.confidence = bs > 0.0f ? sd_clampf((bs - ss) / bs, 0.0f, 1.0f) : 0.0f;
-                    clarity = key_clarity(sorted, 24);
-                }
-            } else {
-                kr = detect_full();
-                clarity = key_clarity(kr.scores, 24);
-            }
-            o.key_mode = kr.mode;
-            o.key_tonic = kr.tonic;
-            o.key_conf = kr.confidence;
-            o.key_clarity = clarity;
-        } catch (const AErr&) {
-            o.key_mode = 0, o.key_tonic = 0, o.key_conf = 0.0f, o.key_clarity = 0.0f;
-        }
+        tr.weights = kv.weights;
+        tr.weights_used = kv.weights_used;
+        tr.used_segments = kv.used_segments;
+        o.key_mode = kv.mode;
+        o.key_tonic = kv.tonic;
+        o.key_conf = kv.conf;
+        o.key_clarity = kv.clarity;
     }
 
     // warnings / flags (:1564-1589)
@@ -895,6 +929,42 @@ int32_t sdsp_oracle_key_stages(float* spec, uint64_t frames, uint64_t bins, uint
     std::memcpy(chroma, ch.data(), ch.size() * sizeof(float));
     std::memcpy(energies, en.data(), en.size() * sizeof(float));
     return 0;
+}
+
+// Key vote export (tests/test_gpu_key_vote.py): analyze's own key_vote over raw chroma rows
+// (frames x 12) and frame energies.  info = {err, mode, tonic, used_segments, weights_used, slice
+// start, slice frames, weights written,
+// segments evaluated}; cc = {confidence, clarity}; chroma_s (frames x 12) the
+// sharpened and smoothed rows; weights (frames capacity) over the slice; scores / order the final
+// sorted table.  With the key trace on (sdsp_oracle_study_key_trace) the trace holds the call's
+// raw scores and segment clarities.
+int32_t sdsp_oracle_key_vote(const float* chroma, const float* energies, uint64_t frames, const sdsp_config* c,
+                             int32_t info[9], float cc[2], float* chroma_s, float* weights, float scores[24],
+                             int32_t order[24]) {
+    if (!c || (frames && (!chroma || !energies))) return -1;
+    KeyVote kv;
+    key_vote(std::vector<float>(chroma, chroma + frames * 12), std::vector<float>(energies, energies + frames), *c, &kv);
+    info[0] = kv.err;
+    info[1] = kv.mode;
+    info[2] = (int32_t)kv.tonic;
+    info[3] = kv.used_segments;
+    info[4] = kv.weights_used;
+    info[5] = (int32_t)kv.t0;
+    info[6] = (int32_t)kv.frames;
+    info[7] = (int32_t)kv.weights.size();
+    info[8] = kv.n_segments;
+    cc[0] = kv.conf;
+    cc[1] = kv.clarity;
+    if (!kv.chroma.empty()) std::memcpy(chroma_s, kv.chroma.data(), kv.chroma.size() * sizeof(float));
+    if (!kv.weights.empty()) std::memcpy(weights, kv.weights.data(), kv.weights.size() * sizeof(float));
+    for (int i = 0; i < 24; i++) scores[i] = kv.scores[i], order[i] = kv.order[i];
+    return 0;
+}
+
+// detect_key_weighted from its raw scores on: the sorted refined table and its key indices
+void sdsp_oracle_key_from_raw(const float raw[24], float scores[24], int32_t order[24]) {
+    const KeyResult r = key_from_raw(raw);
+    for (int i = 0; i < 24; i++) scores[i] = r.scores[i], order[i] = r.order[i];
 }
 
 // combined full-band novelty of an STFT magnitude array (frames x bins), default band cfg

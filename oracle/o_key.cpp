@@ -222,6 +222,13 @@ KeyResult detect_key_weighted(const float* ch, size_t frames, const float* w, co
     for (int k = 0; k < 12; k++) sc[k] = weighted_sum_dot(ch, frames, w, maj[k]);
     for (int k = 0; k < 12; k++) sc[12 + k] = weighted_sum_dot(ch, frames, w, mnr[k]);
     if (g_key_trace) g_key_trace->insert(g_key_trace->end(), sc, sc + 24);
+    return key_from_raw(sc);
+}
+
+// detector.rs:160-313: the raw scores' per-mode normalisation, circle-of-fifths refinement and sort
+KeyResult key_from_raw(const float raw[24]) {
+    float sc[24];
+    for (int k = 0; k < 24; k++) sc[k] = raw[k];
     float mM = 0.0f, mm = 0.0f;
     for (int k = 0; k < 12; k++) mM = sd_maxf(mM, sc[k]);
     for (int k = 0; k < 12; k++) mm = sd_maxf(mm, sc[12 + k]);
@@ -442,8 +449,9 @@ KeyResult detect_key_ensemble(const float* ch, size_t frames, const float* w, fl
 bool detect_key_multi_scale(const float* ch, size_t frames, const float* w, const float maj[12][12],
                             const float mnr[12][12], const std::vector<size_t>& lengths, size_t hop_in, float min_cl,
                             const std::vector<float>* scale_w, const ModeHeuristic& mh, KeyResult* out,
-                            int* used_segments) {
+                            int* used_segments, int* n_segments) {
     float acc[24] = {0};
+    int nseg = 0;
     float total_w = 0.0f;
     int used = 0;
     const size_t hop = std::max<size_t>(hop_in, 1);
@@ -457,6 +465,8 @@ bool detect_key_multi_scale(const float* ch, size_t frames, const float* w, cons
                                                                            mnr, mh)
                                       : detect_key_weighted(ch + st * 12, len, w ? w + st : nullptr, maj, mnr);
             const float cl = key_clarity(r.scores, 24);
+            if (g_key_trace) g_key_trace->push_back(cl);
+            nseg++;
             if (cl >= min_cl) {
                 used++;
                 const float cw = cl * sw;
@@ -466,6 +476,7 @@ bool detect_key_multi_scale(const float* ch, size_t frames, const float* w, cons
         }
     }
     *used_segments = used;
+    if (n_segments) *n_segments = nseg;
     if (used == 0 || total_w <= 1e-12f) return false;
     for (int k = 0; k < 24; k++) acc[k] /= total_w;
     *out = from_table(acc);

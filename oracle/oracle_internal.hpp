@@ -180,6 +180,7 @@ struct KeyResult {
 void key_templates(float major[12][12], float minor[12][12], int template_set = 0);
 KeyResult detect_key_weighted(const float* chroma, size_t frames, const float* weights,
                               const float maj[12][12], const float min[12][12]);
+KeyResult key_from_raw(const float raw[24]);  // detect_key_weighted after its 24 weighted template sums
 float key_clarity(const float* sorted_scores, int n);
 void sharpen_chroma_inplace(float* ch12, float power);
 struct ModeHeuristic {
@@ -196,7 +197,27 @@ KeyResult detect_key_ensemble(const float* chroma, size_t frames, const float* w
 bool detect_key_multi_scale(const float* chroma, size_t frames, const float* weights, const float maj[12][12],
                             const float min[12][12], const std::vector<size_t>& lengths, size_t hop, float min_clarity,
                             const std::vector<float>* scale_weights, const ModeHeuristic& mh, KeyResult* out,
-                            int* used_segments);
+                            int* used_segments, int* n_segments = nullptr);  // n_segments: those evaluated
+
+// The key decision analyze makes from its chroma front-end's output (src/lib.rs:1200-1470): chroma
+// sharpening, median smoothing, edge trim, frame weights, then the ensemble / multi-scale /
+// segment-voting / full-slice branch the configuration selects.  chroma: raw rows (frames x 12),
+// energies: one per frame.  err: the reference's Err path (all-zero key fields).
+struct KeyVote {
+    bool err = false;
+    int mode = 0;
+    uint32_t tonic = 0;
+    float conf = 0.0f, clarity = 0.0f;
+    int used_segments = 0;
+    int n_segments = 0;  // segments evaluated (multi-scale or segment voting)
+    bool weights_used = false;
+    size_t t0 = 0, frames = 0;   // the voted slice [t0, t0 + frames) of the rows (the edge trim's)
+    std::vector<float> chroma;   // sharpened and smoothed, every row
+    std::vector<float> weights;  // over the slice; empty without frame weighting
+    float scores[24] = {0};      // the final table, descending ...
+    int order[24] = {0};         // ... and the key index of each entry
+};
+void key_vote(std::vector<float> chroma, std::vector<float> energies, const sdsp_config& c, KeyVote* out);
 
 // ---------- unit probes (o_*.cpp "unit probes" sections; tests/test_oracle_units_*.py) ----------
 // Entry points at the granularity of the reference's own unit tests.  A probe returns a count /
@@ -206,8 +227,8 @@ extern std::string g_probe_err;
 // Study switches (tools/key_near_study.py; never set by the parity tests): g_block_energy folds
 // each HPCP frame energy in 64-bin blocks the way the GPU's default key path does (k_mask_rp /
 // k_hpcp_band) instead of the reference's one sequential sum; g_key_trace, when
-// non-null, receives per detect_key_weighted call its 24 raw scores and, in segment voting, the
-// segment's clarity after them.
+// non-null, receives per detect_key_weighted call its 24 raw scores and, in segment voting and
+// multi-scale detection, the segment's clarity after them (sdsp_oracle_key_vote returns it too).
 extern int g_block_energy;
 extern std::vector<float>* g_key_trace;
 template <class F>

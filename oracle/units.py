@@ -472,3 +472,57 @@ def key_stages(spec, sample_rate=44100, config=None):
     if L.sdsp_oracle_key_stages(_p(m), m.shape[0], m.shape[1], sample_rate, C.byref(cfg), _p(ch), _p(en)) != 0:
         raise AnalysisError(1, "key_stages: empty spectrogram")
     return m, ch, en
+
+
+def key_from_raw(raw):
+    """detect_key_weighted from its 24 raw scores on: (sorted refined scores, their key indices)."""
+    L = lib()
+    L.sdsp_oracle_key_from_raw.argtypes = [fp, fp, i32p]
+    L.sdsp_oracle_key_from_raw.restype = None
+    r = _f32(raw)
+    sc, ks = np.zeros(24, np.float32), np.zeros(24, np.int32)
+    L.sdsp_oracle_key_from_raw(_p(r), _p(sc), ks.ctypes.data_as(i32p))
+    return sc, ks
+
+
+def key_vote(chroma, energies, config=None):
+    """analyze's key decision over raw chroma rows (F, 12) and frame energies (F,): a dict with key
+    (mode * 12 + tonic), mode, tonic, confidence, clarity, used_segments, weights_used, err (the
+    reference's Err path: all-zero key fields), chroma_s (F, 12) sharpened and smoothed, t0 / frames
+    (the voted slice), weights (over the slice; empty without frame weighting), tab / order (the
+    final sorted table), seg_raw (n, 24) / seg_clarity (n,) per voted-on segment in order and
+    full_raw (m, 24): the raw scores of every other detect_key_weighted call (the full slice's, the
+    ensemble's two)."""
+    L = lib()
+    L.sdsp_oracle_key_vote.argtypes = [fp, fp, C.c_uint64, C.POINTER(oracle.SdspConfig), i32p, fp, fp, fp, fp, i32p]
+    L.sdsp_oracle_key_vote.restype = C.c_int32
+    L.sdsp_oracle_study_key_trace_get.restype = C.c_uint64
+    L.sdsp_oracle_study_key_trace_get.argtypes = [fp, C.c_uint64]
+    cfg = config if config is not None else oracle.default_config()
+    ch = np.ascontiguousarray(chroma, dtype=np.float32).reshape(-1, 12)
+    en = np.ascontiguousarray(energies, dtype=np.float32).reshape(-1)
+    if ch.shape[0] != en.size:
+        raise ValueError("key_vote: one energy per chroma row")
+    F = en.size
+    info, cc = np.zeros(9, np.int32), np.zeros(2, np.float32)
+    cs, w = np.zeros((max(F, 1), 12), np.float32), np.zeros(max(F, 1), np.float32)
+    tab, order = np.zeros(24, np.float32), np.zeros(24, np.int32)
+    L.sdsp_oracle_study_key_trace(1)
+    try:
+        rc = L.sdsp_oracle_key_vote(_p(ch), _p(en), F, C.byref(cfg), info.ctypes.data_as(i32p), _p(cc), _p(cs), _p(w),
+                                    _p(tab), order.ctypes.data_as(i32p))
+        n = int(L.sdsp_oracle_study_key_trace_get(None, 0))
+        tr = np.zeros(max(n, 1), np.float32)
+        L.sdsp_oracle_study_key_trace_get(_p(tr), n)
+    finally:
+        L.sdsp_oracle_study_key_trace(0)
+    if rc != 0:
+        raise AnalysisError(1, "key_vote: bad arguments")
+    tr = tr[:n]
+    nseg = int(info[8])  # segments come first, 24 raw scores and a clarity each; whole-slice calls (24 each) follow
+    seg = tr[:nseg * 25].reshape(nseg, 25)
+    return {"err": bool(info[0]), "mode": int(info[1]), "tonic": int(info[2]), "key": int(info[1]) * 12 + int(info[2]),
+            "confidence": cc[0], "clarity": cc[1], "used_segments": int(info[3]), "weights_used": bool(info[4]),
+            "t0": int(info[5]), "frames": int(info[6]), "chroma_s": cs[:F], "weights": w[:int(info[7])].copy(),
+            "tab": tab, "order": order, "seg_raw": seg[:, :24].copy(), "seg_clarity": seg[:, 24].copy(),
+            "full_raw": tr[nseg * 25:].reshape(-1, 24).copy()}

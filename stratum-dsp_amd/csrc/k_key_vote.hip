@@ -958,8 +958,16 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(4))) void k_
 void launch_key_vote(const int* tracks, int n_items, const uint64_t* frame_pfx, float* chroma_raw,
                      const float* energy, float* chroma_s, float* weights, float* seg_scratch, const uint64_t* seg_off,
                      const float* tmpl, const KeyParams& P, KeyOut* out, hipStream_t st, KeyDbg* dbg,
-                     const float* edel, float* wdel, bool alone) {
+                     const float* edel, float* wdel, bool alone, int force_threads) {
     if (n_items == 0) return;
+    // force_threads (the stage probe's, include/stratum_hip_debug.h): that instantiation, whatever
+    // the launch; 0 is the selection below
+    if (force_threads == 1024 || force_threads == 512 || force_threads == KV_THREADS) {
+        auto* k = force_threads == 1024 ? k_key_vote<1024> : force_threads == 512 ? k_key_vote<512> : k_key_vote<KV_THREADS>;
+        hipLaunchKernelGGL(k, dim3(n_items), dim3(force_threads), 0, st, tracks, n_items, frame_pfx, chroma_raw, energy,
+                           chroma_s, weights, seg_scratch, seg_off, tmpl, P, out, dbg, edel, wdel);
+        return;
+    }
     // a few tracks (the exact reruns of near-decision tracks, one-track calls) or a launch with
     // nothing beside it (the call's last sub-batch, `alone`): the latency of one track's workgroup
     // is the launch, and 1024 threads cut it (the segment scores in one round instead of three);

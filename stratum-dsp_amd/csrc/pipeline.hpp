@@ -443,6 +443,9 @@ class Pipeline {
                             sdsp_debug_tempo_out* out);
     void debug_key_stages(const float* host_mags, const uint64_t* frames, uint64_t n_tracks, int mode, float* masked,
                           float* chroma, float* energy, float* edel, int32_t info[4]);
+    void debug_key_vote(const float* host_chroma, const float* host_energy, const float* host_edel,
+                        const uint64_t* frames, uint64_t n_tracks, const int32_t* sel, uint64_t n_sel, int threads,
+                        bool alone, bool cert_fixed, sdsp_debug_key_vote_out* out);
     void debug_onset_stages(const float* rms, const float* hfc, const float* sfo, const float* hpe,
                             const uint64_t* frames, const uint64_t* n_trim, uint64_t n_tracks, int hop,
                             sdsp_debug_onset_out* out);

@@ -615,6 +615,26 @@ int32_t sdsp_debug_key_stages(const float* host_mags, const uint64_t* frames, ui
     });
 }
 
+int32_t sdsp_debug_key_vote(const float* host_chroma, const float* host_energy, const float* host_edel,
+                            const uint64_t* frames, uint64_t n_tracks, const int32_t* sel, uint64_t n_sel,
+                            uint32_t sample_rate, const sdsp_config* cfg, int32_t threads, int32_t alone,
+                            int32_t cert_fixed, sdsp_debug_key_vote_out* out, int32_t device) {
+    if (!host_chroma || !host_energy || !frames || !cfg || !out || n_tracks == 0 || n_tracks > (1u << 20) ||
+        sample_rate == 0 || (threads != 0 && threads != 256 && threads != 512 && threads != 1024) ||
+        (sel == nullptr) != (n_sel == 0) || n_sel > n_tracks)
+        return SDSP_ERR_INVALID_INPUT;
+    if (!out->key || !out->chroma_s || !out->weights || !out->seg_rows || !out->seg_row_pfx || !out->dbg ||
+        (host_edel && !out->wdel))
+        return SDSP_ERR_INVALID_INPUT;
+    for (uint64_t t = 0; t < n_tracks; t++)
+        if (frames[t] == 0 || frames[t] > (1u << 24)) return SDSP_ERR_INVALID_INPUT;
+    return run_stage_probe("sdsp_debug_key_vote", device, [&](DeviceCtx& d) {
+        Pipeline p(d, *cfg, sample_rate, SDSP_STAGES_FULL, false, false, false, true);
+        p.debug_key_vote(host_chroma, host_energy, host_edel, frames, n_tracks, sel, n_sel, threads, alone != 0,
+                         cert_fixed != 0, out);
+    });
+}
+
 int32_t sdsp_debug_onset_stages(const float* rms, const float* hfc, const float* sfo, const float* hpe,
                                 const uint64_t* frames, const uint64_t* n_trim, uint64_t n_tracks, uint32_t sample_rate,
                                 uint32_t hop, const sdsp_config* cfg, sdsp_debug_onset_out* out, int32_t device) {

@@ -366,6 +366,76 @@ void Pipeline::debug_key_stages(const float* host_mags, const uint64_t* frames, 
     c_.sync();
 }
 
+// sdsp_debug_key_vote: the vote launch of launch_key (all tracks) or rerun_tail (a selection) over
+// uploaded chroma rows and energies, then every buffer the kernel wrote back to the host.
+void Pipeline::debug_key_vote(const float* host_chroma, const float* host_energy, const float* host_edel,
+                              const uint64_t* frames, uint64_t n_tracks, const int32_t* sel, uint64_t n_sel, int threads,
+                              bool alone, bool cert_fixed, sdsp_debug_key_vote_out* out) {
+    static_assert(sizeof(sdsp_debug_key_out) == sizeof(KeyOut) && sizeof(sdsp_debug_key_dbg) == sizeof(KeyDbg),
+                  "the probe's records mirror the kernel's");
+    if (const std::string why = check_supported(cfg_, sr_); !why.empty()) throw HipError(why);
+    KeyParams kp = key_vote_params(cfg_, host_edel != nullptr);
+    kp.cert_fixed = cert_fixed ? 1 : 0;
+    std::vector<uint64_t> kpfx(1, 0);
+    for (uint64_t t = 0; t < n_tracks; t++) kpfx.push_back(kpfx.back() + frames[t]);
+    const uint64_t total = kpfx.back();
+    std::vector<int> items;
+    if (sel) {
+        std::vector<char> seen((size_t)n_tracks, 0);
+        for (uint64_t j = 0; j < n_sel; j++) {
+            if (sel[j] < 0 || (uint64_t)sel[j] >= n_tracks || seen[(size_t)sel[j]]) throw std::invalid_argument("selection");
+            seen[(size_t)sel[j]] = 1;
+            items.push_back(sel[j]);
+        }
+    } else {
+        for (uint64_t t = 0; t < n_tracks; t++) items.push_back((int)t);
+    }
+    const int n_items = (int)items.size();
+    // the segment scratch as launch_key sizes it, compact by item as rerun_tail's
+    std::vector<uint64_t> kseg(1, 0);
+    for (int k : items) kseg.push_back(kseg.back() + (uint64_t)KV_ROW * seg_rows(kp, frames[(size_t)k]));
+    if (kseg.back() / KV_ROW > out->seg_rows_cap) throw std::invalid_argument("capacity");
+    for (size_t i = 0; i < kseg.size(); i++) out->seg_row_pfx[i] = kseg[i] / KV_ROW;
+    if (n_items == 0) return;
+    hipStream_t st = d_.stream;
+    // the kernel sharpens the raw rows in place: a copy of the caller's
+    float* d_cr = c_.up("V.chroma", std::vector<float>(host_chroma, host_chroma + total * 12));
+    float* d_en = c_.up("V.energy", std::vector<float>(host_energy, host_energy + total));
+    float* d_edel = host_edel ? c_.up("V.edel", std::vector<float>(host_edel, host_edel + total)) : nullptr;
+    uint64_t* d_kpfx = c_.up("V.kpfx", kpfx);
+    uint64_t* d_kseg = c_.up("V.kseg", kseg);
+    int* d_items = c_.up("V.items", items);
+    std::vector<float> tpl(576);
+    key_templates(tpl.data());
+    float* d_tpl = c_.up("V.tpl", tpl);
+    const KeyOut* in_ko = reinterpret_cast<const KeyOut*>(out->key);
+    KeyOut* d_ko = c_.up("V.kout", std::vector<KeyOut>(in_ko, in_ko + n_tracks));
+    const size_t n_scr = (size_t)std::max<uint64_t>(kseg.back(), 1);
+    float* d_cs = c_.dev<float>("V.chroma_s", total * 12);
+    float* d_w = c_.dev<float>("V.weights", total);
+    float* d_wdel = host_edel ? c_.dev<float>("V.wdel", total) : nullptr;
+    float* d_scr = c_.dev<float>("V.segscr", n_scr);
+    KeyDbg* d_dbg = c_.dev<KeyDbg>("V.kdbg", (size_t)n_items);
+    SDSP_HIP_CHECK(hipMemsetAsync(d_cs, 0, total * 12 * sizeof(float), st));
+    SDSP_HIP_CHECK(hipMemsetAsync(d_w, 0, total * sizeof(float), st));
+    if (d_wdel) SDSP_HIP_CHECK(hipMemsetAsync(d_wdel, 0, total * sizeof(float), st));
+    SDSP_HIP_CHECK(hipMemsetAsync(d_scr, 0, n_scr * sizeof(float), st));
+    SDSP_HIP_CHECK(hipMemsetAsync(d_dbg, 0, (size_t)n_items * sizeof(KeyDbg), st));
+    launch_key_vote(d_items, n_items, d_kpfx, d_cr, d_en, d_cs, d_w, d_scr, d_kseg, d_tpl, kp, d_ko, st, d_dbg, d_edel,
+                    d_wdel, alone, threads);
+    SDSP_HIP_CHECK(hipGetLastError());
+    auto get = [&](const void* d, void* h, size_t bytes) {
+        if (bytes) SDSP_HIP_CHECK(hipMemcpyAsync(h, d, bytes, hipMemcpyDeviceToHost, st));
+    };
+    get(d_ko, out->key, (size_t)n_tracks * sizeof(KeyOut));
+    get(d_cs, out->chroma_s, (size_t)total * 12 * sizeof(float));
+    get(d_w, out->weights, (size_t)total * sizeof(float));
+    if (d_wdel && out->wdel) get(d_wdel, out->wdel, (size_t)total * sizeof(float));
+    get(d_scr, out->seg_rows, (size_t)kseg.back() * sizeof(float));
+    get(d_dbg, out->dbg, (size_t)n_items * sizeof(KeyDbg));
+    c_.sync();
+}
+
 // sdsp_debug_onset_stages: onset_lists over uploaded curves, then every list back to the host.
 void Pipeline::debug_onset_stages(const float* rms, const float* hfc, const float* sfo, const float* hpe,
                                   const uint64_t* frames, const uint64_t* n_trim, uint64_t n_tracks, int hop,

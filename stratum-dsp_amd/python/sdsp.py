@@ -863,6 +863,108 @@ def debug_tempo_stages(specs, sample_rate=44100, hop=512, config=None, device=0)
     return meta, tracks
 
 
+KV_ROW = 128  # floats per segment scratch row of the key vote (csrc/kernels.hpp)
+
+
+class SdspDebugKeyOut(C.Structure):
+    _fields_ = [("mode", C.c_int32), ("tonic", C.c_int32), ("conf", C.c_float), ("clarity", C.c_float),
+                ("ok", C.c_int32), ("used_segments", C.c_int32), ("weights_used", C.c_int32), ("near", C.c_int32)]
+
+
+class SdspDebugKeyDbg(C.Structure):
+    _fields_ = [("tab", C.c_float * 24), ("order", C.c_int32 * 24), ("key", C.c_int32), ("agg", C.c_float * 12),
+                ("frames", C.c_int32), ("used", C.c_int32)]
+
+
+class SdspDebugKeyVoteOut(C.Structure):
+    _fields_ = [("key", C.POINTER(SdspDebugKeyOut)), ("chroma_s", C.POINTER(C.c_float)),
+                ("weights", C.POINTER(C.c_float)), ("wdel", C.POINTER(C.c_float)), ("seg_rows", C.POINTER(C.c_float)),
+                ("seg_row_pfx", C.POINTER(C.c_uint64)), ("seg_rows_cap", C.c_uint64), ("dbg", C.POINTER(SdspDebugKeyDbg))]
+
+
+def _key_vote_rows_bound(cfg, F):
+    """An upper bound of the vote's segment scratch rows for an F-row track (the pipeline's own
+    sizing is checked by the probe against the capacity this gives)."""
+    ns = 0
+    if cfg.enable_key_segment_voting and cfg.key_segment_len_frames >= 120 and cfg.key_segment_hop_frames >= 1:
+        L = max(int(cfg.key_segment_len_frames), 1)
+        hop = max(min(int(cfg.key_segment_hop_frames), L), 1)
+        ns = (F - L) // hop + 1 if F >= L else 0
+    nm = 0
+    if cfg.enable_key_multi_scale:
+        hop = max(int(cfg.key_multi_scale_hop), 1)
+        for j in range(int(cfg.key_multi_scale_lengths_len)):
+            L = int(cfg.key_multi_scale_lengths[j])
+            if L != 0 and L <= F:
+                nm += (F - L) // hop + 1
+    return max(ns, nm)
+
+
+def debug_key_vote(tracks, edel=None, sel=None, config=None, threads=0, alone=False, cert_fixed=False, sample_rate=44100,
+                   device=0):
+    """The key vote over host chroma rows and frame energies (sdsp_debug_key_vote).  tracks: one
+    (chroma (F, 12), energy (F,)) pair per track; edel: None (the exact path's launch) or one (F,)
+    array of relative energy bounds per track (the band path's launch with its certificate); sel:
+    None or the track indices to vote on.  Returns one dict per track: the KeyOut fields (mode,
+    tonic, key, conf, clarity, ok, used_segments, weights_used, near; key = -1 and ok = -1 for a track
+    outside sel, whose record the probe left as it was), chroma_s (F, 12), weights (F,), wdel (F,;
+    with edel), and for a voted track rows (n, 128; the segment scratch rows sized for it) and dbg
+    (tab, order, key, agg, frames, used)."""
+    cfg = config if config is not None else default_config()
+    T = len(tracks)
+    frames = np.array([np.asarray(c).reshape(-1, 12).shape[0] for c, _ in tracks], np.uint64)
+    total = int(frames.sum())
+    ch = np.ascontiguousarray(np.concatenate([np.asarray(c, np.float32).reshape(-1, 12) for c, _ in tracks]))
+    en = np.ascontiguousarray(np.concatenate([np.asarray(e, np.float32).reshape(-1) for _, e in tracks]))
+    if en.size != total:
+        raise ValueError("one energy per chroma row")
+    ed = None
+    if edel is not None:
+        ed = np.ascontiguousarray(np.concatenate([np.asarray(e, np.float32).reshape(-1) for e in edel]))
+        if ed.size != total:
+            raise ValueError("one energy bound per chroma row")
+    items = list(range(T)) if sel is None else [int(s) for s in sel]
+    sel_a = None if sel is None else np.ascontiguousarray(items, dtype=np.int32)
+    cap = sum(_key_vote_rows_bound(cfg, int(frames[k])) for k in items if 0 <= k < T)
+    key = (SdspDebugKeyOut * T)()
+    for t in range(T):  # a sentinel the kernel never writes: untouched records stay recognisable
+        key[t].mode, key[t].ok = -1, -1
+    dbg = (SdspDebugKeyDbg * max(len(items), 1))()
+    cs, w = np.zeros((total, 12), np.float32), np.zeros(total, np.float32)
+    wd = np.zeros(total, np.float32)
+    rows = np.zeros((max(cap, 1), KV_ROW), np.float32)
+    pfx = np.zeros(len(items) + 1, np.uint64)
+    out = SdspDebugKeyVoteOut(key, _fp(cs), _fp(w), _fp(wd), _fp(rows), pfx.ctypes.data_as(C.POINTER(C.c_uint64)), cap, dbg)
+    f = lib().sdsp_debug_key_vote
+    fp, u64p = C.POINTER(C.c_float), C.POINTER(C.c_uint64)
+    f.argtypes = [fp, fp, fp, u64p, C.c_uint64, C.POINTER(C.c_int32), C.c_uint64, C.c_uint32, C.POINTER(SdspConfig),
+                  C.c_int32, C.c_int32, C.c_int32, C.POINTER(SdspDebugKeyVoteOut), C.c_int32]
+    f.restype = C.c_int32
+    st = f(_fp(ch), _fp(en), _fp(ed) if ed is not None else None, frames.ctypes.data_as(u64p), T,
+           sel_a.ctypes.data_as(C.POINTER(C.c_int32)) if sel_a is not None and sel_a.size else None,
+           0 if sel_a is None else sel_a.size, sample_rate, C.byref(cfg), threads, int(bool(alone)), int(bool(cert_fixed)),
+           C.byref(out), device)
+    if st != 0:
+        raise AnalysisError(st, "debug_key_vote failed")
+    res, g0 = [], 0
+    for t in range(T):
+        sl = slice(g0, g0 + int(frames[t]))
+        k = key[t]
+        d = dict(mode=k.mode, tonic=k.tonic, key=k.mode * 12 + k.tonic if k.mode >= 0 else -1,
+                 conf=np.float32(k.conf), clarity=np.float32(k.clarity), ok=k.ok, used_segments=k.used_segments,
+                 weights_used=k.weights_used, near=k.near, chroma_s=cs[sl].copy(), weights=w[sl].copy())
+        if ed is not None:
+            d["wdel"] = wd[sl].copy()
+        res.append(d)
+        g0 += int(frames[t])
+    for i, t in enumerate(items):
+        g = dbg[i]
+        res[t]["rows"] = rows[int(pfx[i]):int(pfx[i + 1])].copy()
+        res[t]["dbg"] = dict(tab=np.array(g.tab[:], np.float32), order=np.array(g.order[:], np.int32), key=g.key,
+                             agg=np.array(g.agg[:], np.float32), frames=g.frames, used=g.used)
+    return res
+
+
 def debug_key_stages(specs, sample_rate=44100, config=None, mode=0, device=0):
     """The key path's conditioning and chroma over host key spectrograms (sdsp_debug_key_stages;
     mode 0 the configured path, 1 the in-place rerun's sequence, 2 the nested rerun's).  Returns

@@ -1089,6 +1089,13 @@ def key_path64(M8, sr, fft_size=8192, cfg=KEY_DEFAULT, ties=None):
     threshold, where the reference's f32 rounding decides whether the segment votes."""
     H = harmonic_mask64(M8, cfg["margin"], cfg["mask_power"])
     C, E = hpcp64(H, sr, fft_size, cfg)
+    return key_vote64(C, E, cfg, ties)[:3]
+
+
+def key_vote64(C, E, cfg=KEY_DEFAULT, ties=None):
+    """(key, confidence, clarity, used segments) of the default key vote from raw chroma rows (F, 12)
+    and frame energies: smoothing, frame weights, segment voting or the full-slice detection."""
+    C, E = np.asarray(C, np.float64), np.asarray(E, np.float64)
     if C.shape[0] > 5:
         C = smooth_chroma64(C, 5)
     w = key_weights64(C, E, cfg)
@@ -1113,6 +1120,6 @@ def key_path64(M8, sr, fft_size=8192, cfg=KEY_DEFAULT, ties=None):
             scores = [(k, float(acc[k])) for k in order]
             best = scores[0][1]
             conf = float(np.clip((best - scores[1][1]) / best, 0.0, 1.0)) if best > 0 else 0.0
-            return scores[0][0], conf, key_clarity64(scores)
+            return scores[0][0], conf, key_clarity64(scores), used
     scores, key, conf = detect_key_weighted64(C, w, T)
-    return key, conf, key_clarity64(scores)
+    return key, conf, key_clarity64(scores), 0

@@ -1,6 +1,6 @@
-"""The oracle's stage exports (oracle/units.py: tempo_stages, spectral_flux_curve, key_stages) pinned
-against exports that are already pinned.  The stage tests on the GPU (test_gpu_tempo_stages.py,
-test_gpu_key_stages.py) compare kernels with these exports, so the exports themselves must be the
+"""The oracle's stage exports (oracle/units.py: tempo_stages, spectral_flux_curve, key_stages, key_vote)
+pinned against exports that are already pinned.  The stage tests on the GPU (test_gpu_tempo_stages.py,
+test_gpu_key_stages.py, test_gpu_key_vote.py) compare kernels with these exports, so the exports themselves must be the
 arithmetic the whole-track oracle runs: they are taken from inside tempogram_impl and from the key
 conditioning analyze calls, not restated.
 """
@@ -93,6 +93,55 @@ def test_key_stage_energies_are_the_sequential_fold(opts):
     if not opts:
         ch, en = oracle.chroma("hpcp", masked, 44100, 8192)
         assert _same(ch, chroma) and _same(en, energy)
+
+
+_KV_SYNTH = {"synth3": (3, 30.0, 1), "synth11": (11, 24.0, 0), "synth17": (17, 40.0, 1), "synth29": (29, 12.0, None)}
+
+
+def _key_vote_audio(name):
+    import os
+
+    import parity
+
+    if name in _KV_SYNTH:
+        seed, sec, mode = _KV_SYNTH[name]
+        return synth.make_track(seed, seconds=sec, mode=mode)[0], 44100
+    return parity.load_wav(os.path.join(os.path.dirname(__file__), "golden", name))
+
+
+@pytest.mark.parametrize("name", ["120bpm_4bar.wav", "128bpm_4bar.wav", "cmajor_scale.wav", "mixed_silence.wav",
+                                  *_KV_SYNTH])
+def test_key_vote_export_is_the_analysis_vote(name):
+    """The whole-track oracle's key spectrogram (peak normalisation, trim, 8192-point STFT) through
+    key_stages and then key_vote gives analyze's key fields, weights_used, used_segments and the
+    trace's chroma / energy / weight checksums, bit for bit: the export is analyze's own vote."""
+    x, sr = _key_vote_audio(name)
+    rc, r, tr = oracle.analyze(x, sr, trace=True)
+    assert rc == 0, r
+    cfg = oracle.default_config()
+    st_n, xn = oracle.normalize(x, 0, sr)
+    assert st_n == 0
+    ks = oracle.stft(xn[tr["trim_start"]:tr["trim_end"]], int(cfg.key_stft_frame_size), int(cfg.key_stft_hop_size))
+    assert ks.shape[0] == tr["n_key_frames"] and ks.shape[0] > 0
+    _, chroma, energy = units.key_stages(ks, sr, cfg)
+    v = units.key_vote(chroma, energy, cfg)
+    assert not v["err"]
+    assert {"Minor" if v["mode"] else "Major": v["tonic"]} == r["key"]
+    assert _same([v["confidence"], v["clarity"]], [r["key_confidence"], r["key_clarity"]])
+    assert (int(v["weights_used"]), v["used_segments"]) == (tr["weights_used"], tr["used_segments"])
+
+    def fold(a):  # the trace's checksums: sequential sums in double
+        a = np.asarray(a, np.float64).ravel()
+        return float(np.cumsum(a)[-1]) if a.size else 0.0
+
+    cs = v["chroma_s"].astype(np.float64)
+    assert fold(cs) == tr["chroma_sum"] and fold(cs * cs) == tr["chroma_sq"]
+    assert fold(energy) == tr["energy_sum"] and fold(v["weights"]) == tr["weights_sum"]
+    # the trace the export returns: one row of raw scores and a clarity per segment it voted on
+    assert v["seg_raw"].shape[0] == v["seg_clarity"].size >= v["used_segments"]
+    assert int((v["seg_clarity"] >= np.float32(cfg.key_segment_min_clarity)).sum()) == v["used_segments"]
+    for raw, cl in zip(v["seg_raw"], v["seg_clarity"]):
+        assert _same(oracle.key_clarity(units.key_from_raw(raw)[0]), cl)
 
 
 @pytest.mark.parametrize("seed,bpm", [(7, 120.0), (8101, 126.0)])
