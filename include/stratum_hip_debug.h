@@ -271,6 +271,89 @@ int32_t sdsp_debug_beat_grid(const uint32_t* onsets, const uint64_t* n_onsets, c
                              uint32_t sample_rate, const sdsp_config* cfg, sdsp_debug_beat_out* out, int32_t device);
 
 /*
+ * Stage probe of the candidate selection: the pipeline's own select launch (k_tempo_select with the
+ * parameters an analysis call derives from cfg: Pipeline::pass_select from its offset tables on) over
+ * uploaded tempogram lists instead of a novelty curve.  Per track t and variant v (full, low, mid,
+ * high, mel) a list of (bpm, value) pairs in the order the tempogram kernels write them (value
+ * descending):
+ *   fft   track t's five lists back to back, fft_n[t] pairs each (one count per track, as in the
+ *         pipeline; 0 allowed, at most 1024): list (t, v) starts at pair 5 (fft_n[0] + ... +
+ *         fft_n[t - 1]) + v fft_n[t]
+ *   acf   NB pairs per list (one NB for the call, at most 512): list (t, v) at pair (5 t + v) NB
+ * present[v] selects the variants (the lists of the others are not read; present[0] must be set),
+ * active[t] = 0 marks a track without a novelty curve (its record comes back zero), top_n, cand_cap
+ * (1 ... 1024) and gate are the pass's: the candidates kept, the rows of the candidate table, and
+ * whether the ambiguity gate of the base pass is evaluated.  est receives n_tracks records as the
+ * kernel wrote them; cand n_tracks x cand_cap x 4 floats (bpm, score, fft_norm, autocorr_norm), of
+ * which the first est[t].n_cands rows of track t are written.  SDSP_ERR_INVALID_INPUT for a count or
+ * capacity outside these ranges.  Allocates only buffers of its own, released before it returns.
+ */
+typedef struct sdsp_debug_tempo_est {
+    float bpm, conf;
+    int32_t agree, ok, n_cands, ambiguous, trap_low, trap_high;
+} sdsp_debug_tempo_est;
+int32_t sdsp_debug_tempo_select(const float* fft, const int32_t* fft_n, const float* acf, uint32_t NB,
+                                const int32_t present[5], const int32_t* active, uint64_t n_tracks, int32_t top_n,
+                                int32_t cand_cap, int32_t gate, uint32_t sample_rate, const sdsp_config* cfg,
+                                sdsp_debug_tempo_est* est, float* cand, int32_t device);
+
+/*
+ * Stage probe of the multi-resolution fusion: the pipeline's own fusion launch (k_multires with
+ * the parameters, count tables and list stride of an analysis call: the tail of Pipeline::escalate)
+ * over uploaded candidate lists and hop-512 novelty curves instead of three tempo passes.  The call
+ * has n_tracks tracks, of which the n_items listed in `items` (ascending track indices) are fused.
+ *   c256, c1024  n_items x cap_aux x 4 floats (bpm, score, fft_norm, autocorr_norm per candidate),
+ *                n256 / n1024 [n_items] the candidates of each list, -1 where that hop's tempogram
+ *                failed
+ *   c512, n512   the hop-512 lists: with own512 = 0 the base pass's, one per track (n_tracks rows of
+ *                cap_base candidates); with own512 = 1 the escalation's own, one per item (n_items
+ *                rows of max(cfg->tempogram_multi_res_top_k, 1) candidates); -1 as above
+ *   nov512       the hop-512 novelty curves back to back, nov_n[r] values for row r, indexed like
+ *                the hop-512 lists (by track or by item)
+ *   base         the base pass's estimate of every track (the acceptance reads bpm, conf, agree,
+ *                trap_low, trap_high)
+ * out->mr and out->dbg receive one record per item: the multi-resolution estimate (ok = 0: a hop
+ * failed or no hypothesis; its other fields and the item's dbg record are then zero) and what the
+ * kernel decided (fold-down, fold-up and triplet-family switches with their values, the acceptance).
+ * out->used, final_bpm, final_conf hold n_tracks values: the probe uploads the caller's contents
+ * first and the kernel overwrites used for every item and the estimate of the accepted ones, so the
+ * other tracks come back untouched.  SDSP_ERR_INVALID_INPUT for an item list that is not ascending
+ * within [0, n_tracks), a capacity outside 1 ... 1024 (with own512, a top_k above 1024), a count above
+ * its list's capacity, or a novelty row of 2^24 values or more.
+ * Allocates only buffers of its own, released before it returns.
+ */
+typedef struct sdsp_debug_mr_dbg {
+    int32_t fd, fu, tf;
+    float fd_from, fd_to, fd_ratio;
+    int32_t fd_a0, fd_a1;
+    float fu_from, fu_to, fu_ratio;
+    int32_t fu_a0, fu_a1;
+    float tf_from, tf_to, tf_sup0, tf_sup1, tf_al0, tf_al1;
+    int32_t tf_label;
+    float rel;
+    int32_t fam, forbid, better;
+} sdsp_debug_mr_dbg;
+typedef struct sdsp_debug_multires_in {
+    const float *c256, *c512, *c1024;
+    const int32_t *n256, *n512, *n1024;
+    uint32_t cap_aux, cap_base;
+    const float* nov512;
+    const uint64_t* nov_n;
+    const sdsp_debug_tempo_est* base;
+    const int32_t* items;
+    uint64_t n_items, n_tracks;
+    int32_t own512;
+} sdsp_debug_multires_in;
+typedef struct sdsp_debug_multires_out {
+    sdsp_debug_tempo_est* mr;
+    sdsp_debug_mr_dbg* dbg;
+    int32_t* used;
+    float *final_bpm, *final_conf;
+} sdsp_debug_multires_out;
+int32_t sdsp_debug_multires(const sdsp_debug_multires_in* in, uint32_t sample_rate, const sdsp_config* cfg,
+                            sdsp_debug_multires_out* out, int32_t device);
+
+/*
  * Isolated STFT kernel timing: `reps` launches over n_tracks device-resident noise tracks of len
  * samples; mean launch time (HIP events on the launch stream) and algorithmic bytes per launch
  * (4 N_in + 4 F (nfft/2 + 1) per track).  stride 0 = the pipeline's row stride.

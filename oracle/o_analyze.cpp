@@ -496,21 +496,8 @@ void analyze(const float* samples, size_t n, uint32_t sr, const sdsp_config& c, 
             if (run_impl(base_top_n, &base, &base_c)) {
                 tr.base = base;
                 tr.base_cands = base_c;
-                const bool trap_low = base.bpm >= 55.0f && base.bpm <= 80.0f;
-                const bool trap_high = base.bpm >= 170.0f && base.bpm <= 200.0f;
-                auto support = [&](float bpm, float tol) {
-                    float b = 0.0f;
-                    for (auto& cd : base_c)
-                        if (sd_absf(cd.bpm - bpm) <= tol) b = sd_maxf(b, cd.score);
-                    return b;
-                };
-                const float tol = sd_maxf(2.0f, c.bpm_resolution);
-                const float s_base = support(base.bpm, tol), s_2x = support(base.bpm * 2.0f, tol),
-                            s_half = support(base.bpm * 0.5f, tol);
-                const bool family = (s_2x > 0.0f && s_2x >= s_base * 0.90f) || (s_half > 0.0f && s_half >= s_base * 0.90f);
-                const bool fold_into_trap = base.bpm * 2.0f >= 170.0f && base.bpm * 2.0f <= 200.0f;
-                const bool weak = base.method_agreement == 0 || base.confidence < 0.06f;
-                const bool ambiguous = trap_low || trap_high || family || (weak && fold_into_trap);
+                const GateFlags gate = ambiguity_gate(base, base_c, c.bpm_resolution);  // :412-459
+                const bool trap_low = gate.trap_low, trap_high = gate.trap_high, ambiguous = gate.ambiguous;
                 o.mr_trig = ambiguous;
                 tr.ambiguous = ambiguous;
                 BpmEstimate chosen = base;
@@ -534,17 +521,7 @@ void analyze(const float* samples, size_t n, uint32_t sr, const sdsp_config& c, 
                     if (ok) {
                         tr.ran_mr = true;
                         tr.mr = mr;
-                        const float rel = base.bpm > 1e-6f ? sd_maxf(mr.bpm / base.bpm, base.bpm / mr.bpm) : 1.0f;
-                        const bool fam = sd_absf(rel - 2.0f) < 0.05f || sd_absf(rel - 1.5f) < 0.05f ||
-                                         sd_absf(rel - (4.0f / 3.0f)) < 0.05f;
-                        const bool forbid = base.bpm <= 180.0f && mr.bpm > 180.0f;
-                        const bool better =
-                            !forbid && (mr.confidence >= (base.confidence + 0.05f) ||
-                                        (mr.method_agreement > base.method_agreement &&
-                                         mr.confidence >= base.confidence * 0.90f) ||
-                                        ((trap_low || trap_high) && fam && mr.confidence >= base.confidence * 0.88f &&
-                                         ((mr.bpm >= 70.0f && mr.bpm <= 180.0f) || base.bpm > 180.0f)));
-                        if (better) {
+                        if (mr_accept(base, trap_low, trap_high, mr).better) {  // :515-545
                             chosen = mr;
                             chosen_c = mr_c;
                             used = true;

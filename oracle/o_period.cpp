@@ -554,8 +554,6 @@ static std::vector<float> mel_superflux(const Spec& m, const NovFrames& lf, uint
 // =====================================================================================
 // Tempograms (tempogram_fft.rs, tempogram_autocorr.rs)
 // =====================================================================================
-using Tg = std::vector<std::pair<float, float>>;  // (bpm, value), sorted by value desc
-
 static Tg fft_tempogram(const std::vector<float>& nov, uint32_t sr, uint32_t hop, float min_bpm, float max_bpm) {
     if (nov.empty()) fail(SDSP_ERR_INVALID_INPUT, "Novelty curve is empty");
     if (sr == 0) fail(SDSP_ERR_INVALID_INPUT, "Sample rate must be > 0");
@@ -628,15 +626,23 @@ static bool find_best(const Tg& tg, float* bpm, float* conf) {
     return true;
 }
 
-static float lookup_nearest(const Tg& tg, float bpm, float tol) {  // tempogram.rs:521-532
+// ties / at_tol (test probes): an entry as near as the one held but with another value was passed
+// over (the first wins); the entry taken lies exactly at the tolerance
+static float lookup_nearest(const Tg& tg, float bpm, float tol, int* ties = nullptr, int* at_tol = nullptr) {  // tempogram.rs:521-532
     float bd = SD_INF_F, bv = 0.0f;
+    bool tie = false;
     for (auto& e : tg) {
         const float d = sd_absf(e.first - bpm);
         if (d <= tol && d < bd) {
             bd = d;
             bv = e.second;
+            tie = false;
+        } else if (d <= tol && d == bd && e.second != bv) {
+            tie = true;
         }
     }
+    if (ties && tie) (*ties)++;
+    if (at_tol && bd == tol) (*at_tol)++;
     return bv;
 }
 
@@ -676,12 +682,7 @@ void tempogram_impl(const Spec& m, uint32_t sr, uint32_t hop, float min_bpm, flo
         int64_t b = sd_f2i64(sd_roundf(f / fres));
         return (size_t)std::max<int64_t>(0, std::min<int64_t>(b, (int64_t)n_bins - 1));
     };
-    struct Variant {
-        const char* name;
-        float w;
-        Tg fft, ac;
-        float max_fft, max_ac;
-    };
+    using Variant = SelVariant;
     const size_t sf_k = band ? band->superflux_k : 4;
     NovFrames lf = log_frames(m);
     std::vector<float> nov_full;
@@ -700,22 +701,16 @@ void tempogram_impl(const Spec& m, uint32_t sr, uint32_t hop, float min_bpm, flo
     }
     if (nov_full.empty()) fail(SDSP_ERR_PROCESSING, "Novelty curve is empty after extraction");
     auto mk = [&](const char* name, float w, const std::vector<float>& nov) {
-        Variant v{name, w, fft_tempogram(nov, sr, hop, min_bpm, max_bpm), acf_tempogram(nov, sr, hop, min_bpm, max_bpm, res),
-                  0.0f, 0.0f};
+        Variant v{name, w, fft_tempogram(nov, sr, hop, min_bpm, max_bpm), acf_tempogram(nov, sr, hop, min_bpm, max_bpm, res)};
         if (dump) {  // the variant's record is the last one noted
             dump->back().nov = nov;
             dump->back().fft = v.fft;
             dump->back().ac = v.ac;
         }
-        v.max_fft = sd_maxf(v.fft.empty() ? 1.0f : v.fft[0].second, 1e-12f);
-        v.max_ac = sd_maxf(v.ac.empty() ? 1.0f : v.ac[0].second, 1e-12f);
         return v;
     };
     std::vector<Variant> seeds;
     seeds.push_back(mk("full", band ? band->w_full : 1.0f, nov_full));
-    float fft_pb = 0.0f, fft_pc = 0.0f, ac_pb = 0.0f, ac_pc = 0.0f;
-    if (!find_best(seeds[0].fft, &fft_pb, &fft_pc)) fft_pb = 0.0f, fft_pc = 0.0f;
-    if (!find_best(seeds[0].ac, &ac_pb, &ac_pc)) ac_pb = 0.0f, ac_pc = 0.0f;
     if (band && band->enabled) {
         const size_t b0 = std::min<size_t>(1, n_bins >= 1 ? n_bins - 1 : 0);
         const size_t bl = std::max(hz_to_bin(band->low_max_hz), b0);
@@ -758,14 +753,33 @@ void tempogram_impl(const Spec& m, uint32_t sr, uint32_t hop, float min_bpm, flo
             seeds.push_back(mk("mel", band->w_mel, mc));
         }
     }
+    tempo_select(seeds, min_bpm, max_bpm, res, band, est, cands_out);
+}
+
+// tempogram.rs:501-775: tempogram_impl from its seeded variants on
+void tempo_select(const std::vector<SelVariant>& seeds, float min_bpm, float max_bpm, float res, const BandCfg* band,
+                  BpmEstimate* est, std::vector<TempoCand>* cands_out, SelBranch* br) {
+    SelBranch local;
+    SelBranch& rec = br ? *br : local;
+    rec = SelBranch{};
+    std::vector<float> max_fft, max_ac;
+    for (auto& v : seeds) {
+        max_fft.push_back(sd_maxf(v.fft.empty() ? 1.0f : v.fft[0].second, 1e-12f));
+        max_ac.push_back(sd_maxf(v.ac.empty() ? 1.0f : v.ac[0].second, 1e-12f));
+    }
+    float fft_pb = 0.0f, fft_pc = 0.0f, ac_pb = 0.0f, ac_pc = 0.0f;
+    if (!find_best(seeds[0].fft, &fft_pb, &fft_pc)) fft_pb = 0.0f, fft_pc = 0.0f;
+    if (!find_best(seeds[0].ac, &ac_pb, &ac_pc)) ac_pb = 0.0f, ac_pc = 0.0f;
+    rec.fft_pb = fft_pb;
+    rec.ac_pb = ac_pb;
     const bool seed_only = band ? band->seed_only : true;
-    std::vector<const Variant*> score_v;
-    for (auto& v : seeds)
-        if (!seed_only || std::strcmp(v.name, "full") == 0) score_v.push_back(&v);
+    std::vector<size_t> score_v;
+    for (size_t i = 0; i < seeds.size(); i++)
+        if (!seed_only || seeds[i].name == "full") score_v.push_back(i);
     const float support_thr = sd_clampf(band ? band->support_threshold : 0.25f, 0.0f, 1.0f);
     const float bonus = sd_maxf(band ? band->consensus_bonus : 0.0f, 0.0f);
     float w_sum = 0.0f;
-    for (auto* v : score_v) w_sum += sd_maxf(v->w, 0.0f);
+    for (size_t i : score_v) w_sum += sd_maxf(seeds[i].w, 0.0f);
     w_sum = sd_maxf(w_sum, 1e-6f);
     bool all_empty = true;
     for (auto& v : seeds) all_empty &= v.fft.empty() && v.ac.empty();
@@ -783,43 +797,58 @@ void tempogram_impl(const Spec& m, uint32_t sr, uint32_t hop, float min_bpm, flo
     for (float b : seed_bpms)
         for (float f : FACT) {
             const float x = b * f;
-            if (sd_isfinite_f(x) && x >= min_bpm && x <= max_bpm) c.push_back(x);
+            if (sd_isfinite_f(x) && x >= min_bpm && x <= max_bpm) {
+                c.push_back(x);
+                rec.n_in++;
+            } else {
+                rec.n_out++;
+            }
         }
     std::stable_sort(c.begin(), c.end(), [](float a, float b) { return a < b; });
     std::vector<float> uniq;
     for (float b : c) {
-        if (!uniq.empty() && sd_absf(b - uniq.back()) < 0.75f) continue;
+        if (!uniq.empty() && sd_absf(b - uniq.back()) < 0.75f) {
+            rec.n_dup++;
+            continue;
+        }
         uniq.push_back(b);
     }
+    rec.n_uniq = (int)uniq.size();
     const float ac_tol = sd_maxf(res, 0.5f);
     const bool bonus_on = bonus > 0.0f && band && (band->enabled || band->enable_mel);
     std::vector<TempoCand> scored;
     for (float bpm : uniq) {
         float fa = 0.0f, aa = 0.0f;
-        for (auto* v : score_v) {
-            if (v->w <= 0.0f) continue;
-            const float fv = lookup_nearest(v->fft, bpm, 0.75f);
-            const float av = lookup_nearest(v->ac, bpm, ac_tol);
-            fa += v->w * sd_clampf(fv / v->max_fft, 0.0f, 1.0f);
-            aa += v->w * sd_clampf(av / v->max_ac, 0.0f, 1.0f);
+        for (size_t i : score_v) {
+            const SelVariant& v = seeds[i];
+            if (v.w <= 0.0f) continue;
+            const float fv = lookup_nearest(v.fft, bpm, 0.75f, &rec.n_tie, &rec.n_at_tol);
+            const float av = lookup_nearest(v.ac, bpm, ac_tol, &rec.n_tie_ac, &rec.n_at_tol_ac);
+            fa += v.w * sd_clampf(fv / max_fft[i], 0.0f, 1.0f);
+            aa += v.w * sd_clampf(av / max_ac[i], 0.0f, 1.0f);
         }
         const float fn = sd_clampf(fa / w_sum, 0.0f, 1.0f);
         const float an = sd_clampf(aa / w_sum, 0.0f, 1.0f);
         float score = 0.55f * an + 0.45f * fn;
         if (bonus_on) {
             uint32_t sb = 0;
-            for (auto& v : seeds) {
-                if (std::strcmp(v.name, "full") == 0) continue;
-                const float sff = sd_clampf(lookup_nearest(v.fft, bpm, 0.75f) / v.max_fft, 0.0f, 1.0f);
-                const float sac = sd_clampf(lookup_nearest(v.ac, bpm, ac_tol) / v.max_ac, 0.0f, 1.0f);
+            for (size_t i = 0; i < seeds.size(); i++) {
+                const SelVariant& v = seeds[i];
+                if (v.name == "full") continue;
+                const float sff = sd_clampf(lookup_nearest(v.fft, bpm, 0.75f) / max_fft[i], 0.0f, 1.0f);
+                const float sac = sd_clampf(lookup_nearest(v.ac, bpm, ac_tol) / max_ac[i], 0.0f, 1.0f);
                 if (sd_maxf(sff, sac) >= support_thr) sb++;
             }
             if (sb >= 2) score *= 1.0f + bonus * ((float)sb - 1.0f);
+            rec.sb_hist[sb < 4 ? sb : 4]++;
         }
-        if (bpm > 180.0f)
+        if (bpm > 180.0f) {
             score *= 0.80f;
-        else if (bpm < 60.0f)
+            rec.n_pen_hi++;
+        } else if (bpm < 60.0f) {
             score *= 0.90f;
+            rec.n_pen_lo++;
+        }
         scored.push_back({bpm, score, fn, an, false});
     }
     std::stable_sort(scored.begin(), scored.end(), [](auto& a, auto& b) { return b.score < a.score; });
@@ -827,13 +856,19 @@ void tempogram_impl(const Spec& m, uint32_t sr, uint32_t hop, float min_bpm, flo
     TempoCand best = scored[0];
     if (best.bpm > 180.0f) {
         const float folded = best.bpm / 2.0f;
+        rec.fold = 1;
         if (folded >= min_bpm && folded <= max_bpm) {
+            rec.fold = 2;
             for (auto& fc : scored) {
                 if (sd_absf(fc.bpm - folded) < 0.75f) {
                     const float eps = 1e-6f;
                     const float ar = (best.autocorr_norm + eps) / (fc.autocorr_norm + eps);
                     const float fr = (best.fft_norm + eps) / (fc.fft_norm + eps);
-                    if (!(ar > 2.0f && fr > 2.0f)) best = fc;
+                    rec.fold = 3;
+                    if (!(ar > 2.0f && fr > 2.0f)) {
+                        best = fc;
+                        rec.fold = 4;
+                    }
                     break;
                 }
             }
@@ -854,6 +889,28 @@ void tempogram_impl(const Spec& m, uint32_t sr, uint32_t hop, float min_bpm, flo
     }
 }
 
+// src/lib.rs:412-459: the ambiguity gate over the candidates truncated to base_top_n
+GateFlags ambiguity_gate(const BpmEstimate& base, const std::vector<TempoCand>& base_c, float res) {
+    GateFlags g{};
+    g.trap_low = base.bpm >= 55.0f && base.bpm <= 80.0f;
+    g.trap_high = base.bpm >= 170.0f && base.bpm <= 200.0f;
+    auto support = [&](float bpm, float tol) {
+        float b = 0.0f;
+        for (auto& cd : base_c)
+            if (sd_absf(cd.bpm - bpm) <= tol) b = sd_maxf(b, cd.score);
+        return b;
+    };
+    const float tol = sd_maxf(2.0f, res);
+    g.s_base = support(base.bpm, tol);
+    g.s_2x = support(base.bpm * 2.0f, tol);
+    g.s_half = support(base.bpm * 0.5f, tol);
+    g.family = (g.s_2x > 0.0f && g.s_2x >= g.s_base * 0.90f) || (g.s_half > 0.0f && g.s_half >= g.s_base * 0.90f);
+    g.fold_into_trap = base.bpm * 2.0f >= 170.0f && base.bpm * 2.0f <= 200.0f;
+    g.weak = base.method_agreement == 0 || base.confidence < 0.06f;
+    g.ambiguous = g.trap_low || g.trap_high || g.family || (g.weak && g.fold_into_trap);
+    return g;
+}
+
 // =====================================================================================
 // Multi-resolution escalation, multi_resolution.rs:205-901
 // =====================================================================================
@@ -870,7 +927,10 @@ static float lookup_c(const std::vector<TempoCand>& c, float bpm, float tol) {  
     return bs;
 }
 
-static float beat_contrast(const std::vector<float>& nov, uint32_t sr, uint32_t hop, float bpm) {  // :580-678
+// best_ph (test probes): the first phase that reaches the returned maximum; -1 where no phase is walked
+static float beat_contrast(const std::vector<float>& nov, uint32_t sr, uint32_t hop, float bpm,
+                           int* best_ph = nullptr) {  // :580-678
+    if (best_ph) *best_ph = -1;
     if (nov.size() < 16 || !(sd_isfinite_f(bpm) && bpm > 0.0f) || sr == 0 || hop == 0) return 0.0f;
     const float fpb = (60.0f * (float)sr) / (bpm * (float)hop);
     if (!sd_isfinite_f(fpb) || fpb < 3.0f) return 0.0f;
@@ -915,6 +975,7 @@ static float beat_contrast(const std::vector<float>& nov, uint32_t sr, uint32_t 
         const float tm = tn > 0 ? ts / (float)tn : 0.0f;
         const float contrast = bm - 0.60f * hm - 0.40f * tm;
         const float score = sd_clampf(contrast / sd_maxf(total / (float)n, 1e-6f), -10.0f, 10.0f);
+        if (best_ph && score > best) *best_ph = (int)ph;
         best = sd_maxf(best, score);
     }
     return best;
@@ -927,6 +988,207 @@ static void total_support(const std::vector<TempoCand>& c256, const std::vector<
     *s = s256 + s512 + s1024;
 }
 
+// multi_resolution.rs:272-901: multi_resolution from its hypothesis loop on
+void multires_fuse(const std::vector<TempoCand>& c256, std::vector<TempoCand>& c512, const std::vector<TempoCand>& c1024,
+                   const std::vector<float>* nov512_p, uint32_t sr, const MrFuseCfg& f, BpmEstimate* est, MrBranch* br) {
+    MrBranch local;
+    MrBranch& rec = br ? *br : local;
+    rec = MrBranch{};
+    const float min_bpm = f.min_bpm, max_bpm = f.max_bpm, w512 = f.w512, w256 = f.w256, w1024 = f.w1024, dt = f.dt,
+                margin_thr = f.margin_thr;
+    const bool human_prior = f.human_prior, band = nov512_p != nullptr;
+    const size_t top_k = f.top_k;
+    const float tol = sd_maxf(2.0f, f.res);
+    static const std::vector<float> no_nov;
+    const std::vector<float>& nov512 = nov512_p ? *nov512_p : no_nov;
+    struct Hyp {
+        float bpm, score;
+    };
+    std::vector<Hyp> hyps;
+    for (size_t ti = 0; ti < std::min(top_k, c512.size()); ti++) {
+        const float t = c512[ti].bpm;
+        if (!(sd_isfinite_f(t) && t > 0.0f)) continue;
+        const float st512 = lookup_c(c512, t, tol), st256 = lookup_c(c256, t, tol), st1024 = lookup_c(c1024, t, tol);
+        const float s2512 = lookup_c(c512, t * 2.0f, tol), s2256 = lookup_c(c256, t * 2.0f, tol),
+                    s21024 = lookup_c(c1024, t * 2.0f, tol);
+        const float sh512 = lookup_c(c512, t * 0.5f, tol), sh256 = lookup_c(c256, t * 0.5f, tol),
+                    sh1024 = lookup_c(c1024, t * 0.5f, tol);
+        const float h_t = w512 * st512 + w256 * st256 + w1024 * st1024;
+        float h_2t = w512 * (dt * st512 + (1.0f - dt) * s2512) + w256 * s2256 + w1024 * s21024;
+        float h_h = w512 * (dt * st512 + (1.0f - dt) * sh512) + w256 * sh256 + w1024 * sh1024;
+        if (st1024 > sh1024 * 1.02f) h_h *= 0.90f, rec.n_h102++;
+        if (st1024 > s21024 * 1.02f) h_2t *= 0.90f, rec.n_2t102++;
+        const float eps = 1e-6f;
+        const float r2 = (s2256 + eps) / (st256 + eps);
+        if (r2 < 1.10f) h_2t *= 0.75f, rec.n_r2_110++;
+        if (r2 < 1.00f) h_2t *= 0.75f, rec.n_r2_100++;
+        const float rh = (sh1024 + eps) / (st1024 + eps);
+        if (rh < 1.10f) h_h *= 0.75f, rec.n_rh_110++;
+        if (rh < 1.00f) h_h *= 0.75f, rec.n_rh_100++;
+        std::vector<Hyp> local;
+        for (Hyp h : {Hyp{t, h_t}, Hyp{t * 2.0f, h_2t}, Hyp{t * 0.5f, h_h}})
+            if (h.bpm >= min_bpm && h.bpm <= max_bpm) local.push_back(h);
+        for (auto& h : local) {
+            if (h.bpm > 210.0f)
+                h.score *= 0.80f, rec.n_pen210++;
+            else if (h.bpm > 180.0f)
+                h.score *= 0.90f, rec.n_pen180++;
+            else if (h.bpm < 60.0f)
+                h.score *= 0.92f, rec.n_pen60++;
+        }
+        std::stable_sort(local.begin(), local.end(), [](auto& a, auto& b) { return b.score < a.score; });
+        if (local.empty()) continue;
+        const float bb = local[0].bpm, bsc = local[0].score;
+        const float ss = local.size() > 1 ? local[1].score : 0.0f;
+        const float margin = bsc - ss;
+        float cb = bb, cs = bsc;
+        if (margin < margin_thr) rec.n_margin_lo++;
+        if (sd_absf(cb - t) > 1e-3f && margin < margin_thr) {
+            cb = t;
+            cs = h_t;
+            rec.n_reset++;
+        }
+        if (margin < margin_thr && human_prior && cb >= 70.0f && cb <= 180.0f && margin < 0.05f) cs += 0.05f, rec.n_prior++;
+        hyps.push_back({cb, cs});
+    }
+    rec.n_hyps = (int)hyps.size();
+    if (hyps.empty()) fail(SDSP_ERR_PROCESSING, "Multi-resolution fusion produced no hypotheses");
+    std::stable_sort(hyps.begin(), hyps.end(), [](auto& a, auto& b) { return b.score < a.score; });
+    std::vector<Hyp> uniq;
+    for (auto& h : hyps) {
+        bool dup = false;
+        for (auto& u : uniq) dup |= sd_absf(u.bpm - h.bpm) < 0.75f;
+        if (dup) {
+            rec.n_dup++;
+            continue;
+        }
+        uniq.push_back(h);
+        if (uniq.size() >= 8) break;
+    }
+    rec.n_uniq = (int)uniq.size();
+    Hyp best = uniq[0];
+    if (best.bpm >= 170.0f) {  // fold-down :698-724
+        const float half = best.bpm * 0.5f;
+        if (half >= 70.0f && half <= 120.0f) {
+            float sb, sh;
+            uint32_t ab, ah;
+            total_support(c256, c512, c1024, best.bpm, tol, &sb, &ab);
+            total_support(c256, c512, c1024, half, tol, &sh, &ah);
+            const float ratio = sb > 0.0f ? sh / sb : 0.0f;
+            rec.fd_eval = 1 + (ah >= 3 ? 4 : 0) + (sh > 0.0f && sb > 0.0f ? 2 : 0) + (ratio >= 0.45f ? 1 : 0);
+            rec.fd_eval_ratio = ratio;
+            rec.fd_eval_a1 = (int)ah;
+            if (ah >= 3 && sh > 0.0f && sb > 0.0f && ratio >= 0.45f) {
+                rec.fd = 1, rec.fd_from = best.bpm, rec.fd_to = half, rec.fd_ratio = ratio, rec.fd_a0 = (int)ab,
+                rec.fd_a1 = (int)ah;
+                best = {half, sh};
+            }
+        }
+    }
+    if (best.bpm <= 80.0f) {  // fold-up :727-751
+        const float dbl = best.bpm * 2.0f;
+        if (dbl >= 70.0f && dbl <= 180.0f) {
+            float sb, sd;
+            uint32_t ab, ad;
+            total_support(c256, c512, c1024, best.bpm, tol, &sb, &ab);
+            total_support(c256, c512, c1024, dbl, tol, &sd, &ad);
+            const float ratio = sb > 0.0f ? sd / sb : 0.0f;
+            rec.fu_eval = 1 + (ad >= 2 ? 4 : 0) + (sd > 0.0f && sb > 0.0f ? 2 : 0) + (ratio >= 0.55f ? 1 : 0);
+            rec.fu_eval_ratio = ratio;
+            rec.fu_eval_a1 = (int)ad;
+            if (ad >= 2 && sd > 0.0f && sb > 0.0f && ratio >= 0.55f) {
+                rec.fu = 1, rec.fu_from = best.bpm, rec.fu_to = dbl, rec.fu_ratio = ratio, rec.fu_a0 = (int)ab,
+                rec.fu_a1 = (int)ad;
+                best = {dbl, sd};
+            }
+        }
+    }
+    if (band && best.bpm >= 70.0f && best.bpm <= 180.0f && !nov512.empty()) {  // triplet family :764-867
+        const float fam_f[5] = {1.0f, 3.0f / 2.0f, 2.0f / 3.0f, 4.0f / 3.0f, 3.0f / 4.0f};
+        struct Fam {
+            float bpm, support, align;
+            int label;
+        };
+        std::vector<Fam> fams;
+        for (int k = 0; k < 5; k++) {
+            const float bpm = best.bpm * fam_f[k];
+            if (!(sd_isfinite_f(bpm) && bpm >= min_bpm && bpm <= max_bpm)) continue;
+            if (!(bpm >= 70.0f && bpm <= 180.0f)) continue;
+            float sup;
+            uint32_t ag;
+            total_support(c256, c512, c1024, bpm, tol, &sup, &ag);
+            if (ag < 2 || sup <= 0.0f) continue;
+            int ph = -1;
+            fams.push_back({bpm, sup, beat_contrast(nov512, sr, 512, bpm, &ph), k});
+            rec.fam_phase[fams.size() - 1] = ph;
+        }
+        rec.n_fam = (int)fams.size();
+        for (size_t k = 0; k < fams.size(); k++)
+            rec.fam_bpm[k] = fams[k].bpm, rec.fam_sup[k] = fams[k].support, rec.fam_align[k] = fams[k].align;
+        if (fams.size() >= 2) {
+            float bs = 0.0f;
+            for (auto& fm : fams) bs = sd_maxf(bs, fm.support);
+            bs = sd_maxf(bs, 1e-6f);
+            float max_alt = 0.0f;
+            for (auto& fm : fams)
+                if (sd_absf(fm.bpm - best.bpm) > 0.75f) max_alt = sd_maxf(max_alt, fm.support / bs);
+            rec.max_alt = max_alt;
+            if (max_alt >= 0.45f) {
+                Fam chosen = fams[0];
+                float cscore = -1e9f;
+                for (size_t k = 0; k < fams.size(); k++) {
+                    const Fam& fm = fams[k];
+                    const float sn = sd_clampf(fm.support / bs, 0.0f, 1.0f);
+                    const float sc = fm.align + 0.35f * sn;
+                    if (sc > cscore) {
+                        chosen = fm;
+                        cscore = sc;
+                        rec.chosen = (int)k;
+                    }
+                }
+                const float cur_align = beat_contrast(nov512, sr, 512, best.bpm, &rec.cur_phase);
+                rec.fam_eval = 1;
+                rec.cur_align = cur_align;
+                {  // the debug line's supports (multi_resolution.rs:845-857): current and chosen over the best
+                    float sc;
+                    uint32_t ac;
+                    total_support(c256, c512, c1024, best.bpm, tol, &sc, &ac);
+                    rec.tf_sup0 = sc / bs;
+                    rec.tf_sup1 = chosen.support / bs;
+                    rec.tf_label = chosen.label;
+                }
+                if (sd_absf(chosen.bpm - best.bpm) > 0.75f && chosen.align >= cur_align + 0.40f) {
+                    rec.tf = 1, rec.tf_from = best.bpm, rec.tf_to = chosen.bpm, rec.tf_al0 = cur_align,
+                    rec.tf_al1 = chosen.align;
+                    best = {chosen.bpm, chosen.support};
+                }
+            }
+        }
+    }
+    const float second = uniq.size() > 1 ? uniq[1].score : 0.0f;
+    const float conf =
+        best.score > 1e-6f ? sd_clampf(sd_maxf(best.score - second, 0.0f) / best.score, 0.0f, 1.0f) : 0.0f;
+    uint32_t agree = (lookup_c(c256, best.bpm, tol) > 0.0f) + (lookup_c(c512, best.bpm, tol) > 0.0f) +
+                     (lookup_c(c1024, best.bpm, tol) > 0.0f);
+    for (auto& c : c512) c.selected = sd_absf(c.bpm - best.bpm) < 0.75f;
+    *est = {best.bpm, conf, agree};
+}
+
+// src/lib.rs:515-545: whether the multi-resolution estimate replaces the base estimate
+MrAccept mr_accept(const BpmEstimate& base, bool trap_low, bool trap_high, const BpmEstimate& mr) {
+    MrAccept a{};
+    a.rel = base.bpm > 1e-6f ? sd_maxf(mr.bpm / base.bpm, base.bpm / mr.bpm) : 1.0f;
+    a.fam = sd_absf(a.rel - 2.0f) < 0.05f || sd_absf(a.rel - 1.5f) < 0.05f || sd_absf(a.rel - (4.0f / 3.0f)) < 0.05f;
+    a.forbid = base.bpm <= 180.0f && mr.bpm > 180.0f;
+    const bool c1 = mr.confidence >= (base.confidence + 0.05f);
+    const bool c2 = mr.method_agreement > base.method_agreement && mr.confidence >= base.confidence * 0.90f;
+    const bool c3 = (trap_low || trap_high) && a.fam && mr.confidence >= base.confidence * 0.88f &&
+                    ((mr.bpm >= 70.0f && mr.bpm <= 180.0f) || base.bpm > 180.0f);
+    a.clause = (c1 ? 1 : 0) | (c2 ? 2 : 0) | (c3 ? 4 : 0);
+    a.better = !a.forbid && (c1 || c2 || c3);
+    return a;
+}
+
 void multi_resolution(const std::vector<float>& samples, uint32_t sr, size_t frame_size, float min_bpm,
                       float max_bpm, float res, size_t top_k_in, float w512, float w256, float w1024,
                       float structural_discount, float dt, float margin_thr, bool human_prior, const BandCfg* band,
@@ -935,7 +1197,6 @@ void multi_resolution(const std::vector<float>& samples, uint32_t sr, size_t fra
     if (samples.size() < frame_size) fail(SDSP_ERR_INVALID_INPUT, "Audio too short for STFT");
     const size_t top_k = std::max<size_t>(top_k_in, 1);
     const size_t aux_k = std::min<size_t>(std::max<size_t>(top_k * 4, 25), 200);
-    const float tol = sd_maxf(2.0f, res);
     Spec h256 = compute_stft(samples.data(), samples.size(), frame_size, 256);
     Spec h512 = compute_stft(samples.data(), samples.size(), frame_size, 512);
     Spec h1024 = compute_stft(samples.data(), samples.size(), frame_size, 1024);
@@ -952,136 +1213,10 @@ void multi_resolution(const std::vector<float>& samples, uint32_t sr, size_t fra
     call(h256, 256, aux_k, &c256);
     call(h512, 512, top_k, &c512);
     call(h1024, 1024, aux_k, &c1024);
-    struct Hyp {
-        float bpm, score;
-    };
-    std::vector<Hyp> hyps;
-    for (size_t ti = 0; ti < std::min(top_k, c512.size()); ti++) {
-        const float t = c512[ti].bpm;
-        if (!(sd_isfinite_f(t) && t > 0.0f)) continue;
-        const float st512 = lookup_c(c512, t, tol), st256 = lookup_c(c256, t, tol), st1024 = lookup_c(c1024, t, tol);
-        const float s2512 = lookup_c(c512, t * 2.0f, tol), s2256 = lookup_c(c256, t * 2.0f, tol),
-                    s21024 = lookup_c(c1024, t * 2.0f, tol);
-        const float sh512 = lookup_c(c512, t * 0.5f, tol), sh256 = lookup_c(c256, t * 0.5f, tol),
-                    sh1024 = lookup_c(c1024, t * 0.5f, tol);
-        const float h_t = w512 * st512 + w256 * st256 + w1024 * st1024;
-        float h_2t = w512 * (dt * st512 + (1.0f - dt) * s2512) + w256 * s2256 + w1024 * s21024;
-        float h_h = w512 * (dt * st512 + (1.0f - dt) * sh512) + w256 * sh256 + w1024 * sh1024;
-        if (st1024 > sh1024 * 1.02f) h_h *= 0.90f;
-        if (st1024 > s21024 * 1.02f) h_2t *= 0.90f;
-        const float eps = 1e-6f;
-        const float r2 = (s2256 + eps) / (st256 + eps);
-        if (r2 < 1.10f) h_2t *= 0.75f;
-        if (r2 < 1.00f) h_2t *= 0.75f;
-        const float rh = (sh1024 + eps) / (st1024 + eps);
-        if (rh < 1.10f) h_h *= 0.75f;
-        if (rh < 1.00f) h_h *= 0.75f;
-        std::vector<Hyp> local;
-        for (Hyp h : {Hyp{t, h_t}, Hyp{t * 2.0f, h_2t}, Hyp{t * 0.5f, h_h}})
-            if (h.bpm >= min_bpm && h.bpm <= max_bpm) local.push_back(h);
-        for (auto& h : local) {
-            if (h.bpm > 210.0f)
-                h.score *= 0.80f;
-            else if (h.bpm > 180.0f)
-                h.score *= 0.90f;
-            else if (h.bpm < 60.0f)
-                h.score *= 0.92f;
-        }
-        std::stable_sort(local.begin(), local.end(), [](auto& a, auto& b) { return b.score < a.score; });
-        if (local.empty()) continue;
-        const float bb = local[0].bpm, bsc = local[0].score;
-        const float ss = local.size() > 1 ? local[1].score : 0.0f;
-        const float margin = bsc - ss;
-        float cb = bb, cs = bsc;
-        if (sd_absf(cb - t) > 1e-3f && margin < margin_thr) {
-            cb = t;
-            cs = h_t;
-        }
-        if (margin < margin_thr && human_prior && cb >= 70.0f && cb <= 180.0f && margin < 0.05f) cs += 0.05f;
-        hyps.push_back({cb, cs});
-    }
-    if (hyps.empty()) fail(SDSP_ERR_PROCESSING, "Multi-resolution fusion produced no hypotheses");
-    std::stable_sort(hyps.begin(), hyps.end(), [](auto& a, auto& b) { return b.score < a.score; });
-    std::vector<Hyp> uniq;
-    for (auto& h : hyps) {
-        bool dup = false;
-        for (auto& u : uniq) dup |= sd_absf(u.bpm - h.bpm) < 0.75f;
-        if (dup) continue;
-        uniq.push_back(h);
-        if (uniq.size() >= 8) break;
-    }
-    Hyp best = uniq[0];
     std::vector<float> nov512;
     if (band) nov512 = combined_full_novelty(h512, sr, *band);
-    if (best.bpm >= 170.0f) {  // fold-down :698-724
-        const float half = best.bpm * 0.5f;
-        if (half >= 70.0f && half <= 120.0f) {
-            float sb, sh;
-            uint32_t ab, ah;
-            total_support(c256, c512, c1024, best.bpm, tol, &sb, &ab);
-            total_support(c256, c512, c1024, half, tol, &sh, &ah);
-            const float ratio = sb > 0.0f ? sh / sb : 0.0f;
-            if (ah >= 3 && sh > 0.0f && sb > 0.0f && ratio >= 0.45f) best = {half, sh};
-        }
-    }
-    if (best.bpm <= 80.0f) {  // fold-up :727-751
-        const float dbl = best.bpm * 2.0f;
-        if (dbl >= 70.0f && dbl <= 180.0f) {
-            float sb, sd;
-            uint32_t ab, ad;
-            total_support(c256, c512, c1024, best.bpm, tol, &sb, &ab);
-            total_support(c256, c512, c1024, dbl, tol, &sd, &ad);
-            const float ratio = sb > 0.0f ? sd / sb : 0.0f;
-            if (ad >= 2 && sd > 0.0f && sb > 0.0f && ratio >= 0.55f) best = {dbl, sd};
-        }
-    }
-    if (band && best.bpm >= 70.0f && best.bpm <= 180.0f && !nov512.empty()) {  // triplet family :764-867
-        const float fam_f[5] = {1.0f, 3.0f / 2.0f, 2.0f / 3.0f, 4.0f / 3.0f, 3.0f / 4.0f};
-        struct Fam {
-            float bpm, support, align;
-        };
-        std::vector<Fam> fams;
-        for (float f : fam_f) {
-            const float bpm = best.bpm * f;
-            if (!(sd_isfinite_f(bpm) && bpm >= min_bpm && bpm <= max_bpm)) continue;
-            if (!(bpm >= 70.0f && bpm <= 180.0f)) continue;
-            float sup;
-            uint32_t ag;
-            total_support(c256, c512, c1024, bpm, tol, &sup, &ag);
-            if (ag < 2 || sup <= 0.0f) continue;
-            fams.push_back({bpm, sup, beat_contrast(nov512, sr, 512, bpm)});
-        }
-        if (fams.size() >= 2) {
-            float bs = 0.0f;
-            for (auto& f : fams) bs = sd_maxf(bs, f.support);
-            bs = sd_maxf(bs, 1e-6f);
-            float max_alt = 0.0f;
-            for (auto& f : fams)
-                if (sd_absf(f.bpm - best.bpm) > 0.75f) max_alt = sd_maxf(max_alt, f.support / bs);
-            if (max_alt >= 0.45f) {
-                Fam chosen = fams[0];
-                float cscore = -1e9f;
-                for (auto& f : fams) {
-                    const float sn = sd_clampf(f.support / bs, 0.0f, 1.0f);
-                    const float sc = f.align + 0.35f * sn;
-                    if (sc > cscore) {
-                        chosen = f;
-                        cscore = sc;
-                    }
-                }
-                const float cur_align = beat_contrast(nov512, sr, 512, best.bpm);
-                if (sd_absf(chosen.bpm - best.bpm) > 0.75f && chosen.align >= cur_align + 0.40f)
-                    best = {chosen.bpm, chosen.support};
-            }
-        }
-    }
-    const float second = uniq.size() > 1 ? uniq[1].score : 0.0f;
-    const float conf =
-        best.score > 1e-6f ? sd_clampf(sd_maxf(best.score - second, 0.0f) / best.score, 0.0f, 1.0f) : 0.0f;
-    uint32_t agree = (lookup_c(c256, best.bpm, tol) > 0.0f) + (lookup_c(c512, best.bpm, tol) > 0.0f) +
-                     (lookup_c(c1024, best.bpm, tol) > 0.0f);
-    for (auto& c : c512) c.selected = sd_absf(c.bpm - best.bpm) < 0.75f;
-    *est = {best.bpm, conf, agree};
+    const MrFuseCfg fc{min_bpm, max_bpm, res, top_k, w512, w256, w1024, dt, margin_thr, human_prior};
+    multires_fuse(c256, c512, c1024, band ? &nov512 : nullptr, sr, fc, est);
     if (c512_out) *c512_out = c512;
 }
 
@@ -1366,5 +1501,106 @@ int32_t sdsp_oracle_multi_resolution_analysis(const float* spec, uint64_t frames
         out3[2] = (float)r.method_agreement;
         return 0;
     });
+}
+
+// tempo_select (tempogram_impl from its seeded variants on) over given variants, under the BandCfg
+// analyze passes for the configuration, and the ambiguity gate over its candidates truncated to
+// the base pass's top_n (tests/test_gpu_tempo_select.py).  kind[i]: 0 full (first), 1 low, 2 mid,
+// 3 high, 4 mel; fft / acf: the variants' (bpm, value) pairs back to back, fft_n[i] / acf_n[i] each.
+// cands receives the full scored list (4 floats each, up to cap); rec_i = {n_in, n_out, n_dup,
+// n_uniq, n_pen_hi, n_pen_lo, sb_hist[5], fold, trap_low, trap_high, family, fold_into_trap, weak,
+// ambiguous, n_tie, n_at_tol, n_tie_ac, n_at_tol_ac}, rec_f = {fft_pb, ac_pb, s_base, s_2x, s_half}.  Returns the number of scored candidates.
+int64_t sdsp_oracle_tempo_select(const int32_t* kind, const float* w, int32_t n_var, const float* fft, const int32_t* fft_n,
+                                 const float* acf, const int32_t* acf_n, float min_bpm, float max_bpm, float res,
+                                 const sdsp_config* c, float* est3, float* cands, uint64_t cap, int32_t* rec_i,
+                                 float* rec_f) {
+    return probe_call([&]() -> int64_t {
+        static const char* names[5] = {"full", "low", "mid", "high", "mel"};
+        std::vector<SelVariant> seeds;
+        size_t fa = 0, aa = 0;
+        for (int32_t i = 0; i < n_var; i++) {
+            SelVariant v{names[kind[i]], w[i], {}, {}};
+            for (int32_t j = 0; j < fft_n[i]; j++, fa++) v.fft.push_back({fft[2 * fa], fft[2 * fa + 1]});
+            for (int32_t j = 0; j < acf_n[i]; j++, aa++) v.ac.push_back({acf[2 * aa], acf[2 * aa + 1]});
+            seeds.push_back(v);
+        }
+        const BandCfg band = band_cfg_of(*c);
+        BpmEstimate e{0.0f, 0.0f, 0};
+        std::vector<TempoCand> sc;
+        SelBranch br;
+        tempo_select(seeds, min_bpm, max_bpm, res, band_cfg_used(*c) ? &band : nullptr, &e, &sc, &br);
+        est3[0] = e.bpm;
+        est3[1] = e.confidence;
+        est3[2] = (float)e.method_agreement;
+        for (size_t i = 0; i < sc.size() && i < cap; i++) {
+            cands[4 * i] = sc[i].bpm;
+            cands[4 * i + 1] = sc[i].score;
+            cands[4 * i + 2] = sc[i].fft_norm;
+            cands[4 * i + 3] = sc[i].autocorr_norm;
+        }
+        const size_t base_top_n =
+            std::max<size_t>(std::max<size_t>(c->tempogram_candidates_top_n, c->tempogram_multi_res_top_k), 10);
+        std::vector<TempoCand> top = sc;
+        if (top.size() > base_top_n) top.resize(base_top_n);
+        const GateFlags g = ambiguity_gate(e, top, res);
+        const int32_t ri[22] = {br.n_in, br.n_out, br.n_dup, br.n_uniq, br.n_pen_hi, br.n_pen_lo, br.sb_hist[0],
+                                br.sb_hist[1], br.sb_hist[2], br.sb_hist[3], br.sb_hist[4], br.fold, g.trap_low,
+                                g.trap_high, g.family, g.fold_into_trap, g.weak, g.ambiguous, br.n_tie, br.n_at_tol,
+                                br.n_tie_ac, br.n_at_tol_ac};
+        std::memcpy(rec_i, ri, sizeof ri);
+        const float rf[5] = {br.fft_pb, br.ac_pb, g.s_base, g.s_2x, g.s_half};
+        std::memcpy(rec_f, rf, sizeof rf);
+        return (int64_t)sc.size();
+    });
+}
+
+// multires_fuse (multi_resolution from its hypothesis loop on) over given candidate lists (4 floats
+// per candidate; a count of -1: that hop's tempogram failed) and hop-512 novelty, then the
+// acceptance against base5 = {bpm, confidence, agreement, trap_low, trap_high}
+// (tests/test_gpu_multires_stages.py).  Returns 1, or 0 where multi_resolution returns Err (est3 and
+// the records are then zero).  rec_i / rec_f: MrBranch and MrAccept in the order of units.MR_REC_I /
+// MR_REC_F.
+int32_t sdsp_oracle_multires_fuse(const float* c256, int32_t n256, const float* c512, int32_t n512, const float* c1024,
+                                  int32_t n1024, const float* nov, uint64_t nn, uint32_t sr, const float* base5,
+                                  const sdsp_config* c, float* est3, int32_t* rec_i, float* rec_f) {
+    std::memset(est3, 0, 3 * sizeof(float));
+    std::memset(rec_i, 0, 40 * sizeof(int32_t));
+    std::memset(rec_f, 0, 32 * sizeof(float));
+    if (n256 < 0 || n512 < 0 || n1024 < 0) return 0;
+    auto list = [](const float* p, int32_t n) {
+        std::vector<TempoCand> v;
+        for (int32_t i = 0; i < n; i++) v.push_back({p[4 * i], p[4 * i + 1], p[4 * i + 2], p[4 * i + 3], false});
+        return v;
+    };
+    const std::vector<TempoCand> a = list(c256, n256), d = list(c1024, n1024);
+    std::vector<TempoCand> b = list(c512, n512);
+    const std::vector<float> nv(nov, nov + nn);
+    const MrFuseCfg fc{c->min_bpm, c->max_bpm, c->bpm_resolution, std::max<size_t>((size_t)c->tempogram_multi_res_top_k, 1),
+                       c->tempogram_multi_res_w512, c->tempogram_multi_res_w256, c->tempogram_multi_res_w1024,
+                       c->tempogram_multi_res_double_time_512_factor, c->tempogram_multi_res_margin_threshold,
+                       (bool)c->tempogram_multi_res_use_human_prior};
+    BpmEstimate e{0.0f, 0.0f, 0};
+    MrBranch r;
+    try {
+        multires_fuse(a, b, d, &nv, sr, fc, &e, &r);
+    } catch (const AErr&) {
+        return 0;
+    }
+    const BpmEstimate base{base5[0], base5[1], (uint32_t)base5[2]};
+    const MrAccept ac = mr_accept(base, base5[3] != 0.0f, base5[4] != 0.0f, e);
+    est3[0] = e.bpm;
+    est3[1] = e.confidence;
+    est3[2] = (float)e.method_agreement;
+    const int32_t ri[40] = {r.fd, r.fu, r.tf, r.fd_a0, r.fd_a1, r.fu_a0, r.fu_a1, r.tf_label, ac.fam, ac.forbid, ac.better,
+                            ac.clause, r.fd_eval, r.fu_eval, r.fd_eval_a1, r.fu_eval_a1, r.n_hyps, r.n_uniq, r.n_dup,
+                            r.n_h102, r.n_2t102, r.n_r2_110, r.n_r2_100, r.n_rh_110, r.n_rh_100, r.n_pen210, r.n_pen180,
+                            r.n_pen60, r.n_margin_lo, r.n_reset, r.n_prior, r.n_fam, r.fam_eval, r.chosen, r.cur_phase,
+                            r.fam_phase[0], r.fam_phase[1], r.fam_phase[2], r.fam_phase[3], r.fam_phase[4]};
+    std::memcpy(rec_i, ri, sizeof ri);
+    float rf[32] = {r.fd_from, r.fd_to, r.fd_ratio, r.fu_from, r.fu_to, r.fu_ratio, r.tf_from, r.tf_to, r.tf_sup0,
+                    r.tf_sup1, r.tf_al0, r.tf_al1, ac.rel, r.fd_eval_ratio, r.fu_eval_ratio, r.max_alt, r.cur_align};
+    for (int k = 0; k < 5; k++) rf[17 + k] = r.fam_bpm[k], rf[22 + k] = r.fam_sup[k], rf[27 + k] = r.fam_align[k];
+    std::memcpy(rec_f, rf, sizeof rf);
+    return 1;
 }
 }

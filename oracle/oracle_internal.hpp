@@ -123,10 +123,79 @@ struct StageVariant {
 void tempogram_impl(const Spec& m, uint32_t sr, uint32_t hop, float min_bpm, float max_bpm, float res,
                     const BandCfg* band, BpmEstimate* est, std::vector<TempoCand>* cands,
                     std::vector<StageVariant>* dump = nullptr);
+// tempogram_impl from its seeded variants on (tempogram.rs:501-775): candidate seeding and dedupe,
+// weighted lookup scoring, the consensus bonus, the octave fold.  seeds[0] is the full variant.
+using Tg = std::vector<std::pair<float, float>>;  // (bpm, value), sorted by value desc
+struct SelVariant {
+    std::string name;
+    float w;
+    Tg fft, ac;
+};
+struct SelBranch {  // what tempo_select did (test probes)
+    int n_in = 0, n_out = 0;        // seed images inside / outside [min_bpm, max_bpm]
+    int n_dup = 0, n_uniq = 0;      // images dropped by the 0.75 dedupe; candidates scored
+    int n_pen_hi = 0, n_pen_lo = 0; // candidates above 180 / below 60
+    int sb_hist[5] = {0, 0, 0, 0, 0};  // candidates by supporting variants (the last bin: 4 or more)
+    int fold = 0;  // 0 best <= 180, 1 folded value out of range, 2 no candidate at it, 3 kept out by both ratios, 4 taken
+    float fft_pb = 0.0f, ac_pb = 0.0f;
+    // scoring lookups that passed over an equidistant entry of another value (the first wins), and
+    // whose entry lies exactly at the tolerance; FFT lists, then autocorrelation lists
+    int n_tie = 0, n_at_tol = 0, n_tie_ac = 0, n_at_tol_ac = 0;
+};
+void tempo_select(const std::vector<SelVariant>& seeds, float min_bpm, float max_bpm, float res, const BandCfg* band,
+                  BpmEstimate* est, std::vector<TempoCand>* cands, SelBranch* br = nullptr);
+// the ambiguity gate over the base estimate and its truncated candidates (src/lib.rs:412-459)
+struct GateFlags {
+    bool trap_low, trap_high, family, fold_into_trap, weak, ambiguous;
+    float s_base, s_2x, s_half;
+};
+GateFlags ambiguity_gate(const BpmEstimate& base, const std::vector<TempoCand>& base_c, float res);
 void multi_resolution(const std::vector<float>& samples, uint32_t sr, size_t frame_size, float min_bpm,
                       float max_bpm, float res, size_t top_k, float w512, float w256, float w1024,
                       float structural_discount, float dt512, float margin_threshold, bool human_prior,
                       const BandCfg* band, BpmEstimate* est, std::vector<TempoCand>* c512);
+// multi_resolution from its hypothesis loop on (multi_resolution.rs:272-901) over the three hops'
+// truncated candidate lists; nov512: the hop-512 novelty of the fold gates, null without a BandCfg.
+// Marks c512's `selected`.
+struct MrBranch {  // what multires_fuse did (test probes; the fields k_multires' MrDbg mirrors, and counters)
+    int fd = 0, fu = 0, tf = 0;
+    float fd_from = 0, fd_to = 0, fd_ratio = 0;
+    int fd_a0 = 0, fd_a1 = 0;
+    float fu_from = 0, fu_to = 0, fu_ratio = 0;
+    int fu_a0 = 0, fu_a1 = 0;
+    float tf_from = 0, tf_to = 0, tf_sup0 = 0, tf_sup1 = 0, tf_al0 = 0, tf_al1 = 0;
+    int tf_label = 0;
+    // fold gates evaluated: 0 not reached, else 1 + 4 (agreement ok) + 2 (supports > 0) + 1 (ratio ok)
+    int fd_eval = 0, fu_eval = 0;
+    float fd_eval_ratio = 0, fu_eval_ratio = 0;
+    int fd_eval_a1 = 0, fu_eval_a1 = 0;
+    int n_hyps = 0, n_uniq = 0, n_dup = 0;  // hypotheses before the dedupe, kept, dropped as duplicates
+    int n_h102 = 0, n_2t102 = 0, n_r2_110 = 0, n_r2_100 = 0, n_rh_110 = 0, n_rh_100 = 0;  // structural discounts taken
+    int n_pen210 = 0, n_pen180 = 0, n_pen60 = 0;  // band penalties taken
+    int n_reset = 0, n_prior = 0, n_margin_lo = 0;  // margin below the threshold; the anchor reset; the human prior
+    int n_fam = 0;  // family members considered
+    float fam_bpm[5] = {0}, fam_sup[5] = {0}, fam_align[5] = {0};
+    int fam_eval = 0;  // max_alt >= 0.45: a member was chosen
+    float max_alt = 0, cur_align = 0;
+    int chosen = -1;   // index of the chosen member
+    int cur_phase = -1, fam_phase[5] = {-1, -1, -1, -1, -1};  // the first phase that gives each alignment
+};
+struct MrFuseCfg {
+    float min_bpm, max_bpm, res;
+    size_t top_k;
+    float w512, w256, w1024, dt, margin_thr;
+    bool human_prior;
+};
+void multires_fuse(const std::vector<TempoCand>& c256, std::vector<TempoCand>& c512, const std::vector<TempoCand>& c1024,
+                   const std::vector<float>* nov512, uint32_t sr, const MrFuseCfg& f, BpmEstimate* est,
+                   MrBranch* br = nullptr);
+// the acceptance of the multi-resolution estimate (src/lib.rs:515-545)
+struct MrAccept {
+    float rel;
+    bool fam, forbid, better;
+    int clause;  // bits: 1 confidence, 2 agreement, 4 trap-zone family
+};
+MrAccept mr_accept(const BpmEstimate& base, bool trap_low, bool trap_high, const BpmEstimate& mr);
 
 // ---------- beat grid (beat_tracking/) ----------
 struct BeatDiag {            // which branches generate_beat_grid took (test probes)

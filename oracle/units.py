@@ -449,6 +449,94 @@ def tempo_stages_estimate():
     return float(out[0]), float(out[1]), int(out[2])
 
 
+VARIANT_KINDS = {"full": 0, "low": 1, "mid": 2, "high": 3, "mel": 4}
+SEL_REC_I = ("n_in", "n_out", "n_dup", "n_uniq", "n_pen_hi", "n_pen_lo", "sb0", "sb1", "sb2", "sb3", "sb4", "fold",
+             "trap_low", "trap_high", "family", "fold_into_trap", "weak", "ambiguous", "n_tie", "n_at_tol", "n_tie_ac",
+             "n_at_tol_ac")
+SEL_REC_F = ("fft_pb", "ac_pb", "s_base", "s_2x", "s_half")
+
+
+def _pairs(a):
+    return np.ascontiguousarray(np.asarray(a, dtype=np.float32).reshape(-1, 2))
+
+
+def tempo_select(variants, min_bpm, max_bpm, res, config=None):
+    """tempogram_impl from its seeded variants on, over variants = [(name, weight, fft list, acf
+    list)] with "full" first and (n, 2) lists of (bpm, value) in the tempograms' order, under the
+    BandCfg analyze passes for the configuration; then the ambiguity gate over the candidates
+    truncated to the base pass's top_n.  Returns None where the reference returns Err, else a dict:
+    bpm, conf (float32), agree, cands (n, 4: bpm, score, fft_norm, autocorr_norm; the full scored
+    list) and the branch record (SEL_REC_I / SEL_REC_F: the gate's flags and supports among them;
+    fold: 0 best <= 180, 1 folded value out of range, 2 no candidate there, 3 kept out by both
+    ratios, 4 taken; n_tie / n_at_tol (_ac: the autocorrelation lists): scoring lookups that passed
+    over an equidistant entry of another value, and whose entry lies exactly at the tolerance)."""
+    L = lib()
+    L.sdsp_oracle_tempo_select.argtypes = [i32p, fp, C.c_int32, fp, i32p, fp, i32p, C.c_float, C.c_float, C.c_float,
+                                           C.POINTER(oracle.SdspConfig), fp, fp, C.c_uint64, i32p, fp]
+    L.sdsp_oracle_tempo_select.restype = C.c_int64
+    cfg = config if config is not None else oracle.default_config()
+    kind = np.array([VARIANT_KINDS[v[0]] for v in variants], np.int32)
+    w = np.array([v[1] for v in variants], np.float32)
+    ffts, acfs = [_pairs(v[2]) for v in variants], [_pairs(v[3]) for v in variants]
+    fn, an = np.array([len(a) for a in ffts], np.int32), np.array([len(a) for a in acfs], np.int32)
+    fft = np.ascontiguousarray(np.concatenate(ffts + [np.zeros((1, 2), np.float32)]))
+    acf = np.ascontiguousarray(np.concatenate(acfs + [np.zeros((1, 2), np.float32)]))
+    cap = 1024
+    est, cands = np.zeros(3, np.float32), np.zeros((cap, 4), np.float32)
+    ri, rf = np.zeros(len(SEL_REC_I), np.int32), np.zeros(len(SEL_REC_F), np.float32)
+    n = L.sdsp_oracle_tempo_select(kind.ctypes.data_as(i32p), _p(w), len(variants), _p(fft), fn.ctypes.data_as(i32p),
+                                   _p(acf), an.ctypes.data_as(i32p), min_bpm, max_bpm, res, C.byref(cfg), _p(est),
+                                   _p(cands), cap, ri.ctypes.data_as(i32p), _p(rf))
+    if n < 0:
+        return None
+    assert n <= cap
+    d = dict(bpm=est[0], conf=est[1], agree=int(est[2]), cands=cands[:n].copy())
+    d.update({k: int(v) for k, v in zip(SEL_REC_I, ri)})
+    d.update({k: np.float32(v) for k, v in zip(SEL_REC_F, rf)})
+    return d
+
+
+MR_REC_I = ("fd", "fu", "tf", "fd_a0", "fd_a1", "fu_a0", "fu_a1", "tf_label", "fam", "forbid", "better", "clause",
+            "fd_eval", "fu_eval", "fd_eval_a1", "fu_eval_a1", "n_hyps", "n_uniq", "n_dup", "n_h102", "n_2t102",
+            "n_r2_110", "n_r2_100", "n_rh_110", "n_rh_100", "n_pen210", "n_pen180", "n_pen60", "n_margin_lo", "n_reset",
+            "n_prior", "n_fam", "fam_eval", "chosen", "cur_phase", "fam_ph0", "fam_ph1", "fam_ph2", "fam_ph3", "fam_ph4")
+MR_REC_F = ("fd_from", "fd_to", "fd_ratio", "fu_from", "fu_to", "fu_ratio", "tf_from", "tf_to", "tf_sup0", "tf_sup1",
+            "tf_al0", "tf_al1", "rel", "fd_eval_ratio", "fu_eval_ratio", "max_alt", "cur_align")
+
+
+def multires_fuse(c256, c512, c1024, nov512, sr, base, config=None):
+    """multi_resolution from its hypothesis loop on over the three hops' candidate lists ((n, 4)
+    arrays, or None for a hop whose tempogram failed) and the hop-512 novelty, then the acceptance
+    against base = (bpm, conf, agree, trap_low, trap_high).  Returns a dict: ok (False where
+    multi_resolution returns Err; everything else is then zero), bpm, conf (float32), agree, used and
+    the branch record (MR_REC_I / MR_REC_F, fam_bpm / fam_sup / fam_align of the n_fam family members
+    considered; fd_eval / fu_eval: 0 the fold gate was not reached, else 1 + 4 (agreement ok) +
+    2 (supports > 0) + 1 (ratio ok); clause: bits of the acceptance's three clauses; cur_phase /
+    fam_phase: the first beat phase that gives the current best's / each member's alignment)."""
+    L = lib()
+    L.sdsp_oracle_multires_fuse.argtypes = [fp, C.c_int32, fp, C.c_int32, fp, C.c_int32, fp, C.c_uint64, C.c_uint32, fp,
+                                            C.POINTER(oracle.SdspConfig), fp, i32p, fp]
+    L.sdsp_oracle_multires_fuse.restype = C.c_int32
+    cfg = config if config is not None else oracle.default_config()
+    ls = [None if c is None else np.ascontiguousarray(np.asarray(c, np.float32).reshape(-1, 4)) for c in (c256, c512, c1024)]
+    ns = [-1 if a is None else len(a) for a in ls]
+    held = [np.zeros(4, np.float32) if a is None or not len(a) else a for a in ls]  # kept alive over the call
+    ps = [_p(a) for a in held]
+    nov = _f32(nov512)
+    b5 = np.array([base[0], base[1], base[2], base[3], base[4]], np.float32)
+    est = np.zeros(3, np.float32)
+    ri, rf = np.zeros(len(MR_REC_I), np.int32), np.zeros(32, np.float32)
+    ok = L.sdsp_oracle_multires_fuse(ps[0], ns[0], ps[1], ns[1], ps[2], ns[2], _p(nov), nov.size, sr, _p(b5), C.byref(cfg),
+                                     _p(est), ri.ctypes.data_as(i32p), _p(rf))
+    d = dict(ok=bool(ok), bpm=est[0], conf=est[1], agree=int(est[2]))
+    d.update({k: int(v) for k, v in zip(MR_REC_I, ri)})
+    d.update({k: np.float32(v) for k, v in zip(MR_REC_F, rf)})
+    d["used"] = d["better"]
+    d["fam_phase"] = [d[f"fam_ph{k}"] for k in range(d["n_fam"])]
+    d["fam_bpm"], d["fam_sup"], d["fam_align"] = (rf[17 + 5 * j:17 + 5 * j + d["n_fam"]].copy() for j in range(3))
+    return d
+
+
 def spectral_flux_curve(spec):
     """The flux detect_spectral_flux_onsets thresholds: frames - 1 values."""
     L = lib()

@@ -332,7 +332,6 @@ __device__ float lookup_nearest(const float* bpm, const float* val, int n, float
     return bv;
 }
 
-constexpr int SEL_MAXC = 1024;
 
 __global__ __launch_bounds__(256) void k_tempo_select(const int* __restrict__ active, int n_items,
                                                       const float* __restrict__ fft_bpm,
@@ -666,15 +665,23 @@ __global__ __launch_bounds__(64) void k_multires(const int* __restrict__ tracks,
     }
     __syncthreads();
     const float tol = P.tol;
+    // one LDS buffer: lane 0's hypotheses, then block_seq_sum's staging (SEQ_CH) and
+    // beat_contrast_seg's segments
+    __shared__ float wbuf[MR_SEG_BUF];
+    static_assert(MR_SEG_BUF >= SEQ_CH, "the staging buffer is shared");
     if (threadIdx.x == 0) {
         ok_s = 0;
         struct Hyp {
             float bpm, score;
         };
-        Hyp hyps[64];
+        // one hypothesis per scored hop-512 candidate, as many as the reference holds: a list has at
+        // most SEL_MAXC = MR_HYP_MAX candidates (k_tempo_select; fuse_multires checks), so none is cut
+        Hyp* hyps = reinterpret_cast<Hyp*>(wbuf);
+        static_assert(sizeof(Hyp) == 2 * sizeof(float) && MR_HYP_MAX * 2 <= MR_SEG_BUF,
+                      "the hypotheses fit the staging buffer");
         int nh = 0;
         const int kmax = P.top_k < L512.n ? P.top_k : L512.n;
-        for (int ti = 0; ti < kmax && nh < 64; ti++) {
+        for (int ti = 0; ti < kmax && nh < MR_HYP_MAX; ti++) {
             const float t = L512.c[4 * ti];
             if (!(sd_isfinite_f(t) && t > 0.0f)) continue;
             const float st512 = lookup_c(L512, t, tol), st256 = lookup_c(L256, t, tol), st1024 = lookup_c(L1024, t, tol);
@@ -819,9 +826,6 @@ __global__ __launch_bounds__(64) void k_multires(const int* __restrict__ tracks,
     const uint64_t g0 = fpfx512[j512];
     const int nn = (int)(fpfx512[j512 + 1] - g0) - 1;
     const float* nov = nov512 + g0;
-    // one LDS buffer: block_seq_sum's staging (SEQ_CH), then beat_contrast_seg's segments
-    __shared__ float wbuf[MR_SEG_BUF];
-    static_assert(MR_SEG_BUF >= SEQ_CH, "the staging buffer is shared");
     const float nov_total = (nf >= 2 && nn > 0) ? block_seq_sum(nov, nn, wbuf) : 0.0f;
     if (nf >= 2 && nn > 0) {
         for (int k = 0; k < nf; k++) {

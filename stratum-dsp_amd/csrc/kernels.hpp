@@ -101,6 +101,10 @@ struct TempoEst {
     int n_cands;
     int ambiguous, trap_low, trap_high;
 };
+// candidates k_tempo_select scores, so the longest list it writes; k_multires holds one hypothesis per
+// scored hop-512 candidate (min(top_k, list length) of them) and fuse_multires refuses a longer list
+constexpr int SEL_MAXC = 1024;
+constexpr int MR_HYP_MAX = SEL_MAXC;
 struct MrParams {
     float min_bpm, max_bpm, tol, w512, w256, w1024, dt, margin_thr;
     int human_prior, top_k, band;

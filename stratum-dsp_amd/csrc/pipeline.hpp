@@ -261,6 +261,32 @@ struct PassFeat {
     bool configured = false, mel_on = false;  // band_configured(); the mel variant
 };
 
+// pass_select from its offset tables on: the tempogram lists on the device and, per (track, variant)
+// slot t * NVAR + v, where each list starts (0 for an absent variant); fft_k per track.
+struct SelLists {
+    const float *fft_bpm = nullptr, *fft_pow = nullptr, *acf_bpm = nullptr, *acf_str = nullptr;
+    std::vector<uint64_t> fo, ao;
+    std::vector<int> fft_k;
+    int present[NVAR] = {0, 0, 0, 0, 0};
+    int NB = 0;
+};
+// escalate's tail: the three hops' candidate lists on the device with their counts (-1: that hop's
+// tempogram failed; n256 / n1024 per item, n512 per item with own512, else per track), the base
+// estimates and the hop-512 novelty with its frame prefix (by item or by track like n512).
+struct MrFuse {
+    const float *c256 = nullptr, *c512 = nullptr, *c1024 = nullptr;
+    std::vector<int> n256, n512, n1024;
+    int cap_aux = 0, cap_base = 0;  // rows of the aux lists; of the base pass's list (the hop-512 one without own512)
+    bool own512 = false;
+    const TempoEst* base_est = nullptr;
+    const float* nov512 = nullptr;
+    const uint64_t* fpfx512 = nullptr;
+    bool want_dbg = false;
+    // set by fuse_multires
+    int cap512 = 0;
+    MrDbg* d_mdbg = nullptr;
+};
+
 // ---- debug_track_id dumps (pipeline_debug.hip) ----
 struct Cand4 {
     float bpm, score, fft, acf;
@@ -452,6 +478,10 @@ class Pipeline {
     void debug_beat_grid(const uint32_t* onsets, const uint64_t* n_onsets, const uint64_t* frames,
                          const uint64_t* n_trim, const float* bpm, const float* conf, uint64_t n_tracks,
                          sdsp_debug_beat_out* out);
+    void debug_tempo_select(const float* fft, const int32_t* fft_n, const float* acf, int NB, const int32_t present[5],
+                            const int32_t* active, uint64_t n_tracks, int top_n, int cand_cap, int gate,
+                            sdsp_debug_tempo_est* est, float* cand);
+    void debug_multires_fuse(const sdsp_debug_multires_in* in, sdsp_debug_multires_out* out);
 
     void run(const float* d_samples, const std::vector<uint64_t>& in_off, const std::vector<uint64_t>& n_raw,
              std::vector<TrackRes>& res);
@@ -545,6 +575,10 @@ class Pipeline {
                            const TempoPassOut& o);
     void pass_select(const std::string& tag, const TempoPassIn& in, const PassPlan& pl, const PassTg& tg,
                      TempoPassOut& o);
+    void select_lists(const std::string& tag, int P_T, const SelLists& sl, int top_n, int gate, int cand_cap,
+                      TempoPassOut& o);
+    void fuse_multires(const std::vector<int>& E, int NR, MrFuse& m, Tempo& tp);
+    void tempo_down(int NR, Tempo& tp);
     Tempo seed_tempo(const Front& f, const std::vector<TempoEst>& best, const Onsets& on, std::vector<TrackRes>& res);
     void escalate(const Front& f, const TempoPassIn& bin, const TempoPassOut& bo, const std::vector<TempoEst>& best,
                   Tempo& tp, std::vector<TrackDbg>& tdbg, std::vector<TrackRes>& res);

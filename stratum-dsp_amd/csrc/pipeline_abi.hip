@@ -675,6 +675,37 @@ int32_t sdsp_debug_beat_grid(const uint32_t* onsets, const uint64_t* n_onsets, c
     });
 }
 
+int32_t sdsp_debug_tempo_select(const float* fft, const int32_t* fft_n, const float* acf, uint32_t NB,
+                                const int32_t present[5], const int32_t* active, uint64_t n_tracks, int32_t top_n,
+                                int32_t cand_cap, int32_t gate, uint32_t sample_rate, const sdsp_config* cfg,
+                                sdsp_debug_tempo_est* est, float* cand, int32_t device) {
+    if (!fft || !fft_n || !acf || !present || !active || !cfg || !est || !cand || n_tracks == 0 ||
+        n_tracks > (1u << 16) || sample_rate == 0 || NB > 512 || top_n < 0 || cand_cap < 1 || cand_cap > 1024 ||
+        !present[0])
+        return SDSP_ERR_INVALID_INPUT;
+    for (uint64_t t = 0; t < n_tracks; t++)
+        if (fft_n[t] < 0 || fft_n[t] > 1024) return SDSP_ERR_INVALID_INPUT;
+    return run_stage_probe("sdsp_debug_tempo_select", device, [&](DeviceCtx& d) {
+        Pipeline p(d, *cfg, sample_rate, SDSP_STAGES_FULL, false, false, false, true);
+        p.debug_tempo_select(fft, fft_n, acf, (int)NB, present, active, n_tracks, top_n, cand_cap, gate != 0, est, cand);
+    });
+}
+
+int32_t sdsp_debug_multires(const sdsp_debug_multires_in* in, uint32_t sample_rate, const sdsp_config* cfg,
+                            sdsp_debug_multires_out* out, int32_t device) {
+    if (!in || !cfg || !out || sample_rate == 0 || in->n_tracks == 0 || in->n_tracks > (1u << 16) ||
+        in->n_items > in->n_tracks || in->cap_aux == 0 || in->cap_aux > 1024 || in->cap_base == 0 || in->cap_base > 1024)
+        return SDSP_ERR_INVALID_INPUT;
+    if (!in->c256 || !in->c512 || !in->c1024 || !in->n256 || !in->n512 || !in->n1024 || !in->nov512 || !in->nov_n ||
+        !in->base || !in->items || !out->mr || !out->dbg || !out->used || !out->final_bpm || !out->final_conf)
+        return SDSP_ERR_INVALID_INPUT;
+    if (in->own512 && cfg->tempogram_multi_res_top_k > 1024) return SDSP_ERR_INVALID_INPUT;
+    return run_stage_probe("sdsp_debug_multires", device, [&](DeviceCtx& d) {
+        Pipeline p(d, *cfg, sample_rate, SDSP_STAGES_FULL, false, false, false, true);
+        p.debug_multires_fuse(in, out);
+    });
+}
+
 // Host buffers: chunks of whole tracks (up to SDSP_BATCH_CHUNK_TRACKS tracks, default
 // 512, and about 8 GB) pulled from a shared counter by one worker per device; per device a copier
 // thread stages the next chunk into the second of two HBM slots (its own stream, completion

@@ -319,6 +319,111 @@ void Pipeline::debug_tempo_stages(const float* host_mags, const uint64_t* frames
     }
 }
 
+// sdsp_debug_tempo_select: select_lists (pass_select from its offset tables on) over uploaded
+// tempogram lists, packed as pass_tempograms leaves them: the present variants of the active tracks
+// back to back, offset 0 for every other slot.
+void Pipeline::debug_tempo_select(const float* fft, const int32_t* fft_n, const float* acf, int NB, const int32_t present[5],
+                                  const int32_t* active, uint64_t n_tracks, int top_n, int cand_cap, int gate,
+                                  sdsp_debug_tempo_est* est, float* cand) {
+    static_assert(sizeof(sdsp_debug_tempo_est) == sizeof(TempoEst), "the probe's record mirrors the kernel's");
+    if (const std::string why = check_supported(cfg_, sr_); !why.empty()) throw HipError(why);
+    const int T = (int)n_tracks;
+    SelLists sl;
+    sl.NB = NB;
+    for (int v = 0; v < NVAR; v++) sl.present[v] = present[v] != 0;
+    sl.fo.assign((size_t)T * NVAR, 0);
+    sl.ao.assign((size_t)T * NVAR, 0);
+    sl.fft_k.assign((size_t)T, 0);
+    std::vector<float> fb, fw, ab, as;
+    uint64_t pair0 = 0;  // first pair of the track's five lists
+    for (int t = 0; t < T; t++) {
+        const uint64_t K = (uint64_t)fft_n[t];
+        sl.fft_k[(size_t)t] = (int)K;
+        for (int v = 0; v < NVAR && active[t]; v++) {
+            if (!sl.present[v]) continue;
+            sl.fo[(size_t)t * NVAR + (size_t)v] = fb.size();
+            sl.ao[(size_t)t * NVAR + (size_t)v] = ab.size();
+            const float* f = fft + 2 * (pair0 + (uint64_t)v * K);
+            const float* a = acf + 2 * ((uint64_t)t * NVAR + (uint64_t)v) * (uint64_t)NB;
+            for (uint64_t j = 0; j < K; j++) fb.push_back(f[2 * j]), fw.push_back(f[2 * j + 1]);
+            for (int j = 0; j < NB; j++) ab.push_back(a[2 * j]), as.push_back(a[2 * j + 1]);
+        }
+        pair0 += NVAR * K;
+    }
+    sl.fft_bpm = c_.up("S.fftb", fb);
+    sl.fft_pow = c_.up("S.fftp", fw);
+    sl.acf_bpm = c_.up("S.acfb", ab);
+    sl.acf_str = c_.up("S.acfs", as);
+    TempoPassOut o;
+    o.active = c_.up("S.active", std::vector<int>(active, active + T));
+    select_lists("S.", T, sl, top_n, gate, cand_cap, o);
+    const std::vector<TempoEst> e = c_.down(o.est, (size_t)T);
+    const std::vector<float> c = c_.down(o.cand, (size_t)T * (size_t)cand_cap * 4);
+    std::memcpy(est, e.data(), (size_t)T * sizeof(TempoEst));
+    std::fill(cand, cand + (size_t)T * (size_t)cand_cap * 4, 0.0f);
+    for (int t = 0; t < T; t++)  // the rows the kernel wrote
+        std::copy_n(c.begin() + (ptrdiff_t)((size_t)t * (size_t)cand_cap * 4), (size_t)e[(size_t)t].n_cands * 4,
+                    cand + (size_t)t * (size_t)cand_cap * 4);
+}
+
+// sdsp_debug_multires: fuse_multires (escalate's tail) over uploaded candidate lists, base estimates
+// and hop-512 novelty rows; the rows lie at a frame prefix of nov_n + 1 frames each, as a tempo pass
+// leaves a novelty curve.
+void Pipeline::debug_multires_fuse(const sdsp_debug_multires_in* in, sdsp_debug_multires_out* out) {
+    static_assert(sizeof(sdsp_debug_tempo_est) == sizeof(TempoEst) && sizeof(sdsp_debug_mr_dbg) == sizeof(MrDbg),
+                  "the probe's records mirror the kernel's");
+    if (const std::string why = check_supported(cfg_, sr_); !why.empty()) throw HipError(why);
+    const size_t NR = (size_t)in->n_tracks, NE = (size_t)in->n_items;
+    const int top_k = (int)std::max<uint64_t>(cfg_.tempogram_multi_res_top_k, 1);
+    const bool own512 = in->own512 != 0;
+    const size_t rows = own512 ? NE : NR;
+    const int cap512 = own512 ? top_k : (int)in->cap_base, cap_aux = (int)in->cap_aux;
+    std::vector<int> E(in->items, in->items + NE);
+    for (size_t k = 0; k < NE; k++)
+        if (E[k] < 0 || (size_t)E[k] >= NR || (k > 0 && E[k] <= E[k - 1])) throw std::invalid_argument("item list");
+    MrFuse m;
+    m.n256.assign(in->n256, in->n256 + NE);
+    m.n1024.assign(in->n1024, in->n1024 + NE);
+    m.n512.assign(in->n512, in->n512 + rows);
+    for (size_t k = 0; k < NE; k++)
+        if (m.n256[k] > cap_aux || m.n1024[k] > cap_aux) throw std::invalid_argument("capacity");
+    std::vector<uint64_t> fpfx(1, 0);
+    for (size_t r = 0; r < rows; r++) {
+        if (m.n512[r] > cap512) throw std::invalid_argument("capacity");
+        if (in->nov_n[r] >= (1u << 24)) throw std::invalid_argument("novelty row");
+        fpfx.push_back(fpfx.back() + in->nov_n[r] + 1);
+    }
+    std::vector<float> nov((size_t)fpfx.back(), 0.0f);
+    for (size_t r = 0, at = 0; r < rows; at += (size_t)in->nov_n[r], r++)
+        std::copy_n(in->nov512 + at, (size_t)in->nov_n[r], nov.begin() + (ptrdiff_t)fpfx[r]);
+    m.c256 = c_.up("M.c256", std::vector<float>(in->c256, in->c256 + NE * (size_t)cap_aux * 4));
+    m.c1024 = c_.up("M.c1024", std::vector<float>(in->c1024, in->c1024 + NE * (size_t)cap_aux * 4));
+    m.c512 = c_.up("M.c512", std::vector<float>(in->c512, in->c512 + rows * (size_t)cap512 * 4));
+    m.cap_aux = cap_aux;
+    m.cap_base = (int)in->cap_base;
+    m.own512 = own512;
+    const TempoEst* base = reinterpret_cast<const TempoEst*>(in->base);
+    m.base_est = c_.up("M.base", std::vector<TempoEst>(base, base + NR));
+    m.nov512 = c_.up("M.nov", nov);
+    m.fpfx512 = c_.up("M.fpfx", fpfx);
+    m.want_dbg = true;
+    Tempo tp;
+    tp.d_fbpm = c_.up("B.fbpm", std::vector<float>(out->final_bpm, out->final_bpm + NR));
+    tp.d_fconf = c_.up("B.fconf", std::vector<float>(out->final_conf, out->final_conf + NR));
+    tp.d_used = c_.up("B.used", std::vector<int>(out->used, out->used + NR));
+    fuse_multires(E, (int)NR, m, tp);
+    tempo_down((int)NR, tp);
+    std::vector<TempoEst> mr = c_.down(tp.d_mr_all, NE);
+    std::vector<MrDbg> md = c_.down(m.d_mdbg, NE);
+    for (size_t k = 0; k < NE; k++)  // the kernel writes only `ok` of an item it leaves early
+        if (!mr[k].ok) mr[k] = TempoEst{}, md[k] = MrDbg{};
+    std::memcpy(out->mr, mr.data(), NE * sizeof(TempoEst));
+    std::memcpy(out->dbg, md.data(), NE * sizeof(MrDbg));
+    std::copy(tp.used.begin(), tp.used.end(), out->used);
+    std::copy(tp.fbpm_h.begin(), tp.fbpm_h.end(), out->final_bpm);
+    std::copy(tp.fconf_h.begin(), tp.fconf_h.end(), out->final_conf);
+}
+
 // sdsp_debug_key_stages: key_condition (and, for mode 1, tail_exact) over uploaded key spectrograms.
 // exact_energy_ selects mode 2's sequence, as it does for the nested rerun.
 void Pipeline::debug_key_stages(const float* host_mags, const uint64_t* frames, uint64_t n_tracks, int mode,

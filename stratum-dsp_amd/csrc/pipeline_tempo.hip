@@ -294,19 +294,34 @@ void Pipeline::pass_select(const std::string& tag, const TempoPassIn& in, const 
                            TempoPassOut& o) {
     const int P_T = pl.P_T;
     // per (track, variant) offsets for the selector
-    std::vector<uint64_t> fo((size_t)P_T * NVAR, 0), ao((size_t)P_T * NVAR, 0);
+    SelLists sl;
+    sl.fo.assign((size_t)P_T * NVAR, 0);
+    sl.ao.assign((size_t)P_T * NVAR, 0);
     for (size_t i = 0; i < tg.items.size(); i++) {
-        fo[(size_t)tg.items[i]] = tg.fft_off[i];
-        ao[(size_t)tg.items[i]] = (uint64_t)i * (uint64_t)tg.NB;
+        sl.fo[(size_t)tg.items[i]] = tg.fft_off[i];
+        sl.ao[(size_t)tg.items[i]] = (uint64_t)i * (uint64_t)tg.NB;
     }
-    uint64_t* d_fo = c_.up(tag + "selfo", fo);
-    uint64_t* d_ao = c_.up(tag + "selao", ao);
-    int* d_fk = c_.up(tag + "selfk", tg.fft_k_track);
-    const SelParams sp = sel_params(cfg_, tg.present, tg.NB, in.top_n, in.gate);
+    sl.fft_k = tg.fft_k_track;
+    sl.fft_bpm = tg.fft_bpm;
+    sl.fft_pow = tg.fft_pow;
+    sl.acf_bpm = tg.acf_bpm;
+    sl.acf_str = tg.acf_str;
+    for (int v = 0; v < NVAR; v++) sl.present[v] = tg.present[v];
+    sl.NB = tg.NB;
+    select_lists(tag, P_T, sl, in.top_n, in.gate, in.cand_cap, o);
+}
+
+// pass_select from its offset tables on (o.active is the pass's); sdsp_debug_tempo_select enters here
+void Pipeline::select_lists(const std::string& tag, int P_T, const SelLists& sl, int top_n, int gate, int cand_cap,
+                            TempoPassOut& o) {
+    uint64_t* d_fo = c_.up(tag + "selfo", sl.fo);
+    uint64_t* d_ao = c_.up(tag + "selao", sl.ao);
+    int* d_fk = c_.up(tag + "selfk", sl.fft_k);
+    const SelParams sp = sel_params(cfg_, sl.present, sl.NB, top_n, gate);
     o.est = c_.dev<TempoEst>(tag + "est", (size_t)std::max(P_T, 1));
-    o.cand = c_.dev<float>(tag + "cand", (size_t)std::max(P_T, 1) * (size_t)in.cand_cap * 4);
-    launch_tempo_select(P_T, o.active, tg.fft_bpm, tg.fft_pow, d_fo, d_fk, tg.acf_bpm, tg.acf_str, d_ao, sp, o.est,
-                        o.cand, in.cand_cap, d_.stream);
+    o.cand = c_.dev<float>(tag + "cand", (size_t)std::max(P_T, 1) * (size_t)cand_cap * 4);
+    launch_tempo_select(P_T, o.active, sl.fft_bpm, sl.fft_pow, d_fo, d_fk, sl.acf_bpm, sl.acf_str, d_ao, sp, o.est,
+                        o.cand, cand_cap, d_.stream);
     SDSP_HIP_CHECK(hipGetLastError());
 }
 
@@ -405,7 +420,11 @@ void Pipeline::escalate(const Front& f, const TempoPassIn& bin, const TempoPassO
         add_pass_times(o1024);
         if (own512) add_pass_times(o512);
         std::vector<TempoEst> e256 = c_.down(o256.est, (size_t)NE), e1024 = c_.down(o1024.est, (size_t)NE);
-        std::vector<int> n256((size_t)NE), n1024((size_t)NE), n512((size_t)NR);
+        MrFuse mf;
+        mf.n256.assign((size_t)NE, 0);
+        mf.n1024.assign((size_t)NE, 0);
+        mf.n512.assign((size_t)NR, 0);
+        std::vector<int> &n256 = mf.n256, &n1024 = mf.n1024, &n512 = mf.n512;  // the fusion's count tables
         for (int k = 0; k < NE; k++) {
             n256[(size_t)k] = e256[(size_t)k].ok ? e256[(size_t)k].n_cands : -1;
             n1024[(size_t)k] = e1024[(size_t)k].ok ? e1024[(size_t)k].n_cands : -1;
@@ -423,26 +442,52 @@ void Pipeline::escalate(const Front& f, const TempoPassIn& bin, const TempoPassO
         } else {
             for (int i = 0; i < NR; i++) n512[(size_t)i] = std::min(best[(size_t)i].n_cands, top_k);
         }
-        int* d_n256 = c_.up("C.n256", n256);
-        int* d_n1024 = c_.up("C.n1024", n1024);
-        int* d_n512 = c_.up("C.n512", n512);
-        int* d_E = c_.up("C.E", E);
-        const int cap512 = own512 ? top_k : bin.cand_cap;
-        TempoEst* d_mr = tp.d_mr_all = c_.dev<TempoEst>("C.mr", (size_t)NE);
-        MrDbg* d_mdbg = dbg_on() ? c_.dev<MrDbg>("C.mrdbg", (size_t)NE) : nullptr;
-        launch_multires(d_E, NE, o256.cand, d_n256, b512.cand, d_n512, o1024.cand, d_n1024, ein.cand_cap, cap512,
-                        ein.cand_cap, bo.est, b512.nov_mr, b512.d_fpfx, mr_params(cfg_, sr_, top_k, own512), d_mr,
-                        tp.d_used, tp.d_fbpm, tp.d_fconf, d_.stream, d_mdbg);
-        SDSP_HIP_CHECK(hipGetLastError());
+        mf.c256 = o256.cand;
+        mf.c512 = b512.cand;
+        mf.c1024 = o1024.cand;
+        mf.cap_aux = ein.cand_cap;
+        mf.cap_base = bin.cand_cap;
+        mf.own512 = own512;
+        mf.base_est = bo.est;
+        mf.nov512 = b512.nov_mr;
+        mf.fpfx512 = b512.d_fpfx;
+        mf.want_dbg = dbg_on();
+        fuse_multires(E, NR, mf, tp);
         if (dbg_on())
-            debug_multires(E, own512, cap512, ein.cand_cap, (size_t)(own512 ? NE : NR), o256, b512, o1024, n256, n512,
-                           n1024, d_mr, d_mdbg, tdbg);
-        tp.used = c_.down(tp.d_used, (size_t)NR);
+            debug_multires(E, own512, mf.cap512, ein.cand_cap, (size_t)(own512 ? NE : NR), o256, b512, o1024, n256, n512,
+                           n1024, tp.d_mr_all, mf.d_mdbg, tdbg);
         for (int i : E)
             if (tp.used[(size_t)i]) res[f.slot[(size_t)i]].mr_used = 1;
     }
     tp.epos.assign((size_t)NR, -1);
     for (size_t k = 0; k < E.size(); k++) tp.epos[(size_t)E[k]] = (int)k;
+    tempo_down(NR, tp);
+}
+
+// escalate's tail (sdsp_debug_multires enters here): the count tables and the item list up,
+// k_multires over the three hops' lists, and which tracks took the multi-resolution estimate back.
+// tp.d_used / d_fbpm / d_fconf hold the base pass's values; the kernel overwrites the accepted tracks'.
+void Pipeline::fuse_multires(const std::vector<int>& E, int NR, MrFuse& m, Tempo& tp) {
+    const int NE = (int)E.size();
+    const int top_k = (int)std::max<uint64_t>(cfg_.tempogram_multi_res_top_k, 1);
+    int* d_n256 = c_.up("C.n256", m.n256);
+    int* d_n1024 = c_.up("C.n1024", m.n1024);
+    int* d_n512 = c_.up("C.n512", m.n512);
+    int* d_E = c_.up("C.E", E);
+    const int cap512 = m.cap512 = m.own512 ? top_k : m.cap_base;
+    for (int n : m.n512)  // k_tempo_select writes at most SEL_MAXC = MR_HYP_MAX
+        if (std::min(top_k, n) > MR_HYP_MAX) throw HipError("multi-resolution fusion: more than 1024 hop-512 candidates");
+    TempoEst* d_mr = tp.d_mr_all = c_.dev<TempoEst>("C.mr", (size_t)NE);
+    MrDbg* d_mdbg = m.d_mdbg = m.want_dbg ? c_.dev<MrDbg>("C.mrdbg", (size_t)NE) : nullptr;
+    launch_multires(d_E, NE, m.c256, d_n256, m.c512, d_n512, m.c1024, d_n1024, m.cap_aux, cap512, m.cap_aux, m.base_est,
+                    m.nov512, m.fpfx512, mr_params(cfg_, sr_, top_k, m.own512), d_mr, tp.d_used, tp.d_fbpm, tp.d_fconf,
+                    d_.stream, d_mdbg);
+    SDSP_HIP_CHECK(hipGetLastError());
+    tp.used = c_.down(tp.d_used, (size_t)NR);
+}
+
+// the estimates as they stand back on the host
+void Pipeline::tempo_down(int NR, Tempo& tp) {
     tp.fbpm_h = c_.down(tp.d_fbpm, (size_t)NR);
     tp.fconf_h = c_.down(tp.d_fconf, (size_t)NR);
 }

@@ -863,6 +863,158 @@ def debug_tempo_stages(specs, sample_rate=44100, hop=512, config=None, device=0)
     return meta, tracks
 
 
+class SdspDebugTempoEst(C.Structure):
+    """sdsp_debug_tempo_est (include/stratum_hip_debug.h)."""
+    _fields_ = [("bpm", C.c_float), ("conf", C.c_float), ("agree", C.c_int32), ("ok", C.c_int32), ("n_cands", C.c_int32),
+                ("ambiguous", C.c_int32), ("trap_low", C.c_int32), ("trap_high", C.c_int32)]
+
+
+class SdspDebugMrDbg(C.Structure):
+    """sdsp_debug_mr_dbg (include/stratum_hip_debug.h)."""
+    _fields_ = ([(n, C.c_int32) for n in ("fd", "fu", "tf")] + [(n, C.c_float) for n in ("fd_from", "fd_to", "fd_ratio")] +
+                [(n, C.c_int32) for n in ("fd_a0", "fd_a1")] + [(n, C.c_float) for n in ("fu_from", "fu_to", "fu_ratio")] +
+                [(n, C.c_int32) for n in ("fu_a0", "fu_a1")] +
+                [(n, C.c_float) for n in ("tf_from", "tf_to", "tf_sup0", "tf_sup1", "tf_al0", "tf_al1")] +
+                [("tf_label", C.c_int32), ("rel", C.c_float)] + [(n, C.c_int32) for n in ("fam", "forbid", "better")])
+
+
+class SdspDebugMultiresIn(C.Structure):
+    """sdsp_debug_multires_in (include/stratum_hip_debug.h)."""
+    _fields_ = ([(n, C.POINTER(C.c_float)) for n in ("c256", "c512", "c1024")] +
+                [(n, C.POINTER(C.c_int32)) for n in ("n256", "n512", "n1024")] +
+                [("cap_aux", C.c_uint32), ("cap_base", C.c_uint32), ("nov512", C.POINTER(C.c_float)),
+                 ("nov_n", C.POINTER(C.c_uint64)), ("base", C.POINTER(SdspDebugTempoEst)),
+                 ("items", C.POINTER(C.c_int32)), ("n_items", C.c_uint64), ("n_tracks", C.c_uint64),
+                 ("own512", C.c_int32)])
+
+
+class SdspDebugMultiresOut(C.Structure):
+    """sdsp_debug_multires_out (include/stratum_hip_debug.h)."""
+    _fields_ = [("mr", C.POINTER(SdspDebugTempoEst)), ("dbg", C.POINTER(SdspDebugMrDbg)), ("used", C.POINTER(C.c_int32)),
+                ("final_bpm", C.POINTER(C.c_float)), ("final_conf", C.POINTER(C.c_float))]
+
+
+def _est_dict(e):
+    return dict(bpm=np.float32(e.bpm), conf=np.float32(e.conf), agree=e.agree, ok=e.ok, n_cands=e.n_cands,
+                ambiguous=e.ambiguous, trap_low=e.trap_low, trap_high=e.trap_high)
+
+
+def debug_tempo_select(tracks, present=(1, 1, 1, 1, 1), top_n=10, cand_cap=10, gate=False, config=None,
+                       sample_rate=44100, device=0):
+    """The candidate selection over host tempogram lists (sdsp_debug_tempo_select).  tracks: dicts of
+    fft and acf ({variant name: (n, 2) array of (bpm, value)} for the present variants; the fft lists
+    of one track share their length, the acf lists of the call theirs) and optionally active
+    (default True).  Returns per track the TempoEst fields (bpm, conf, agree, ok, n_cands, ambiguous,
+    trap_low, trap_high) and cands (n_cands, 4)."""
+    cfg = config if config is not None else default_config()
+    T = len(tracks)
+    on = [VARIANTS[v] for v in range(5) if present[v]]
+
+    def length(lists):
+        ns = {np.asarray(lists[k], np.float32).reshape(-1, 2).shape[0] for k in on}
+        if len(ns) != 1:
+            raise ValueError("one list length per track over the present variants")
+        return ns.pop()
+
+    fft_n = np.array([length(t["fft"]) for t in tracks], np.int32)
+    nbs = {length(t["acf"]) for t in tracks}
+    if len(nbs) != 1:
+        raise ValueError("one autocorrelation list length per call")
+    NB = nbs.pop()
+    fft = np.zeros((5 * int(fft_n.sum()) + 1, 2), np.float32)
+    acf = np.zeros((T, 5, max(NB, 1), 2), np.float32)
+    at = 0
+    for t, trk in enumerate(tracks):
+        K = int(fft_n[t])
+        for v in range(5):
+            if present[v]:
+                fft[at + v * K:at + (v + 1) * K] = np.asarray(trk["fft"][VARIANTS[v]], np.float32).reshape(-1, 2)
+                acf[t, v, :NB] = np.asarray(trk["acf"][VARIANTS[v]], np.float32).reshape(-1, 2)
+        at += 5 * K
+    acf = np.ascontiguousarray(acf[:, :, :NB]) if NB else acf
+    active = np.array([1 if t.get("active", True) else 0 for t in tracks], np.int32)
+    pres = (C.c_int32 * 5)(*[int(bool(p)) for p in present])
+    est = (SdspDebugTempoEst * T)()
+    cand = np.zeros((T, max(cand_cap, 1), 4), np.float32)
+    f = lib().sdsp_debug_tempo_select
+    fp, i32p = C.POINTER(C.c_float), C.POINTER(C.c_int32)
+    f.argtypes = [fp, i32p, fp, C.c_uint32, i32p, i32p, C.c_uint64, C.c_int32, C.c_int32, C.c_int32, C.c_uint32,
+                  C.POINTER(SdspConfig), C.POINTER(SdspDebugTempoEst), fp, C.c_int32]
+    f.restype = C.c_int32
+    st = f(_fp(fft), fft_n.ctypes.data_as(i32p), _fp(acf), NB, pres, active.ctypes.data_as(i32p), T, top_n, cand_cap,
+           int(bool(gate)), sample_rate, C.byref(cfg), est, _fp(cand), device)
+    if st != 0:
+        raise AnalysisError(st, "debug_tempo_select failed")
+    out = []
+    for t in range(T):
+        d = _est_dict(est[t])
+        d["cands"] = cand[t, :est[t].n_cands].copy()
+        out.append(d)
+    return out
+
+
+def debug_multires(items, tracks, base, own512=False, cap_aux=None, cap_base=None, config=None, sample_rate=44100,
+                   used=None, final_bpm=None, final_conf=None, device=0):
+    """The multi-resolution fusion over host candidate lists (sdsp_debug_multires).  base: one
+    (bpm, conf, agree, trap_low, trap_high) per track of the call; items: dicts of track (ascending),
+    c256 and c1024 ((n, 4) arrays, or None for a failed hop) and, with own512, c512 and nov; tracks
+    (without own512): one dict of c512 and nov per track of the call.  used / final_bpm / final_conf:
+    the values uploaded first (default: 0 and the base estimate).  Returns (per item: the
+    multi-resolution TempoEst fields and dbg, the MrDbg fields), used, final_bpm, final_conf."""
+    cfg = config if config is not None else default_config()
+    NR, NE = len(base), len(items)
+    top_k = max(int(cfg.tempogram_multi_res_top_k), 1)
+    rows = items if own512 else tracks
+
+    def pack(lists, cap):
+        n = np.array([-1 if a is None else len(a) for a in lists], np.int32)
+        buf = np.zeros((max(len(lists), 1), cap, 4), np.float32)
+        for r, a in enumerate(lists):
+            if a is not None and len(a):  # a list longer than cap keeps its count: the probe refuses it
+                buf[r, :min(len(a), cap)] = np.asarray(a, np.float32).reshape(-1, 4)[:cap]
+        return buf, n
+
+    lens = [len(a) for it in items for a in (it["c256"], it["c1024"]) if a is not None]
+    cap_aux = cap_aux if cap_aux is not None else max(lens + [1])
+    l512 = [r["c512"] for r in rows]
+    cap_base = cap_base if cap_base is not None else max([len(a) for a in l512 if a is not None] + [1])
+    cap512 = top_k if own512 else cap_base
+    c256, n256 = pack([it["c256"] for it in items], cap_aux)
+    c1024, n1024 = pack([it["c1024"] for it in items], cap_aux)
+    c512, n512 = pack(l512, cap512)
+    novs = [np.asarray(r["nov"], np.float32).ravel() for r in rows]
+    nov_n = np.array([a.size for a in novs] + [0], np.uint64)
+    nov = np.ascontiguousarray(np.concatenate(novs + [np.zeros(1, np.float32)]))
+    b = (SdspDebugTempoEst * NR)()
+    for t, e in enumerate(base):
+        b[t].bpm, b[t].conf, b[t].agree, b[t].ok = e[0], e[1], int(e[2]), 1
+        b[t].trap_low, b[t].trap_high = int(bool(e[3])), int(bool(e[4]))
+    E = np.array([int(it["track"]) for it in items] + [0], np.int32)
+    u = np.zeros(NR, np.int32) if used is None else np.array(used, np.int32)
+    fb = np.array([e[0] for e in base], np.float32) if final_bpm is None else np.array(final_bpm, np.float32)
+    fc = np.array([e[1] for e in base], np.float32) if final_conf is None else np.array(final_conf, np.float32)
+    mr, dbg = (SdspDebugTempoEst * max(NE, 1))(), (SdspDebugMrDbg * max(NE, 1))()
+    fp, i32p, u64p = C.POINTER(C.c_float), C.POINTER(C.c_int32), C.POINTER(C.c_uint64)
+    i = SdspDebugMultiresIn(_fp(c256), _fp(c512), _fp(c1024), n256.ctypes.data_as(i32p), n512.ctypes.data_as(i32p),
+                            n1024.ctypes.data_as(i32p), cap_aux, cap_base, _fp(nov), nov_n.ctypes.data_as(u64p), b,
+                            E.ctypes.data_as(i32p), NE, NR, int(bool(own512)))
+    o = SdspDebugMultiresOut(mr, dbg, u.ctypes.data_as(i32p), _fp(fb), _fp(fc))
+    f = lib().sdsp_debug_multires
+    f.argtypes = [C.POINTER(SdspDebugMultiresIn), C.c_uint32, C.POINTER(SdspConfig), C.POINTER(SdspDebugMultiresOut),
+                  C.c_int32]
+    f.restype = C.c_int32
+    st = f(C.byref(i), sample_rate, C.byref(cfg), C.byref(o), device)
+    if st != 0:
+        raise AnalysisError(st, "debug_multires failed")
+    out = []
+    for k in range(NE):
+        d = _est_dict(mr[k])
+        d["dbg"] = {n: (np.float32(getattr(dbg[k], n)) if ty is C.c_float else getattr(dbg[k], n))
+                    for n, ty in SdspDebugMrDbg._fields_}
+        out.append(d)
+    return out, u, fb, fc
+
+
 KV_ROW = 128  # floats per segment scratch row of the key vote (csrc/kernels.hpp)
 
 

@@ -111,9 +111,27 @@ STRUCTS = {"sdsp_config": sdsp_abi.SdspConfig, "sdsp_result": sdsp_abi.SdspResul
            "sdsp_confidence": sdsp_abi.SdspConfidence}
 
 
+# the stage probes' record and argument structs (include/stratum_hip_debug.h): the tempo estimate and
+# the multi-resolution decision record mirror the kernels' TempoEst and MrDbg (static_assert on the
+# library's side), and these ctypes classes mirror the header
+DEBUG_STRUCTS = {"sdsp_debug_tempo_est": sdsp.SdspDebugTempoEst, "sdsp_debug_mr_dbg": sdsp.SdspDebugMrDbg,
+                 "sdsp_debug_multires_in": sdsp.SdspDebugMultiresIn, "sdsp_debug_multires_out": sdsp.SdspDebugMultiresOut,
+                 "sdsp_debug_key_out": sdsp.SdspDebugKeyOut, "sdsp_debug_key_dbg": sdsp.SdspDebugKeyDbg,
+                 "sdsp_debug_key_vote_out": sdsp.SdspDebugKeyVoteOut}
+
+
 def test_struct_layout_matches_header(tmp_path):
-    lines = ['#include <stdio.h>', '#include <stddef.h>', f'#include "{HEADER}"', "int main(void) {"]
-    for cname, py in STRUCTS.items():
+    _check_layout(tmp_path, HEADER, STRUCTS)
+
+
+def test_debug_struct_layout_matches_header(tmp_path):
+    _check_layout(tmp_path, DEBUG_HEADER, DEBUG_STRUCTS)
+    assert C.sizeof(sdsp.SdspDebugTempoEst) == 32 and C.sizeof(sdsp.SdspDebugMrDbg) == 96
+
+
+def _check_layout(tmp_path, header, structs):
+    lines = ['#include <stdio.h>', '#include <stddef.h>', f'#include "{header}"', "int main(void) {"]
+    for cname, py in structs.items():
         lines.append(f'printf("{cname} size %zu\\n", sizeof({cname}));')
         for f, _ in py._fields_:
             lines.append(f'printf("{cname}.{f} %zu\\n", offsetof({cname}, {f}));')
@@ -128,7 +146,7 @@ def test_struct_layout_matches_header(tmp_path):
         if ln:
             k, v = ln.rsplit(" ", 1)
             c[k] = int(v)
-    for cname, py in STRUCTS.items():
+    for cname, py in structs.items():
         assert c[f"{cname} size"] == C.sizeof(py), cname
         for f, _ in py._fields_:
             assert c[f"{cname}.{f}"] == getattr(py, f).offset, f"{cname}.{f}"

@@ -1,8 +1,9 @@
-"""The oracle's stage exports (oracle/units.py: tempo_stages, spectral_flux_curve, key_stages, key_vote)
-pinned against exports that are already pinned.  The stage tests on the GPU (test_gpu_tempo_stages.py,
-test_gpu_key_stages.py, test_gpu_key_vote.py) compare kernels with these exports, so the exports themselves must be the
-arithmetic the whole-track oracle runs: they are taken from inside tempogram_impl and from the key
-conditioning analyze calls, not restated.
+"""The oracle's stage exports (oracle/units.py: tempo_stages, spectral_flux_curve, key_stages, key_vote,
+tempo_select, multires_fuse) pinned against exports that are already pinned.  The stage tests on the
+GPU (test_gpu_tempo_stages.py, test_gpu_key_stages.py, test_gpu_key_vote.py, test_gpu_tempo_select.py,
+test_gpu_multires_stages.py) compare kernels with these exports, so the exports themselves must be the
+arithmetic the whole-track oracle runs: they are taken from inside tempogram_impl, multi_resolution
+and analyze and from the key conditioning analyze calls, not restated.
 """
 import numpy as np
 import pytest
@@ -166,3 +167,75 @@ def test_chained_exports_reproduce_the_base_estimate(seed, bpm):
         assert _same(np.array(acf, np.float32).reshape(-1, 2), v["acf"]), name
     base = tr["base"]
     assert est[0] > 0 and _same(est[:2], base[:2]) and est[2] == base[2], (est, base)
+
+
+# ---- the tempo decision stages: tempo_select and multires_fuse are the functions tempogram_impl,
+# multi_resolution and analyze call, so over the whole-track oracle's own lists they give its results ----
+_FIXTURES = ["120bpm_4bar.wav", "128bpm_4bar.wav", "cmajor_scale.wav", "mixed_silence.wav"]
+
+
+def _variants(cfg, st):
+    import tempo_select_cases as S
+
+    w = S.weights(cfg)
+    return [(n, w[n], v["fft"], v["acf"]) for n, v in st.items()]
+
+
+def _select(m, sr, hop, cfg):
+    st = units.tempo_stages(m, sr, hop, cfg)
+    est = units.tempo_stages_estimate()
+    return st, est, units.tempo_select(_variants(cfg, st), cfg.min_bpm, cfg.max_bpm, cfg.bpm_resolution, cfg)
+
+
+@pytest.mark.parametrize("what", _FIXTURES + ["spec:130", "spec:301"])
+def test_tempo_select_over_stage_lists_is_the_stage_estimate(what):
+    """tempo_select over the lists tempo_stages exports equals the estimate tempogram_impl made from
+    them, bit for bit; on the fixtures also analyze's base estimate, candidates and gate decision."""
+    import os
+
+    import parity
+
+    cfg = oracle.default_config()
+    if what.startswith("spec:"):
+        m, sr, tr = _spec(int(what[5:]), int(what[5:]), 1025), 44100, None
+    else:
+        x, sr = parity.load_wav(os.path.join(os.path.dirname(__file__), "golden", what))
+        rc, _, tr = oracle.analyze(x, sr, trace=True)
+        assert rc == 0 and tr["has_tempogram"]
+        _, xn = oracle.normalize(x, 0, sr)
+        m = oracle.stft(xn[tr["trim_start"]:tr["trim_end"]], 2048, 512)
+    st, est, sel = _select(m, sr, 512, cfg)
+    assert sel is not None and est[0] > 0
+    assert _same([sel["bpm"], sel["conf"]], est[:2]) and sel["agree"] == est[2]
+    if tr is not None and tr["has_tempogram"]:
+        assert _same(est[:2], tr["base"][:2]) and est[2] == tr["base"][2]
+        bc = np.array(tr["base_cands"], np.float32).reshape(-1, 4)
+        assert _same(sel["cands"][:len(bc)], bc)
+        assert sel["ambiguous"] == tr["ambiguous"]
+
+
+@pytest.mark.parametrize("seed,bpm", [(301, 90.0), (306, 188.0), (319, 198.0), (310, 180.5)])
+def test_multires_fuse_over_hop_lists_is_the_escalation(seed, bpm):
+    """On escalating tracks, the candidate lists tempogram_impl gives at hops 256, 512 and 1024 (each
+    through tempo_stages and tempo_select, truncated as multi_resolution truncates them) and the hop-512
+    novelty, through multires_fuse, give analyze's multi-resolution estimate and acceptance, bit for bit."""
+    x = synth.make_track(seed, seconds=20.0, bpm=bpm)[0]
+    rc, _, tr = oracle.analyze(x, 44100, trace=True)
+    assert rc == 0 and tr["ambiguous"] and tr["ran_mr"]
+    cfg = oracle.default_config()
+    _, xn = oracle.normalize(x, 0)
+    xt = xn[tr["trim_start"]:tr["trim_end"]]
+    top_k = int(cfg.tempogram_multi_res_top_k)
+    aux_k = min(max(4 * top_k, 25), 200)
+    lists, base, nov = {}, None, None
+    for hop, k in ((256, aux_k), (512, top_k), (1024, aux_k)):
+        st, _, sel = _select(oracle.stft(xt, 2048, hop), 44100, hop, cfg)
+        lists[hop] = sel["cands"][:k]
+        if hop == 512:
+            assert _same([sel["bpm"], sel["conf"]], tr["base"][:2])
+            base = (sel["bpm"], sel["conf"], sel["agree"], sel["trap_low"], sel["trap_high"])
+            nov = st["full"]["nov"]
+    r = units.multires_fuse(lists[256], lists[512], lists[1024], nov, 44100, base, cfg)
+    assert r["ok"]
+    assert _same([r["bpm"], r["conf"]], tr["mr"][:2]) and r["agree"] == tr["mr"][2], (r["bpm"], r["conf"], tr["mr"])
+    assert r["used"] == tr["used_mr"]
