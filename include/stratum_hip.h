@@ -472,6 +472,113 @@ int32_t sdsp_analyze_batch_device_requests(const float* d_samples, const uint64_
 void sdsp_key_timeline_free(sdsp_key_timeline* t);
 
 /*
+ * Levels: the loudness metadata of the reference's normalize() and the silence map of its
+ * detect_and_trim(), both of which analyze_audio computes and drops
+ * (src/preprocessing/normalization.rs:64-73, 262-547; src/preprocessing/silence.rs:102-279),
+ * computed inside the analysis call from the samples on the device.
+ *
+ * method[m], for each method bit m of the request (bit m = NormalizationMethod m), is what
+ *   normalize(copy of the caller's raw track, {method m, -14 LUFS, 1 dB}, sample_rate)
+ * returns, whatever cfg.normalization and cfg.enable_normalization say.  With peak = max |x|,
+ * target = 10^(-1/20), dB(v) = 20 log10(v), every sum the sequential f32 fold from 0 in sample order,
+ * every log10 / pow include/sdsp_libm.h's, the K-weighting coefficients as the engine's own
+ * normalisation computes them:
+ *   Peak      peak <= 1e-10: peak_db = rms_db = -inf, gain_db = 0, gain = 1.  Else peak_db = dB(peak),
+ *             gain_db = dB(target / peak) while the applied gain = min(target / peak, 1 / peak)
+ *             (normalization.rs:291-295: the metadata is that of the unlimited gain), and rms_db is
+ *             the RMS of the *normalised* samples, sqrt(sum (x * gain)^2 / n) (:303), -inf at or
+ *             below 1e-10.
+ *   RMS       rms = sqrt(sum x^2 / n) of the raw samples; rms <= 1e-10 as the quiet Peak case.  Else
+ *             rms_db = dB(rms) (raw), peak_db = dB(peak), gain = 10^((-14 + 3 - 1) / 20) / rms, or
+ *             1 / peak when peak * gain > 1; gain_db = dB(applied gain).
+ *   Loudness  measured_lufs = -0.691 + 10 log10(mean of the 400-ms blocks' mean squares of the
+ *             K-weighted signal that exceed 10^((-70 + 0.691) / 10)); gain = 10^((-14 - lufs) / 20), or
+ *             target / peak when peak * gain > target (gain_db then dB(target / peak), else -14 - lufs);
+ *             rms_db the RMS of the normalised samples (:443, :464).  With every block under the gate
+ *             the reference falls back to normalize_peak: the Peak metadata, has_lufs 0.  This is the
+ *             reference's measure: one shelving stage, no relative gate (BS.1770 has a second stage
+ *             and a relative gate; the reference has neither).  The NumericalError branch of
+ *             calculate_lufs cannot be reached: a gated mean exceeds the gate, about 1.17e-7, and the
+ *             branch tests mean <= 1e-10.
+ * A method the request does not ask for has measured 0 and zeroed fields.  -inf is reported as -inf;
+ * measured_lufs is -inf wherever has_lufs is 0 (the reference's None).
+ *
+ * The silence map (SDSP_LEVELS_SILENCE_MAP) is detect_and_trim's second return value on the signal
+ * raw * applied_gain, with the detector {cfg.min_amplitude_db, 500 ms, cfg.frame_size}: frames of
+ * frame_size every frame_size / 2, silent when their RMS <= 10^(threshold_db / 20), runs of silent
+ * frames as regions [start_sample, end_sample) in the caller's track, ascending.
+ *   - the run starting at frame 0 is kept whatever its length; an interior run is kept from
+ *     min_duration_frames = ceil((u64)(0.5f * sample_rate) / (frame_size / 2)) frames on;
+ *   - a trailing run (ending with the last frame, end_sample = n) shorter than that is dropped: the
+ *     reference's in-loop test `silence_end_frame == num_frames` can never be true, a run found in the
+ *     loop ends at a frame index < num_frames;
+ *   - duration_seconds = (f32)(end_sample - start_sample) / (f32)sample_rate.
+ * The map is computed when requested even with enable_silence_trimming off (it is a pure function
+ * of the signal; trim_start / trim_end are then 0 / n).
+ *
+ * Per track: every track with n > 0, sample_rate > 0 and a supported configuration has status
+ * SDSP_OK, including one whose analysis fails with "entirely silent after trimming".  Any other track
+ * carries the analysis status and zeroed fields.  If the configured normalisation itself fails,
+ * method[m].status carries the error, applied_gain is 1 and the map is empty.  Non-finite samples
+ * are out of scope.  True peak, loudness range and per-channel levels are not computed.
+ */
+enum sdsp_levels_what { /* bits of sdsp_levels_request.what */
+    SDSP_LEVELS_PEAK = 1, SDSP_LEVELS_RMS = 2, SDSP_LEVELS_LOUDNESS = 4, /* bit m = NormalizationMethod m */
+    SDSP_LEVELS_SILENCE_MAP = 8
+};
+typedef struct sdsp_levels_request { uint32_t what; } sdsp_levels_request;
+
+typedef struct sdsp_loudness { /* LoudnessMetadata of one method, normalization.rs:64-73 */
+    int32_t status;            /* SDSP_OK, or the error normalize() returns for this method */
+    int8_t measured;           /* 1 iff the request asked for this method */
+    int8_t has_lufs;           /* measured_lufs is Some */
+    float measured_lufs, peak_db, rms_db, gain_db;
+    float gain; /* the f32 the reference multiplies the samples by (1.0f where it applies none) */
+} sdsp_loudness;
+
+typedef struct sdsp_silence_region { uint64_t start_sample, end_sample; float duration_seconds; } sdsp_silence_region;
+
+typedef struct sdsp_levels {
+    sdsp_loudness method[3];       /* index = enum sdsp_normalization */
+    float applied_gain;            /* what this analysis multiplied by (1.0f with normalisation off) */
+    uint64_t n_samples;            /* the caller's track length */
+    uint64_t trim_start, trim_end; /* the bounds the analysis used, in the caller's track */
+    uint32_t frame_size;           /* the detector's: cfg.frame_size */
+    float threshold_db;            /* ... and cfg.min_amplitude_db */
+    uint64_t n_regions;
+    sdsp_silence_region* regions;  /* library-owned, NULL for none */
+    int32_t status;
+} sdsp_levels;
+
+/*
+ * The optional requests of one analysis call, by name: a later request is a new pair of fields at
+ * the end, and a caller built against an older header (a smaller struct_size) keeps working.
+ */
+typedef struct sdsp_request_set {
+    uint32_t struct_size; /* sizeof(sdsp_request_set) of the caller; fields past it read as NULL */
+    const sdsp_overview_request* ov_req;     sdsp_overview* overviews;
+    const sdsp_key_timeline_request* kt_req; sdsp_key_timeline* timelines;
+    const sdsp_levels_request* lv_req;       sdsp_levels* levels;
+} sdsp_request_set;
+
+/*
+ * sdsp_analyze_batch_device_ex with any of the optional requests from one analysis: overviews and
+ * key timelines as in sdsp_analyze_batch_device_requests (which forwards here), levels (n_tracks
+ * entries, freed one by one with sdsp_levels_free) as above, with SDSP_STAGES_FULL and
+ * SDSP_STAGES_BPM_ONLY alike.  set == NULL, or a set with every request NULL, is
+ * sdsp_analyze_batch_device_ex itself (the same launches, the same results).  A request never
+ * changes an sdsp_result.  Refused with SDSP_ERR_INVALID_INPUT before any device is touched, beside
+ * what sdsp_analyze_batch_device_requests refuses: a levels request with what == 0 or with unknown
+ * bits, a request without its output array, a struct_size smaller than the first request pair.
+ */
+int32_t sdsp_analyze_batch_device_with(const float* d_samples, const uint64_t* offsets, const uint64_t* lens,
+                                       uint64_t n_tracks, uint32_t sample_rate, const sdsp_config* cfg,
+                                       int32_t device, void* stream, int32_t stages, sdsp_result* outs,
+                                       const sdsp_request_set* set);
+/* Frees the regions owned by one sdsp_levels. */
+void sdsp_levels_free(sdsp_levels* l);
+
+/*
  * Synthetic track generator on device: writes n_tracks tracks of `len`
  * samples each, track i at d_out + i*len, seeds seed0 + i.  bpm_out/key_out (host, may be
  * NULL) receive the generated tempo and key (key = mode*12 + tonic).  bpm_mode 0 = uniform

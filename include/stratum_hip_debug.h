@@ -114,6 +114,19 @@ typedef struct sdsp_debug_overview_times {
 int32_t sdsp_debug_last_overview_times(int32_t device, sdsp_debug_overview_times* out);
 
 /*
+ * The levels folds of the last sdsp_analyze_batch_device_with call with a levels request on
+ * `device`: HIP event times of the first launch (the peak kernels and k_levels_fold with every
+ * chain but Loudness' rms_db) and of the second (k_levels_gain and that chain), and the tracks
+ * folded.  The events lie on the fold stream, so beside a running analysis they include what the
+ * folds waited for.  All zero after a call without a request.
+ */
+typedef struct sdsp_debug_levels_times {
+    double fold_ms, fold2_ms;
+    uint64_t tracks;
+} sdsp_debug_levels_times;
+int32_t sdsp_debug_last_levels_times(int32_t device, sdsp_debug_levels_times* out);
+
+/*
  * Stage probe of the key timeline (include/stratum_hip.h, sdsp_key_timeline): the timeline kernel
  * and the host's primary-key and change logic over uploaded chroma rows, taken as the smoothed rows
  * C of the definition.  host_chroma: the tracks' rows back to back, frames[t] rows of 12 floats for

@@ -208,7 +208,86 @@ pub struct sdsp_result {
     pub error_message: [c_char; 256],
 }
 
+/// Bits of `sdsp_levels_request.what` (`enum sdsp_levels_what`); bit m = NormalizationMethod m.
+pub const SDSP_LEVELS_PEAK: u32 = 1;
+pub const SDSP_LEVELS_RMS: u32 = 2;
+pub const SDSP_LEVELS_LOUDNESS: u32 = 4;
+pub const SDSP_LEVELS_SILENCE_MAP: u32 = 8;
+
+/// `sdsp_levels_request`
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct sdsp_levels_request {
+    pub what: u32,
+}
+
+/// `sdsp_loudness`: LoudnessMetadata of one method (src/preprocessing/normalization.rs:64-73) and
+/// the gain the reference multiplies the samples by
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct sdsp_loudness {
+    pub status: i32,
+    pub measured: i8,
+    pub has_lufs: i8,
+    pub measured_lufs: f32,
+    pub peak_db: f32,
+    pub rms_db: f32,
+    pub gain_db: f32,
+    pub gain: f32,
+}
+
+/// `sdsp_silence_region`: `[start_sample, end_sample)` in the caller's track
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct sdsp_silence_region {
+    pub start_sample: u64,
+    pub end_sample: u64,
+    pub duration_seconds: f32,
+}
+
+/// `sdsp_levels`: `regions` is owned by the library until `sdsp_levels_free`.
+#[repr(C)]
+pub struct sdsp_levels {
+    pub method: [sdsp_loudness; 3],
+    pub applied_gain: f32,
+    pub n_samples: u64,
+    pub trim_start: u64,
+    pub trim_end: u64,
+    pub frame_size: u32,
+    pub threshold_db: f32,
+    pub n_regions: u64,
+    pub regions: *mut sdsp_silence_region,
+    pub status: i32,
+}
+
+/// `sdsp_request_set`: the optional requests of `sdsp_analyze_batch_device_with`.  The overview and
+/// key timeline pairs are not bound here (null pointers leave them out).
+#[repr(C)]
+pub struct sdsp_request_set {
+    pub struct_size: u32,
+    pub ov_req: *const c_void,
+    pub overviews: *mut c_void,
+    pub kt_req: *const c_void,
+    pub timelines: *mut c_void,
+    pub lv_req: *const sdsp_levels_request,
+    pub levels: *mut sdsp_levels,
+}
+
 extern "C" {
+    pub fn sdsp_analyze_batch_device_with(
+        d_samples: *const f32,
+        offsets: *const u64,
+        lens: *const u64,
+        n_tracks: u64,
+        sample_rate: u32,
+        cfg: *const sdsp_config,
+        device: i32,
+        stream: *mut c_void,
+        stages: i32,
+        outs: *mut sdsp_result,
+        set: *const sdsp_request_set,
+    ) -> i32;
+    pub fn sdsp_levels_free(l: *mut sdsp_levels);
     pub fn sdsp_config_default(cfg: *mut sdsp_config);
     pub fn sdsp_analyze_audio(
         samples: *const f32,

@@ -25,11 +25,15 @@
 // "key_timeline" member (include/stratum_hip.h, sdsp_key_timeline): the key of every SEC-second
 // segment (overlapping by OVERLAP seconds, default SEC / 4), the primary key and the key changes
 // whose confidence exceeds MINCONF (default -1: every change; 0.2 is the reference's constant), with
-// key names.  It runs through sdsp_analyze_batch_device_requests like --overview and combines with it
+// key names.  It runs through sdsp_analyze_batch_device_with like --overview and combines with it
 // in one analysis.
+// --levels [LIST] (opt-in; JSONL only): each line's object gets a "levels" member
+// (include/stratum_hip.h, sdsp_levels): the loudness metadata of each normalisation method in LIST
+// (out of peak,rms,loudness,silence; all four without a list), -inf as null, and the silence
+// regions as [start_sample, end_sample, seconds].  It combines with the other two in one analysis.
 //
 //   analyze_batch [--jobs N] [--devices MASK] [--json] [--gpu-decode] [--overview N | --overview-frames K]
-//                 [--key-timeline SEC[:OVERLAP[:MINCONF]]] <file1> <file2> ...
+//                 [--key-timeline SEC[:OVERLAP[:MINCONF]]] [--levels [LIST]] <file1> <file2> ...
 #include <algorithm>
 #include <atomic>
 #include <chrono>
@@ -57,6 +61,7 @@ struct Item {
     int8_t tr[4] = {-1, -1, -1, -1};
     std::string overview;  // --overview: the "overview" member's value
     std::string timeline;  // --key-timeline: the "key_timeline" member's value
+    std::string levels;    // --levels: the "levels" member's value
 };
 
 // floats so that an f32 round-trips
@@ -122,6 +127,39 @@ std::string key_timeline_json(const sdsp_key_timeline& t) {
                       i ? "," : "", (unsigned long long)c.segment, (double)c.timestamp, c.from_key,
                       json_str(key_index_name(c.from_key)).c_str(), c.to_key, json_str(key_index_name(c.to_key)).c_str(),
                       (double)c.confidence);
+        s += b;
+    }
+    return s + "]}";
+}
+
+// an f32 so that it round-trips; -inf (a level of silence, no LUFS value) as null
+std::string json_db(float v) {
+    if (!std::isfinite(v)) return "null";
+    char b[32];
+    std::snprintf(b, sizeof b, "%.9g", (double)v);
+    return b;
+}
+std::string levels_json(const sdsp_levels& l) {
+    static const char* const names[3] = {"peak", "rms", "loudness"};
+    char b[256];
+    std::snprintf(b, sizeof b,
+                  "{\"status\":%d,\"n_samples\":%llu,\"applied_gain\":%.9g,\"trim_start\":%llu,\"trim_end\":%llu,"
+                  "\"frame_size\":%u,\"threshold_db\":%.9g",
+                  l.status, (unsigned long long)l.n_samples, (double)l.applied_gain, (unsigned long long)l.trim_start,
+                  (unsigned long long)l.trim_end, l.frame_size, (double)l.threshold_db);
+    std::string s = b;
+    for (int m = 0; m < 3; m++) {
+        const sdsp_loudness& e = l.method[m];
+        if (!e.measured) continue;
+        s += std::string(",\"") + names[m] + "\":{\"status\":" + std::to_string(e.status) +
+             ",\"measured_lufs\":" + (e.has_lufs ? json_db(e.measured_lufs) : std::string("null")) +
+             ",\"peak_db\":" + json_db(e.peak_db) + ",\"rms_db\":" + json_db(e.rms_db) + ",\"gain_db\":" +
+             json_db(e.gain_db) + ",\"gain\":" + json_db(e.gain) + "}";
+    }
+    s += ",\"n_regions\":" + std::to_string((unsigned long long)l.n_regions) + ",\"regions\":[";
+    for (uint64_t i = 0; i < l.n_regions; i++) {
+        std::snprintf(b, sizeof b, "%s[%llu,%llu,%.9g]", i ? "," : "", (unsigned long long)l.regions[i].start_sample,
+                      (unsigned long long)l.regions[i].end_sample, (double)l.regions[i].duration_seconds);
         s += b;
     }
     return s + "]}";
@@ -206,6 +244,8 @@ int main(int argc, char** argv) {
     bool overview = false;
     sdsp_key_timeline_request ktreq{0.0f, 0.0f, 0, 0, -1.0f};
     bool timeline = false;
+    sdsp_levels_request lvreq{SDSP_LEVELS_PEAK | SDSP_LEVELS_RMS | SDSP_LEVELS_LOUDNESS | SDSP_LEVELS_SILENCE_MAP};
+    bool levels = false;
     std::vector<std::string> paths;
     for (size_t i = 0; i < a.size(); i++) {
         const std::string& s = a[i];
@@ -259,10 +299,31 @@ int main(int argc, char** argv) {
             ktreq.min_change_confidence = v[2];
             timeline = true;
             i++;
+        } else if (s == "--levels") {
+            // an optional list out of peak,rms,loudness,silence (the next argument when it is such a list)
+            levels = true;
+            uint32_t what = 0;
+            bool list = i + 1 < a.size() && !a[i + 1].empty();
+            for (size_t p0 = 0; list;) {
+                const std::string& w = a[i + 1];
+                const size_t p1 = std::min(w.find(',', p0), w.size());
+                const std::string part = w.substr(p0, p1 - p0);
+                if (part == "peak") what |= SDSP_LEVELS_PEAK;
+                else if (part == "rms") what |= SDSP_LEVELS_RMS;
+                else if (part == "loudness") what |= SDSP_LEVELS_LOUDNESS;
+                else if (part == "silence") what |= SDSP_LEVELS_SILENCE_MAP;
+                else list = false;
+                if (p1 == w.size()) break;
+                p0 = p1 + 1;
+            }
+            if (list) {
+                lvreq.what = what;
+                i++;
+            }
         } else if (s == "--help" || s == "-h") {
             std::fprintf(stderr,
                          "Usage: analyze_batch [--jobs N] [--devices MASK] [--json] [--gpu-decode] [--overview N | "
-                         "--overview-frames K] [--key-timeline SEC[:OVERLAP[:MINCONF]]] <file1> <file2> ...\n\n"
+                         "--overview-frames K] [--key-timeline SEC[:OVERLAP[:MINCONF]]] [--levels [LIST]] <file1> <file2> ...\n\n"
                          "--jobs N        Decode workers (default: CPU-1)\n"
                          "--devices MASK  GPU bitmask (default: all visible GPUs)\n"
                          "--json          Emit one JSON object per line (JSONL)\n"
@@ -271,7 +332,9 @@ int main(int argc, char** argv) {
                          "--overview-frames K  ... or in one column per K analysis frames\n"
                          "--key-timeline SEC[:OVERLAP[:MINCONF]]  With --json: add each track's key per SEC-second segment,\n"
                          "                primary key and key changes (\"key_timeline\"); OVERLAP defaults to SEC/4, MINCONF\n"
-                         "                to -1 (every change; 0.2 is the reference's threshold)\n");
+                         "                to -1 (every change; 0.2 is the reference's threshold)\n"
+                         "--levels [LIST] With --json: add each track's loudness metadata and silence regions (\"levels\");\n"
+                         "                LIST out of peak,rms,loudness,silence (default: all four)\n");
             return 0;
         } else {
             paths.push_back(s);
@@ -283,6 +346,7 @@ int main(int argc, char** argv) {
     }
     if (overview && !json) std::fprintf(stderr, "Note: --overview / --overview-frames add to the --json lines only\n");
     if (timeline && !json) std::fprintf(stderr, "Note: --key-timeline adds to the --json lines only\n");
+    if (levels && !json) std::fprintf(stderr, "Note: --levels adds to the --json lines only\n");
     if (paths.empty()) {
         std::fprintf(stderr, "ERROR: Provide at least one audio file path. Use --help for usage.\n");
         return 2;
@@ -337,9 +401,10 @@ int main(int argc, char** argv) {
     sdsp_config cfg;
     sdsp_config_default(&cfg);
     auto take = [](Item& it, const sdsp_result& r, const sdsp_overview* ov = nullptr,
-                   const sdsp_key_timeline* kt = nullptr) {
+                   const sdsp_key_timeline* kt = nullptr, const sdsp_levels* lv = nullptr) {
         if (ov) it.overview = overview_json(*ov);
         if (kt) it.timeline = key_timeline_json(*kt);
+        if (lv) it.levels = levels_json(*lv);
         if (r.status != 0) {
             it.error = std::string("analysis failed: ") + r.error_message;
             return;
@@ -356,6 +421,34 @@ int main(int argc, char** argv) {
         it.tr[1] = r.tempogram_multi_res_used;
         it.tr[2] = r.tempogram_percussive_triggered;
         it.tr[3] = r.tempogram_percussive_used;
+    };
+
+    // the optional requests of one analysis call over n tracks, and their outputs
+    struct Requests {
+        std::vector<sdsp_overview> ovs;
+        std::vector<sdsp_key_timeline> kts;
+        std::vector<sdsp_levels> lvs;
+        sdsp_request_set set{};
+    };
+    auto requests = [&](size_t n) {
+        Requests q;
+        q.ovs.resize(overview ? n : 0);  // (zeroed; without a request: the plain entry)
+        q.kts.resize(timeline ? n : 0);
+        q.lvs.resize(levels ? n : 0);
+        return q;
+    };
+    auto request_set = [&](Requests& q) {
+        q.set.struct_size = (uint32_t)sizeof(q.set);
+        if (overview) q.set.ov_req = &ovreq, q.set.overviews = q.ovs.data();
+        if (timeline) q.set.kt_req = &ktreq, q.set.timelines = q.kts.data();
+        if (levels) q.set.lv_req = &lvreq, q.set.levels = q.lvs.data();
+        return &q.set;
+    };
+    auto take_requests = [&](Item& it, const sdsp_result& r, Requests& q, size_t j) {
+        take(it, r, overview ? &q.ovs[j] : nullptr, timeline ? &q.kts[j] : nullptr, levels ? &q.lvs[j] : nullptr);
+        if (overview) sdsp_overview_free(&q.ovs[j]);
+        if (timeline) sdsp_key_timeline_free(&q.kts[j]);
+        if (levels) sdsp_levels_free(&q.lvs[j]);
     };
 
     if (gpu_decode) {
@@ -409,17 +502,12 @@ int main(int argc, char** argv) {
                     l2.push_back(lens[k]);
                 }
                 std::vector<sdsp_result> outs(okk.size());
-                std::vector<sdsp_overview> ovs(overview ? okk.size() : 0);  // (zeroed; without a request: the plain entry)
-                std::vector<sdsp_key_timeline> kts(timeline ? okk.size() : 0);
-                (void)sdsp_analyze_batch_device_requests(d_samples, o2.data(), l2.data(), okk.size(), kv.first, &cfg, dev,
-                                                         nullptr, SDSP_STAGES_FULL, outs.data(), overview ? &ovreq : nullptr,
-                                                         overview ? ovs.data() : nullptr, timeline ? &ktreq : nullptr,
-                                                         timeline ? kts.data() : nullptr);
+                Requests q = requests(okk.size());
+                (void)sdsp_analyze_batch_device_with(d_samples, o2.data(), l2.data(), okk.size(), kv.first, &cfg, dev, nullptr,
+                                                     SDSP_STAGES_FULL, outs.data(), request_set(q));
                 for (size_t j = 0; j < okk.size(); j++) {
-                    take(items[ch.idx[okk[j]]], outs[j], overview ? &ovs[j] : nullptr, timeline ? &kts[j] : nullptr);
+                    take_requests(items[ch.idx[okk[j]]], outs[j], q, j);
                     sdsp_result_free(&outs[j]);
-                    if (overview) sdsp_overview_free(&ovs[j]);
-                    if (timeline) sdsp_key_timeline_free(&kts[j]);
                 }
             }
             if (d_samples) sdsp_device_free(dev, d_samples);
@@ -443,7 +531,7 @@ int main(int argc, char** argv) {
             ptrs.push_back(items[i].samples.data());
             lens.push_back(items[i].samples.size());
         }
-        if (overview || timeline) {
+        if (overview || timeline || levels) {
             // the requests entry reads device-resident tracks: upload each group to the first device of
             // the mask in parts of at most 512 tracks or 2 Gi samples
             int dev = 0;
@@ -455,8 +543,7 @@ int main(int argc, char** argv) {
                 const size_t n = k1 - k0;
                 std::vector<uint64_t> off(n);
                 std::vector<sdsp_result> outs(n);
-                std::vector<sdsp_overview> ovs(overview ? n : 0);
-                std::vector<sdsp_key_timeline> kts(timeline ? n : 0);
+                Requests q = requests(n);
                 void* d = nullptr;
                 bool up = sdsp_device_malloc(dev, std::max<uint64_t>(tot, 1) * sizeof(float), &d) == 0;
                 uint64_t o = 0;
@@ -466,16 +553,12 @@ int main(int argc, char** argv) {
                     o += lens[k];
                 }
                 if (up)
-                    (void)sdsp_analyze_batch_device_requests((const float*)d, off.data(), lens.data() + k0, n, kv.first, &cfg, dev,
-                                                             nullptr, SDSP_STAGES_FULL, outs.data(), overview ? &ovreq : nullptr,
-                                                             overview ? ovs.data() : nullptr, timeline ? &ktreq : nullptr,
-                                                             timeline ? kts.data() : nullptr);
+                    (void)sdsp_analyze_batch_device_with((const float*)d, off.data(), lens.data() + k0, n, kv.first, &cfg, dev,
+                                                         nullptr, SDSP_STAGES_FULL, outs.data(), request_set(q));
                 for (size_t k = k0; k < k1; k++) {
                     if (up) {
-                        take(items[idx[k]], outs[k - k0], overview ? &ovs[k - k0] : nullptr, timeline ? &kts[k - k0] : nullptr);
+                        take_requests(items[idx[k]], outs[k - k0], q, k - k0);
                         sdsp_result_free(&outs[k - k0]);
-                        if (overview) sdsp_overview_free(&ovs[k - k0]);
-                        if (timeline) sdsp_key_timeline_free(&kts[k - k0]);
                     } else {
                         items[idx[k]].error = "analysis failed: Processing error: device upload failed";
                     }
@@ -515,6 +598,10 @@ int main(int argc, char** argv) {
             if (!o.timeline.empty()) {
                 std::fputs(",\"key_timeline\":", stdout);
                 std::fputs(o.timeline.c_str(), stdout);
+            }
+            if (!o.levels.empty()) {
+                std::fputs(",\"levels\":", stdout);
+                std::fputs(o.levels.c_str(), stdout);
             }
             std::fputs("}\n", stdout);
         } else {

@@ -299,6 +299,27 @@ struct LoudnessParams {
 void launch_loudness_gain(const float* x, const uint64_t* in_off, const uint64_t* n_raw, const uint64_t* chunk_pfx,
                           int T, uint64_t n_chunks, unsigned int* chunk_bits, unsigned int* peak_bits,
                           const LoudnessParams& P, float* gain, int* status, hipStream_t st);
+// ---- k_levels: the levels request (levels_core.hpp has the arithmetic and LvParams) ----
+struct LvParams;
+constexpr int LV_CHAINS = 4;  // sum x^2; gated K-weighted block sums; sum (x g_peak)^2; sum (x g_lufs)^2
+struct LvFoldArgs {
+    const float* x;
+    const uint64_t* in_off;
+    const uint64_t* n_raw;
+    int T;
+    uint32_t chains;     // bit c: chain c runs in this launch
+    const float* gains;  // chain c >= 2 multiplies track t's samples by gains[c * T + t]
+    float* sums;         // chain c of track t -> sums[c * T + t] (chain 1: the gated sum)
+    int* gated_n;        // chain 1: gated blocks
+};
+void launch_levels_fold(const LvFoldArgs& A, const LvParams& P, hipStream_t st);
+void launch_levels_gain(const unsigned int* peak_bits, const float* sums, const int* gated_n, int T, const LvParams& P,
+                        float* gains, hipStream_t st);
+// the silence map over the rows launch_trim reads; track t's kept regions as (start, end) sample
+// pairs at dense[2 * pfx[t] ...], pfx[T] in all; regions / count: scratch of cap_pfx[T] pairs / T
+void launch_silence_map(const float* rms, const uint64_t* frame_pfx, const uint64_t* base_pfx, int stride, int T,
+                        const uint64_t* n_raw, int hop, float thr, uint64_t min_frames, const uint64_t* cap_pfx,
+                        uint64_t* regions, int* count, uint64_t* pfx, uint64_t* dense, hipStream_t st);
 void launch_frame_rms(const float* x, const uint64_t* src_off, const float* gain, const uint64_t* n_len,
                       const uint64_t* frame_pfx, int T, uint64_t total, int fs, int hop, float* rms, hipStream_t st, bool per_frame_kernel = false);
 // base_pfx / stride: trim frame f of track t at rms[base_pfx[t] + f * stride] (default: frame_pfx, 1)

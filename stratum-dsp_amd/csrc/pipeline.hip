@@ -64,6 +64,7 @@ void Pipeline::run(const float* d_samples, const std::vector<uint64_t>& in_off, 
     res.assign(T, TrackRes{});
     if (ov_out_) ov_out_->assign(T, TrackOv{});
     if (kt_out_) kt_out_->assign(T, TrackKt{});
+    if (lv_out_) lv_out_->assign(T, TrackLv{});
     const std::string why = check_supported(cfg_, sr_);
     for (size_t i = 0; i < T; i++) {
         if (n_raw[i] == 0) {
@@ -104,7 +105,10 @@ void Pipeline::run(const float* d_samples, const std::vector<uint64_t>& in_off, 
     times_ = sdsp_stage_times{};
     last_sub_ = false;
     auto t0 = std::chrono::steady_clock::now();
-    if (cfg_.enable_normalization && cfg_.normalization != SDSP_NORM_PEAK && why.empty())
+    // with a levels request its folds also give the configured RMS / LUFS gain (one fold, not two)
+    if (lv_out_ && why.empty())
+        levels_prepass(d_samples, in_off, n_raw, res);
+    else if (cfg_.enable_normalization && cfg_.normalization != SDSP_NORM_PEAK && why.empty())
         loudness_prepass(d_samples, in_off, n_raw, res);
     // equal shares: the fewest sub-batches that fit the budget, each near total / count (a
     // short last sub-batch runs at a fraction of the chip)
@@ -120,6 +124,10 @@ void Pipeline::run(const float* d_samples, const std::vector<uint64_t>& in_off, 
         if (cfg_.enable_key_hpss_harmonic && !bpm_only_) need[i] += n / khop * 1024.0 * 4.0;
         if (kt_out_ && !bpm_only_) need[i] += (n / khop / kt_H_ + 1.0) * 2.0 * sizeof(KtSeg);  // both parities' segments
         if (cfg_.enable_tempogram_multi_resolution && hop != 512) need[i] += n / 512 * s2_ * 4.0 * 1.3;
+        if (lv_out_) {  // the folds' words; the map's frame RMS (not there with trimming off), scratch and dense regions
+            const double F = n / (fs_ / 2) + 1.0;
+            need[i] += 64.0 + (map_on() ? F * 4.0 + (F / (double)(lv_min_frames(sr_, (uint64_t)fs_) + 1) + 2.0) * 2.0 * 16.0 : 0.0);
+        }
         total_need += need[i];
     }
     const double parts = std::max(1.0, std::ceil(total_need / budget));
@@ -142,6 +150,7 @@ void Pipeline::run(const float* d_samples, const std::vector<uint64_t>& in_off, 
     // the last sub-batch's near tracks: rerun in place when its band-path buffers are intact,
     // otherwise by run_locked
     rerun_tail(finish_key(res, true), res);
+    levels_join();  // the one join of the levels folds (nothing without a request)
     times_.total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     times_.key_reruns = reruns_;  // in-flight reruns (rerun_near), their time inside total_ms
     times_.rerun_ms = rerun_ms_;
@@ -284,7 +293,7 @@ Front Pipeline::front(const float* d_samples, const std::vector<uint64_t>& in_of
         nr[(size_t)t] = n_raw[(size_t)idx[(size_t)t]];
         cpfx[(size_t)t + 1] = cpfx[(size_t)t] + (nr[(size_t)t] + PK_CH - 1) / PK_CH;
         const uint64_t fs = nr[(size_t)t] >= (uint64_t)FS ? (nr[(size_t)t] - FS) / (FS / 2) + 1 : 1;
-        spfx[(size_t)t + 1] = spfx[(size_t)t] + (cfg_.enable_silence_trimming ? fs : 0);
+        spfx[(size_t)t + 1] = spfx[(size_t)t] + (cfg_.enable_silence_trimming || map_on() ? fs : 0);
     }
     uint64_t* d_off = c_.up("A.off", f.off);
     uint64_t* d_nr = c_.up("A.nr", nr);
@@ -334,10 +343,37 @@ Front Pipeline::front(const float* d_samples, const std::vector<uint64_t>& in_of
     uint64_t* d_te = c_.dev<uint64_t>("A.te", (size_t)T);
     launch_trim(f.d_srms, d_spfx, T, d_nr, FS / 2, thr, min_frames, cfg_.enable_silence_trimming, d_ts, d_te, st,
                 rms_shared ? d_rpfx : nullptr, rms_shared ? (FS / 2) / HOP : 1);
+    // the silence map (levels request) from the same rows, trimming on or off
+    uint64_t *d_mpfx = nullptr, *d_mdense = nullptr;
+    if (map_on()) {
+        std::vector<uint64_t> mcap((size_t)T + 1, 0);
+        for (int t = 0; t < T; t++)
+            mcap[(size_t)t + 1] = mcap[(size_t)t] + lv_map_capacity(spfx[(size_t)t + 1] - spfx[(size_t)t], min_frames);
+        d_mpfx = c_.dev<uint64_t>("A.mpfx", (size_t)T + 1);
+        d_mdense = c_.dev<uint64_t>("A.mdense", 2 * mcap[(size_t)T]);
+        launch_silence_map(f.d_srms, d_spfx, rms_shared ? d_rpfx : nullptr, rms_shared ? (FS / 2) / HOP : 1, T, d_nr,
+                           FS / 2, thr, min_frames, c_.up("A.mcap", mcap), c_.dev<uint64_t>("A.mreg", 2 * mcap[(size_t)T]),
+                           c_.dev<int>("A.mcnt", (size_t)T), d_mpfx, d_mdense, st);
+    }
     SDSP_HIP_CHECK(hipGetLastError());
     f.gain_h = c_.down(d_gain, (size_t)T);
     f.ts = c_.down(d_ts, (size_t)T);
     f.te = c_.down(d_te, (size_t)T);
+    if (lv_out_) {
+        std::vector<uint64_t> mpfx((size_t)T + 1, 0), dense;
+        if (map_on()) {
+            mpfx = c_.down(d_mpfx, (size_t)T + 1);
+            dense = c_.down(d_mdense, 2 * (size_t)mpfx[(size_t)T]);
+        }
+        for (int t = 0; t < T; t++) {
+            TrackLv& l = (*lv_out_)[(size_t)idx[(size_t)t]];
+            if (nstat[(size_t)t] != 0) continue;  // the configured normalisation failed: gain 1, no map
+            l.applied_gain = f.gain_h[(size_t)t];
+            l.ts = f.ts[(size_t)t];
+            l.te = f.te[(size_t)t];
+            l.regions.assign(dense.begin() + (long)(2 * mpfx[(size_t)t]), dense.begin() + (long)(2 * mpfx[(size_t)t + 1]));
+        }
+    }
     for (int t = 0; t < T; t++) {
         TrackRes& r = res[(size_t)idx[(size_t)t]];
         const uint64_t n = f.te[(size_t)t] - f.ts[(size_t)t];

@@ -22,6 +22,7 @@
 #include "../../include/sdsp_fft_spec.h"
 #include "../../include/stratum_hip_debug.h"
 #include "kernels.hpp"
+#include "levels_core.hpp"
 #include "sdsp_runtime.hpp"
 
 namespace sdsp {
@@ -455,6 +456,28 @@ struct TrackOv {
     size_t at = 0;
 };
 
+// One track's levels on the host (sdsp_levels without the config-wide fields).  `on`: the track
+// gets levels (n > 0, a sample rate, a supported configuration), whatever its analysis status.
+struct TrackLv {
+    bool on = false;
+    sdsp_loudness method[3]{};
+    float applied_gain = 1.0f;
+    uint64_t n = 0, ts = 0, te = 0;
+    std::vector<uint64_t> regions;  // (start, end) sample pairs, ascending
+};
+// The levels folds as queued before the sub-batches (Pipeline::levels_prepass) and read at the
+// call's end (Pipeline::levels_join); nothing is queued without a request.
+struct LevelsPending {
+    bool on = false;
+    std::vector<size_t> at;  // result slot of each folded track
+    uint32_t chains = 0;
+    LvParams P{};
+    unsigned int* d_peak = nullptr;
+    float* d_sums = nullptr;
+    int* d_gn = nullptr;
+    std::unique_ptr<Timers> tm;  // events 0-1: the first launch (peak and folds), 1-2: the second
+};
+
 }  // namespace detail
 using namespace detail;
 
@@ -499,6 +522,13 @@ class Pipeline {
         kt_H_ = H;
         kt_out_ = out;
     }
+    // Before run(): also compute every track's levels (include/stratum_hip.h, sdsp_levels; `what`
+    // checked by levels_request_error) into *out, one entry per track of the call.  A pipeline
+    // without a request queues nothing for it; nested pipelines get none.
+    void set_levels(uint32_t what, std::vector<TrackLv>* out) {
+        lv_what_ = what;
+        lv_out_ = out;
+    }
 
    private:
     Ctx c_;
@@ -537,6 +567,10 @@ class Pipeline {
     std::vector<TrackOv>* ov_out_ = nullptr;  // the call's overviews (set_overview), else nullptr
     uint32_t kt_L_ = 0, kt_H_ = 0;
     std::vector<TrackKt>* kt_out_ = nullptr;  // the call's key timelines (set_key_timeline), else nullptr
+    uint32_t lv_what_ = 0;
+    std::vector<TrackLv>* lv_out_ = nullptr;  // the call's levels (set_levels), else nullptr
+    LevelsPending lv_pending_;
+    bool map_on() const { return lv_out_ && (lv_what_ & SDSP_LEVELS_SILENCE_MAP); }
 
     // force_legacy_bpm skips the tempogram estimate (src/lib.rs:337): no escalation, no
     // candidates, the flags stay None; the hop-512 pass still feeds the onset detectors
@@ -550,6 +584,9 @@ class Pipeline {
     // pipeline.hip
     void loudness_prepass(const float* d_samples, const std::vector<uint64_t>& in_off,
                           const std::vector<uint64_t>& n_raw, std::vector<TrackRes>& res);
+    void levels_prepass(const float* d_samples, const std::vector<uint64_t>& in_off, const std::vector<uint64_t>& n_raw,
+                        std::vector<TrackRes>& res);
+    void levels_join();
     void sub_batch(const float* d_samples, const std::vector<uint64_t>& in_off, const std::vector<uint64_t>& n_raw,
                    const std::vector<int>& idx, std::vector<TrackRes>& res);
     Front front(const float* d_samples, const std::vector<uint64_t>& in_off, const std::vector<uint64_t>& n_raw,

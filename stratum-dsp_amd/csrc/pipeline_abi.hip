@@ -178,6 +178,37 @@ void fill_key_timeline(const TrackKt& t, int status, const sdsp_config& cfg, uin
     }
 }
 
+// A checked levels request and where the levels go.
+struct LvCall {
+    uint32_t what = 0;
+    sdsp_levels* out = nullptr;
+};
+// One track's levels: every field for a track that gets levels (TrackLv::on: status SDSP_OK whatever
+// the analysis status), else the analysis status and zeroed fields.
+void fill_levels(const TrackLv& t, int status, const sdsp_config& cfg, uint32_t sr, sdsp_levels* o) {
+    std::memset(o, 0, sizeof(*o));
+    o->status = t.on ? (int32_t)SDSP_OK : status;
+    if (!t.on) return;
+    for (int m = 0; m < 3; m++) o->method[m] = t.method[m];
+    o->applied_gain = t.applied_gain;
+    o->n_samples = t.n;
+    o->trim_start = t.ts;
+    o->trim_end = t.te;
+    o->frame_size = (uint32_t)cfg.frame_size;
+    o->threshold_db = cfg.min_amplitude_db;
+    const size_t R = t.regions.size() / 2;
+    if (R == 0) return;
+    o->regions = (sdsp_silence_region*)std::malloc(R * sizeof(sdsp_silence_region));
+    for (size_t r = 0; r < R; r++) {
+        sdsp_silence_region& e = o->regions[r];
+        std::memset(&e, 0, sizeof e);
+        e.start_sample = t.regions[2 * r];
+        e.end_sample = t.regions[2 * r + 1];
+        e.duration_seconds = (float)(e.end_sample - e.start_sample) / (float)sr;
+    }
+    o->n_regions = R;
+}
+
 // One device-resident batch on `device`.  The engine's main stream first waits for `user_stream`
 // (everything queued on it so far) and for `wait_ev` (a copy's completion), whichever are given.
 // The batch on a context whose mutex the caller holds (run_device, and sdsp_analyze_audio's
@@ -185,7 +216,7 @@ void fill_key_timeline(const TrackKt& t, int status, const sdsp_config& cfg, uin
 int32_t run_locked(DeviceCtx& d, const float* d_samples, const uint64_t* offsets, const uint64_t* lens, uint64_t n,
                    uint32_t sr, const sdsp_config* cfg, void* user_stream, sdsp_result* outs, int stages,
                    hipEvent_t wait_ev, const sdsp_overview_request* req = nullptr, sdsp_overview* ovs = nullptr,
-                   const KtCall* ktc = nullptr) {
+                   const KtCall* ktc = nullptr, const LvCall* lvc = nullptr) {
     if (stages != SDSP_STAGES_FULL && stages != SDSP_STAGES_BPM_ONLY) throw HipError("unknown stage mask");
     if (user_stream) {
         hipEvent_t ev;
@@ -204,6 +235,9 @@ int32_t run_locked(DeviceCtx& d, const float* d_samples, const uint64_t* offsets
     if (req) p.set_overview(*req, &ov);
     std::vector<TrackKt> ktl;
     if (ktc) p.set_key_timeline(ktc->L, ktc->H, &ktl);
+    std::vector<TrackLv> lvl;
+    d.last_lv = sdsp_debug_levels_times{};
+    if (lvc) p.set_levels(lvc->what, &lvl);
     try {
         p.run(d_samples, off, ln, res);
         // Certified block energies: a track whose key vote had an energy-dependent
@@ -254,6 +288,8 @@ int32_t run_locked(DeviceCtx& d, const float* d_samples, const uint64_t* offsets
     if (ktc)
         for (uint64_t i = 0; i < n; i++)
             fill_key_timeline(ktl[(size_t)i], res[(size_t)i].status, *cfg, sr, *ktc, &ktc->out[i]);
+    if (lvc)
+        for (uint64_t i = 0; i < n; i++) fill_levels(lvl[(size_t)i], res[(size_t)i].status, *cfg, sr, &lvc->out[i]);
     return SDSP_OK;
 }
 
@@ -261,11 +297,11 @@ int32_t run_device(int device, const float* d_samples, const uint64_t* offsets, 
                    uint32_t sr, const sdsp_config* cfg, void* user_stream, sdsp_result* outs,
                    int stages = SDSP_STAGES_FULL, hipEvent_t wait_ev = nullptr,
                    const sdsp_overview_request* req = nullptr, sdsp_overview* ovs = nullptr,
-                   const KtCall* ktc = nullptr) {
+                   const KtCall* ktc = nullptr, const LvCall* lvc = nullptr) {
     DeviceCtx& d = device_ctx(device);
     std::lock_guard<std::mutex> lk(d.mu);
     SDSP_HIP_CHECK(hipSetDevice(device));
-    return run_locked(d, d_samples, offsets, lens, n, sr, cfg, user_stream, outs, stages, wait_ev, req, ovs, ktc);
+    return run_locked(d, d_samples, offsets, lens, n, sr, cfg, user_stream, outs, stages, wait_ev, req, ovs, ktc, lvc);
 }
 
 }  // namespace
@@ -428,7 +464,31 @@ int32_t sdsp_analyze_batch_device_requests(const float* d_samples, const uint64_
                                            int32_t device, void* stream, int32_t stages, sdsp_result* outs,
                                            const sdsp_overview_request* ov_req, sdsp_overview* overviews,
                                            const sdsp_key_timeline_request* kt_req, sdsp_key_timeline* timelines) {
-    if (!ov_req && !kt_req)
+    sdsp_request_set set{};
+    set.struct_size = (uint32_t)sizeof(set);
+    set.ov_req = ov_req;
+    set.overviews = overviews;
+    set.kt_req = kt_req;
+    set.timelines = timelines;
+    return sdsp_analyze_batch_device_with(d_samples, offsets, lens, n_tracks, sample_rate, cfg, device, stream, stages, outs,
+                                          &set);
+}
+
+// The device batch with any of the optional requests (include/stratum_hip.h): the overview
+// envelopes, the key timelines and the levels from one analysis.  Every request is checked before
+// any device is touched.
+int32_t sdsp_analyze_batch_device_with(const float* d_samples, const uint64_t* offsets, const uint64_t* lens,
+                                       uint64_t n_tracks, uint32_t sample_rate, const sdsp_config* cfg, int32_t device,
+                                       void* stream, int32_t stages, sdsp_result* outs, const sdsp_request_set* caller_set) {
+    sdsp_request_set set;
+    const char* set_err = request_set_read(caller_set, &set);
+    const sdsp_overview_request* ov_req = set.ov_req;
+    sdsp_overview* overviews = set.overviews;
+    const sdsp_key_timeline_request* kt_req = set.kt_req;
+    sdsp_key_timeline* timelines = set.timelines;
+    const sdsp_levels_request* lv_req = set.lv_req;
+    sdsp_levels* levels = set.levels;
+    if (!set_err && !ov_req && !kt_req && !lv_req)
         return sdsp_analyze_batch_device_ex(d_samples, offsets, lens, n_tracks, sample_rate, cfg, device, stream, stages,
                                             outs);
     auto fail_all = [&](int32_t status, const char* text) {
@@ -444,10 +504,22 @@ int32_t sdsp_analyze_batch_device_requests(const float* d_samples, const uint64_
                 std::memset(&timelines[i], 0, sizeof(timelines[i]));
                 timelines[i].status = status;
             }
+            if (lv_req && levels) {
+                std::memset(&levels[i], 0, sizeof(levels[i]));
+                levels[i].status = status;
+            }
         }
         return status;
     };
+    if (set_err) return fail_all(SDSP_ERR_INVALID_INPUT, set_err);
     if (!cfg) return fail_all(SDSP_ERR_INVALID_INPUT, "Invalid input: no configuration");
+    LvCall lc;
+    if (lv_req) {
+        if (const char* why = levels_request_error(lv_req->what)) return fail_all(SDSP_ERR_INVALID_INPUT, why);
+        if (!levels) return fail_all(SDSP_ERR_INVALID_INPUT, "Invalid input: levels request without a levels array");
+        lc.what = lv_req->what;
+        lc.out = levels;
+    }
     if (ov_req) {
         if (const char* why = overview_request_error(ov_req->columns, ov_req->frames_per_column, ov_req->low_max_hz,
                                                      ov_req->mid_max_hz))
@@ -475,12 +547,31 @@ int32_t sdsp_analyze_batch_device_requests(const float* d_samples, const uint64_
         return fail_all(SDSP_ERR_PROCESSING, "Processing error: no HIP device");
     try {
         return run_device(device, d_samples, offsets, lens, n_tracks, sample_rate, cfg, stream, outs, stages, nullptr,
-                          ov_req, overviews, kt_req ? &kc : nullptr);
+                          ov_req, overviews, kt_req ? &kc : nullptr, lv_req ? &lc : nullptr);
     } catch (const std::exception& e) {
-        std::fprintf(stderr, "sdsp_analyze_batch_device_requests: %s\n", e.what());
+        std::fprintf(stderr, "sdsp_analyze_batch_device_with: %s\n", e.what());
         char text[256];
         std::snprintf(text, sizeof text, "Processing error: %s", e.what());
         return fail_all(SDSP_ERR_PROCESSING, text);
+    }
+}
+
+void sdsp_levels_free(sdsp_levels* l) {
+    if (!l) return;
+    std::free(l->regions);
+    l->regions = nullptr;
+    l->n_regions = 0;
+}
+
+int32_t sdsp_debug_last_levels_times(int32_t device, sdsp_debug_levels_times* out) {
+    try {
+        if (!out) return SDSP_ERR_INVALID_INPUT;
+        DeviceCtx& d = device_ctx(device);
+        std::lock_guard<std::mutex> lk(d.mu);
+        *out = d.last_lv;
+        return SDSP_OK;
+    } catch (const std::exception&) {
+        return SDSP_ERR_PROCESSING;
     }
 }
 

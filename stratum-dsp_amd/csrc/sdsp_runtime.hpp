@@ -89,6 +89,7 @@ struct DeviceCtx {
     std::vector<uint8_t> last_near;  // per track of the last call: its key vote was near a decision (rerun)
     uint64_t last_tail_reruns = 0;   // tracks the last call reran in place (Pipeline::rerun_tail)
     sdsp_debug_overview_times last_ov{};  // the last call with an overview request (Pipeline::overview)
+    sdsp_debug_levels_times last_lv{};    // the last call with a levels request (Pipeline::levels_join)
     DevBuf& buf(const std::string& name) {
         auto& b = bufs[name];
         if (!b) {

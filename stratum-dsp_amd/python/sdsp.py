@@ -17,7 +17,8 @@ import numpy as np
 from sdsp_abi import (ERROR_NAMES, FLAG_NAMES, SdspAudioDecodeStats, SdspConfidence, SdspConfig, SdspDebugOverviewTimes,
                       SdspDecodeStats, SdspFlacDecodeStats, SdspOverview, SdspOverviewRequest, SdspResult,
                       SdspStageTimes, OVERVIEW_ARRAYS, result_to_dict, SdspKeyChange, SdspKeySegment, SdspKeyTimeline,
-                      SdspKeyTimelineRequest)
+                      SdspKeyTimelineRequest, SdspDebugLevelsTimes, SdspLevels, SdspLevelsRequest, SdspLoudness,
+                      SdspRequestSet, SdspSilenceRegion, LEVELS_BITS)
 
 PKG = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LIB_PATH = os.environ.get("SDSP_LIB_PATH") or os.path.join(PKG, "lib", "libstratum_hip.so")  # override: layout/ablation builds
@@ -83,6 +84,14 @@ def _load(path):
                                                          C.POINTER(SdspOverview), C.POINTER(SdspKeyTimelineRequest),
                                                          C.POINTER(SdspKeyTimeline)]
         L.sdsp_analyze_batch_device_requests.restype = C.c_int32
+        L.sdsp_analyze_batch_device_with.argtypes = [C.c_void_p, u64p, u64p, C.c_uint64, C.c_uint32,
+                                                     C.POINTER(SdspConfig), C.c_int32, C.c_void_p, C.c_int32,
+                                                     C.POINTER(SdspResult), C.POINTER(SdspRequestSet)]
+        L.sdsp_analyze_batch_device_with.restype = C.c_int32
+        L.sdsp_levels_free.argtypes = [C.POINTER(SdspLevels)]
+        L.sdsp_levels_free.restype = None
+        L.sdsp_debug_last_levels_times.argtypes = [C.c_int32, C.POINTER(SdspDebugLevelsTimes)]
+        L.sdsp_debug_last_levels_times.restype = C.c_int32
         L.sdsp_key_timeline_free.argtypes = [C.POINTER(SdspKeyTimeline)]
         L.sdsp_key_timeline_free.restype = None
         L.sdsp_debug_key_timeline.argtypes = [C.POINTER(C.c_float), u64p, C.c_uint64, C.c_uint32, C.POINTER(SdspConfig),
@@ -675,6 +684,96 @@ def analyze_batch_device_requests(d_ptr, offsets, lens, sample_rate=44100, confi
             timelines.append(key_timeline_to_dict(kts[i]))
             lib().sdsp_key_timeline_free(C.byref(kts[i]))
     return ResultBatch(outs, n), overviews, timelines
+
+
+LOUDNESS_FIELDS = ("measured_lufs", "peak_db", "rms_db", "gain_db", "gain")
+LEVELS_METHODS = ("peak", "rms", "loudness")  # index = enum sdsp_normalization
+
+
+def levels_request(what=("peak", "rms", "loudness", "silence")):
+    """An sdsp_levels_request: `what` is a mask of sdsp_levels_what bits, or names out of peak, rms,
+    loudness, silence (the default asks for all four)."""
+    if not isinstance(what, int):
+        mask = 0
+        for name in what:
+            mask |= LEVELS_BITS[name]
+        what = mask
+    return SdspLevelsRequest(what)
+
+
+def levels_to_dict(l):
+    """One sdsp_levels: its scalar fields, `methods` (peak / rms / loudness -> dict of status,
+    measured, has_lufs and the np.float32 fields of LOUDNESS_FIELDS) and `regions`, a list of
+    (start_sample, end_sample, np.float32 duration_seconds)."""
+    d = {k: int(getattr(l, k)) for k in ("n_samples", "trim_start", "trim_end", "frame_size", "n_regions", "status")}
+    d["applied_gain"] = np.float32(l.applied_gain)
+    d["threshold_db"] = np.float32(l.threshold_db)
+    d["methods"] = {}
+    for m, name in enumerate(LEVELS_METHODS):
+        e = l.method[m]
+        md = {"status": int(e.status), "measured": int(e.measured), "has_lufs": int(e.has_lufs)}
+        for k in LOUDNESS_FIELDS:
+            md[k] = np.float32(getattr(e, k))
+        d["methods"][name] = md
+    reg = _records(l.regions, d["n_regions"], SdspSilenceRegion)
+    d["regions"] = [(int(r["start_sample"]), int(r["end_sample"]), np.float32(r["duration_seconds"])) for r in reg]
+    return d
+
+
+def analyze_batch_device_with(d_ptr, offsets, lens, sample_rate=44100, config=None, device=0, stream=None,
+                              stages=STAGES_FULL, overview=None, key_timeline=None, levels=None, request_set=True):
+    """sdsp_analyze_batch_device_with: analyze_batch_device(raw=True) with any of the optional
+    requests: an SdspOverviewRequest, an SdspKeyTimelineRequest, an SdspLevelsRequest
+    (levels_request()); None leaves a request out.  request_set=False passes set == NULL.  Returns
+    (ResultBatch, overviews, timelines, levels): levels[i] a levels_to_dict(); each list [] without
+    its request.  Raises AnalysisError when the call as a whole fails (a refused request)."""
+    offs = np.ascontiguousarray(offsets, dtype=np.uint64)
+    ln = np.ascontiguousarray(lens, dtype=np.uint64)
+    n = ln.size
+    outs = (SdspResult * n)()
+    ovs = (SdspOverview * max(n, 1))() if overview is not None else None
+    kts = (SdspKeyTimeline * max(n, 1))() if key_timeline is not None else None
+    lvs = (SdspLevels * max(n, 1))() if levels is not None else None
+    cfg = config if config is not None else default_config()
+    _schedule_from_env()
+    rs = SdspRequestSet()
+    rs.struct_size = C.sizeof(SdspRequestSet)
+    if overview is not None:
+        rs.ov_req = C.pointer(overview)
+        rs.overviews = ovs
+    if key_timeline is not None:
+        rs.kt_req = C.pointer(key_timeline)
+        rs.timelines = kts
+    if levels is not None:
+        rs.lv_req = C.pointer(levels)
+        rs.levels = lvs
+    u64p = C.POINTER(C.c_uint64)
+    st = lib().sdsp_analyze_batch_device_with(C.c_void_p(d_ptr), offs.ctypes.data_as(u64p), ln.ctypes.data_as(u64p), n,
+                                              sample_rate, C.byref(cfg), device, C.c_void_p(stream or 0), stages, outs,
+                                              C.byref(rs) if request_set else None)
+    if st != 0:
+        raise AnalysisError(st, _batch_error(outs, n, "device batch failed"))
+    overviews, timelines, lv = [], [], []
+    for i in range(n if request_set else 0):
+        if ovs is not None:
+            overviews.append(overview_to_dict(ovs[i]))
+            lib().sdsp_overview_free(C.byref(ovs[i]))
+        if kts is not None:
+            timelines.append(key_timeline_to_dict(kts[i]))
+            lib().sdsp_key_timeline_free(C.byref(kts[i]))
+        if lvs is not None:
+            lv.append(levels_to_dict(lvs[i]))
+            lib().sdsp_levels_free(C.byref(lvs[i]))
+    return ResultBatch(outs, n), overviews, timelines, lv
+
+
+def levels_times(device=0):
+    """sdsp_debug_last_levels_times: the levels folds' event times of the last call with a levels
+    request on `device`."""
+    t = SdspDebugLevelsTimes()
+    if lib().sdsp_debug_last_levels_times(device, C.byref(t)) != 0:
+        raise RuntimeError("sdsp_debug_last_levels_times failed")
+    return {k: getattr(t, k) for k, _ in SdspDebugLevelsTimes._fields_}
 
 
 def debug_key_timeline(chroma_list, request, sample_rate=44100, config=None, device=0):

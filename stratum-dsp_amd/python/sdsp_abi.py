@@ -395,6 +395,74 @@ class SdspKeyTimeline(C.Structure):
     ]
 
 
+LEVELS_PEAK, LEVELS_RMS, LEVELS_LOUDNESS, LEVELS_SILENCE_MAP = 1, 2, 4, 8  # enum sdsp_levels_what
+LEVELS_BITS = {"peak": LEVELS_PEAK, "rms": LEVELS_RMS, "loudness": LEVELS_LOUDNESS, "silence": LEVELS_SILENCE_MAP}
+
+
+class SdspLevelsRequest(C.Structure):
+    """sdsp_levels_request: `what` is a mask of sdsp_levels_what bits."""
+
+    _fields_ = [("what", u32)]
+
+
+class SdspLoudness(C.Structure):
+    """sdsp_loudness: the reference's LoudnessMetadata of one normalisation method."""
+
+    _fields_ = [
+        ("status", C.c_int32),
+        ("measured", C.c_int8),
+        ("has_lufs", C.c_int8),
+        ("measured_lufs", f32),
+        ("peak_db", f32),
+        ("rms_db", f32),
+        ("gain_db", f32),
+        ("gain", f32),
+    ]
+
+
+class SdspSilenceRegion(C.Structure):
+    """sdsp_silence_region: [start_sample, end_sample) in the caller's track."""
+
+    _fields_ = [("start_sample", u64), ("end_sample", u64), ("duration_seconds", f32)]
+
+
+class SdspLevels(C.Structure):
+    """sdsp_levels: one track's loudness metadata per method and its silence map (library-owned)."""
+
+    _fields_ = [
+        ("method", SdspLoudness * 3),
+        ("applied_gain", f32),
+        ("n_samples", u64),
+        ("trim_start", u64),
+        ("trim_end", u64),
+        ("frame_size", u32),
+        ("threshold_db", f32),
+        ("n_regions", u64),
+        ("regions", C.POINTER(SdspSilenceRegion)),
+        ("status", C.c_int32),
+    ]
+
+
+class SdspRequestSet(C.Structure):
+    """sdsp_request_set: the optional requests of sdsp_analyze_batch_device_with, by name."""
+
+    _fields_ = [
+        ("struct_size", u32),
+        ("ov_req", C.POINTER(SdspOverviewRequest)),
+        ("overviews", C.POINTER(SdspOverview)),
+        ("kt_req", C.POINTER(SdspKeyTimelineRequest)),
+        ("timelines", C.POINTER(SdspKeyTimeline)),
+        ("lv_req", C.POINTER(SdspLevelsRequest)),
+        ("levels", C.POINTER(SdspLevels)),
+    ]
+
+
+class SdspDebugLevelsTimes(C.Structure):
+    """sdsp_debug_levels_times (include/stratum_hip_debug.h)."""
+
+    _fields_ = [("fold_ms", C.c_double), ("fold2_ms", C.c_double), ("tracks", u64)]
+
+
 OVERVIEW_ARRAYS = ("smin", "smax", "low", "mid", "high")
 
 
