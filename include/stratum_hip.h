@@ -551,6 +551,86 @@ typedef struct sdsp_levels {
 } sdsp_levels;
 
 /*
+ * Tempo map: what the beat stage computes on the way to the beat list and drops, as the reference's
+ * analyze_audio does: the consensus onsets, the tempo segments of detect_tempo_variations over the
+ * whole-track HMM beats with what the Bayesian refinement did in each (beat_tracking/mod.rs:140-219,
+ * tempo_variation.rs:95-227, bayesian.rs:104-178), and the time signature that chose the downbeats
+ * (time_signature.rs:90-199).  Everything is a function of (onsets, nominal_bpm): with the onsets
+ * returned a caller can recompute every field.  Times are seconds on the time axis of the result's
+ * beats (0 = first_sample of the caller's track).
+ *
+ * Segments: exactly detect_tempo_variations(HMM beats, nominal_bpm); start_time, end_time, bpm and
+ * confidence are the reference's f32 values.  With b the HMM beats (hmm_beats of them):
+ *   - fewer than 4 beats: one segment [b first, b last], nominal_bpm, confidence 0.5, not variable;
+ *     a span under 2 s, or no window that qualified: the same with confidence 0.8;
+ *   - else windows of seg_dur = clamp(span / 4, 4, 8) s starting at cur, from cur = b first while
+ *     cur < b last, where cur is the sequential f32 accumulation cur += seg_dur - seg_dur / 2 (not
+ *     b first + s * step); a window ends at min(cur + seg_dur, b last);
+ *   - a window with fewer than 3 beats in [start, end], or without a positive interval, emits nothing;
+ *   - bpm = 60 / mean positive interval, cv = sd / mean (population variance, both folded in beat
+ *     order), is_variable = cv > 0.15, confidence = max(1 - min(cv / 0.3, 1), 0).
+ * Refinement (filled only when has_variation; else updated = 0 and the four fields are 0): a tracker
+ * starts at nominal_bpm and walks the segments in order, its tempo carrying from one variable segment
+ * to the next.  In a variable segment with onsets in [start_time, end_time] (n_onsets of them) it
+ * scores the candidates max(t - 5, 60), +0.5, ... <= min(t + 5, 180) around its tempo t; updated_bpm
+ * is the first candidate that reaches the maximum likelihood (t itself when none is positive),
+ * updated_confidence = min(likelihood * penalty, 1) with penalty 1 / 0.8 / 0.5 for a change below 1 /
+ * below 3 / otherwise, and n_beats the beat count of the HMM re-run over those onsets at updated_bpm
+ * (0 if it failed).  A variable segment without onsets is skipped (updated 0, n_beats 0).  A constant
+ * segment passes the HMM beats in [start_time, end_time] on: n_beats of them.  The refined list is the
+ * concatenation, stably sorted: `refined` (it was not empty, and is what the result publishes)
+ * implies sum of n_beats == the result's n_beats, and because the windows overlap by half, beats
+ * of overlapping segments are in that list twice.
+ *
+ * Time signature: detect_time_signature(the published beats, nominal_bpm).  time_signature_scores are
+ * the scores of 4/4, 3/4 and 6/8, 0.7 x the mean similarity of the positive intervals at lag 4, 3, 6
+ * + 0.3 / (1 + cv); the LAST maximum wins and time_signature_confidence is its score clamped to
+ * [0, 1].  With fewer than 8 beats or no positive interval nothing is scored: beats_per_bar 4,
+ * confidence 0.5, time_signature_scored 0.  What these numbers are: a perfectly regular grid ties all
+ * three scores and is therefore reported as 6 beats per bar; an exact click track comes out as 6, a
+ * four-bar 120 BPM loop as 3.  The value explains which of the published beats became downbeats; it
+ * is not a meter estimate.
+ *
+ * onsets: the consensus onset list the beat stage and the legacy estimator ran on, as sample
+ * positions after first_sample, ascending.  SDSP_TEMPO_MAP_SEGMENTS asks for the segment list,
+ * SDSP_TEMPO_MAP_ONSETS for the onset list (n_* = 0 and NULL when not asked for); the scalar fields
+ * are always filled.
+ *
+ * Per track: an analysis status other than SDSP_OK gives that status and zeroed fields.  A track
+ * without a grid (tempo <= 0 or above 300, fewer than 2 onsets, an HMM or tracker error) has has_grid 0,
+ * no segments, zero counts, beats_per_bar 0, and still its nominal tempo and its onsets.
+ */
+enum sdsp_tempo_map_what { SDSP_TEMPO_MAP_SEGMENTS = 1, SDSP_TEMPO_MAP_ONSETS = 2 }; /* bits of sdsp_tempo_map_request.what */
+typedef struct sdsp_tempo_map_request { uint32_t what; } sdsp_tempo_map_request;
+
+typedef struct sdsp_tempo_segment { /* TempoSegment, tempo_variation.rs:56-71, and what mod.rs:167-208 did with it */
+    float start_time, end_time;     /* seconds, on the time axis of the result's beats */
+    float bpm, confidence;
+    uint8_t is_variable;
+    uint8_t updated;                /* the Bayesian tracker was updated with this segment's onsets */
+    uint32_t n_onsets;              /* onsets in [start_time, end_time] handed to it (0 unless updated) */
+    float updated_bpm, updated_confidence; /* update_with_onsets' return (0 unless updated) */
+    uint32_t n_beats;               /* beats this segment put into the refined list (0 without variation) */
+} sdsp_tempo_segment;
+
+typedef struct sdsp_tempo_map {
+    int32_t status;                 /* the track's sdsp_status */
+    int8_t has_grid;                /* generate_beat_grid returned Ok: the result has beats */
+    int8_t has_variation, refined;  /* has_tempo_variation(); the published beats are the refined list */
+    int8_t time_signature_scored;   /* 0: fewer than 8 beats or no positive interval -> (4, 0.5), scores 0 */
+    float nominal_bpm, nominal_confidence; /* what the beat stage ran with */
+    uint32_t hmm_beats;             /* the whole-track HMM's beat count */
+    uint32_t beats_per_bar;         /* 4, 3 or 6 */
+    float time_signature_confidence;
+    float time_signature_scores[3]; /* 4/4, 3/4, 6/8 */
+    uint64_t first_sample;          /* trim start in the caller's track, as in sdsp_overview */
+    uint64_t n_segments;
+    sdsp_tempo_segment* segments;   /* library-owned, one allocation with onsets */
+    uint64_t n_onsets;
+    uint32_t* onsets;
+} sdsp_tempo_map;
+
+/*
  * The optional requests of one analysis call, by name: a later request is a new pair of fields at
  * the end, and a caller built against an older header (a smaller struct_size) keeps working.
  */
@@ -559,6 +639,7 @@ typedef struct sdsp_request_set {
     const sdsp_overview_request* ov_req;     sdsp_overview* overviews;
     const sdsp_key_timeline_request* kt_req; sdsp_key_timeline* timelines;
     const sdsp_levels_request* lv_req;       sdsp_levels* levels;
+    const sdsp_tempo_map_request* tm_req;    sdsp_tempo_map* tempo_maps;
 } sdsp_request_set;
 
 /*
@@ -570,6 +651,9 @@ typedef struct sdsp_request_set {
  * changes an sdsp_result.  Refused with SDSP_ERR_INVALID_INPUT before any device is touched, beside
  * what sdsp_analyze_batch_device_requests refuses: a levels request with what == 0 or with unknown
  * bits, a request without its output array, a struct_size smaller than the first request pair.
+ * Tempo maps (n_tracks entries, freed one by one with sdsp_tempo_map_free) as above; also refused:
+ * a tempo map request with what == 0 or unknown bits, or with SDSP_STAGES_BPM_ONLY, which has no
+ * beat stage.  The nested exact key reruns never see a request.
  */
 int32_t sdsp_analyze_batch_device_with(const float* d_samples, const uint64_t* offsets, const uint64_t* lens,
                                        uint64_t n_tracks, uint32_t sample_rate, const sdsp_config* cfg,
@@ -577,6 +661,8 @@ int32_t sdsp_analyze_batch_device_with(const float* d_samples, const uint64_t* o
                                        const sdsp_request_set* set);
 /* Frees the regions owned by one sdsp_levels. */
 void sdsp_levels_free(sdsp_levels* l);
+/* Frees the arrays owned by one tempo map (they share one allocation: never free() them one by one). */
+void sdsp_tempo_map_free(sdsp_tempo_map* m);
 
 /*
  * Synthetic track generator on device: writes n_tracks tracks of `len`

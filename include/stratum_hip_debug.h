@@ -284,6 +284,32 @@ int32_t sdsp_debug_beat_grid(const uint32_t* onsets, const uint64_t* n_onsets, c
                              uint32_t sample_rate, const sdsp_config* cfg, sdsp_debug_beat_out* out, int32_t device);
 
 /*
+ * Stage probe of the tempo map (include/stratum_hip.h, sdsp_tempo_map): sdsp_debug_beat_grid's
+ * arguments, set-up and launches with the pipeline's own tempo map step queued behind k_beat and
+ * read back with the beat lists, as an analysis call with a tempo map request does.  what: the
+ * request's bits.  maps receives n_tracks maps (free each with sdsp_tempo_map_free): status SDSP_OK,
+ * or SDSP_ERR_PROCESSING with zeroed fields for a track whose lists outgrew their capacity; the onset
+ * list is the uploaded one, first_sample 0.  beats (NULL allowed) receives what sdsp_debug_beat_grid
+ * returns, from the same launch.  Allocates only buffers of its own, released before it returns.
+ */
+int32_t sdsp_debug_tempo_map(const uint32_t* onsets, const uint64_t* n_onsets, const uint64_t* frames,
+                             const uint64_t* n_trim, const float* bpm, const float* conf, uint64_t n_tracks,
+                             uint32_t sample_rate, const sdsp_config* cfg, uint32_t what, sdsp_tempo_map* maps,
+                             sdsp_debug_beat_out* beats, int32_t device);
+
+/*
+ * The tempo map step of the last sdsp_analyze_batch_device_with call with a tempo map request on
+ * `device`, summed over its sub-batches: HIP event times of k_tempo_map (from k_beat's end to its
+ * own) and of k_beat (the call's beat_ms), and the tracks mapped.  The events lie on the main
+ * stream beside the key stream's work.  All zero after a call without a request.
+ */
+typedef struct sdsp_debug_tempo_map_times {
+    double map_ms, beat_ms;
+    uint64_t tracks;
+} sdsp_debug_tempo_map_times;
+int32_t sdsp_debug_last_tempo_map_times(int32_t device, sdsp_debug_tempo_map_times* out);
+
+/*
  * Stage probe of the candidate selection: the pipeline's own select launch (k_tempo_select with the
  * parameters an analysis call derives from cfg: Pipeline::pass_select from its offset tables on) over
  * uploaded tempogram lists instead of a novelty curve.  Per track t and variant v (full, low, mid,

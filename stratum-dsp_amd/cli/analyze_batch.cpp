@@ -31,9 +31,13 @@
 // (include/stratum_hip.h, sdsp_levels): the loudness metadata of each normalisation method in LIST
 // (out of peak,rms,loudness,silence; all four without a list), -inf as null, and the silence
 // regions as [start_sample, end_sample, seconds].  It combines with the other two in one analysis.
+// --tempo-map[=LIST] (opt-in; JSONL only): each line's object gets a "tempo_map" member
+// (include/stratum_hip.h, sdsp_tempo_map): the tempo segments with what the Bayesian refinement did in
+// each, the time signature with its three scores, and the consensus onsets (LIST out of
+// segments,onsets; both without a list).  It combines with the other three in one analysis.
 //
 //   analyze_batch [--jobs N] [--devices MASK] [--json] [--gpu-decode] [--overview N | --overview-frames K]
-//                 [--key-timeline SEC[:OVERLAP[:MINCONF]]] [--levels [LIST]] <file1> <file2> ...
+//                 [--key-timeline SEC[:OVERLAP[:MINCONF]]] [--levels [LIST]] [--tempo-map[=LIST]] <file1> <file2> ...
 #include <algorithm>
 #include <atomic>
 #include <chrono>
@@ -62,6 +66,7 @@ struct Item {
     std::string overview;  // --overview: the "overview" member's value
     std::string timeline;  // --key-timeline: the "key_timeline" member's value
     std::string levels;    // --levels: the "levels" member's value
+    std::string tempo_map; // --tempo-map: the "tempo_map" member's value
 };
 
 // floats so that an f32 round-trips
@@ -165,6 +170,34 @@ std::string levels_json(const sdsp_levels& l) {
     return s + "]}";
 }
 
+std::string tempo_map_json(const sdsp_tempo_map& m) {
+    char b[512];
+    std::snprintf(b, sizeof b,
+                  "{\"status\":%d,\"has_grid\":%d,\"has_variation\":%d,\"refined\":%d,\"nominal_bpm\":%s,"
+                  "\"nominal_confidence\":%s,\"hmm_beats\":%u,\"beats_per_bar\":%u,\"time_signature_confidence\":%.9g,"
+                  "\"time_signature_scored\":%d,\"time_signature_scores\":[%.9g,%.9g,%.9g],\"first_sample\":%llu",
+                  m.status, m.has_grid, m.has_variation, m.refined, json_db(m.nominal_bpm).c_str(),
+                  json_db(m.nominal_confidence).c_str(), m.hmm_beats, m.beats_per_bar, (double)m.time_signature_confidence,
+                  m.time_signature_scored, (double)m.time_signature_scores[0], (double)m.time_signature_scores[1],
+                  (double)m.time_signature_scores[2], (unsigned long long)m.first_sample);
+    std::string s = b;
+    // a segment: [start, end, bpm, confidence, is_variable, updated, n_onsets, updated_bpm, updated_confidence, n_beats]
+    s += ",\"n_segments\":" + std::to_string((unsigned long long)m.n_segments) + ",\"segments\":[";
+    for (uint64_t i = 0; i < m.n_segments; i++) {
+        const sdsp_tempo_segment& e = m.segments[i];
+        std::snprintf(b, sizeof b, "%s[%.9g,%.9g,%.9g,%.9g,%u,%u,%u,%.9g,%.9g,%u]", i ? "," : "", (double)e.start_time,
+                      (double)e.end_time, (double)e.bpm, (double)e.confidence, (unsigned)e.is_variable, (unsigned)e.updated,
+                      e.n_onsets, (double)e.updated_bpm, (double)e.updated_confidence, e.n_beats);
+        s += b;
+    }
+    s += "],\"n_onsets\":" + std::to_string((unsigned long long)m.n_onsets) + ",\"onsets\":[";
+    for (uint64_t i = 0; i < m.n_onsets; i++) {
+        std::snprintf(b, sizeof b, i ? ",%u" : "%u", m.onsets[i]);
+        s += b;
+    }
+    return s + "]}";
+}
+
 // percentile as the example computes it: sort, index round((len-1) * p)
 float percentile(std::vector<float> xs, float p) {
     std::sort(xs.begin(), xs.end());
@@ -246,6 +279,8 @@ int main(int argc, char** argv) {
     bool timeline = false;
     sdsp_levels_request lvreq{SDSP_LEVELS_PEAK | SDSP_LEVELS_RMS | SDSP_LEVELS_LOUDNESS | SDSP_LEVELS_SILENCE_MAP};
     bool levels = false;
+    sdsp_tempo_map_request tmreq{SDSP_TEMPO_MAP_SEGMENTS | SDSP_TEMPO_MAP_ONSETS};
+    bool tempo_map = false;
     std::vector<std::string> paths;
     for (size_t i = 0; i < a.size(); i++) {
         const std::string& s = a[i];
@@ -320,10 +355,31 @@ int main(int argc, char** argv) {
                 lvreq.what = what;
                 i++;
             }
+        } else if (s == "--tempo-map" || s.rfind("--tempo-map=", 0) == 0) {
+            tempo_map = true;
+            if (s.size() > 11) {  // =LIST out of segments,onsets
+                const std::string w = s.substr(12);
+                uint32_t what = 0;
+                bool good = !w.empty();
+                for (size_t p0 = 0; good;) {
+                    const size_t p1 = std::min(w.find(',', p0), w.size());
+                    const std::string part = w.substr(p0, p1 - p0);
+                    if (part == "segments") what |= SDSP_TEMPO_MAP_SEGMENTS;
+                    else if (part == "onsets") what |= SDSP_TEMPO_MAP_ONSETS;
+                    else good = false;
+                    if (p1 == w.size()) break;
+                    p0 = p1 + 1;
+                }
+                if (!good) {
+                    std::fprintf(stderr, "Error: --tempo-map=LIST takes a list out of segments,onsets\n");
+                    return 1;
+                }
+                tmreq.what = what;
+            }
         } else if (s == "--help" || s == "-h") {
             std::fprintf(stderr,
                          "Usage: analyze_batch [--jobs N] [--devices MASK] [--json] [--gpu-decode] [--overview N | "
-                         "--overview-frames K] [--key-timeline SEC[:OVERLAP[:MINCONF]]] [--levels [LIST]] <file1> <file2> ...\n\n"
+                         "--overview-frames K] [--key-timeline SEC[:OVERLAP[:MINCONF]]] [--levels [LIST]] [--tempo-map[=LIST]] <file1> <file2> ...\n\n"
                          "--jobs N        Decode workers (default: CPU-1)\n"
                          "--devices MASK  GPU bitmask (default: all visible GPUs)\n"
                          "--json          Emit one JSON object per line (JSONL)\n"
@@ -334,7 +390,9 @@ int main(int argc, char** argv) {
                          "                primary key and key changes (\"key_timeline\"); OVERLAP defaults to SEC/4, MINCONF\n"
                          "                to -1 (every change; 0.2 is the reference's threshold)\n"
                          "--levels [LIST] With --json: add each track's loudness metadata and silence regions (\"levels\");\n"
-                         "                LIST out of peak,rms,loudness,silence (default: all four)\n");
+                         "                LIST out of peak,rms,loudness,silence (default: all four)\n"
+                         "--tempo-map[=LIST]  With --json: add each track's tempo segments, time signature and consensus\n"
+                         "                onsets (\"tempo_map\"); LIST out of segments,onsets (default: both)\n");
             return 0;
         } else {
             paths.push_back(s);
@@ -347,6 +405,7 @@ int main(int argc, char** argv) {
     if (overview && !json) std::fprintf(stderr, "Note: --overview / --overview-frames add to the --json lines only\n");
     if (timeline && !json) std::fprintf(stderr, "Note: --key-timeline adds to the --json lines only\n");
     if (levels && !json) std::fprintf(stderr, "Note: --levels adds to the --json lines only\n");
+    if (tempo_map && !json) std::fprintf(stderr, "Note: --tempo-map adds to the --json lines only\n");
     if (paths.empty()) {
         std::fprintf(stderr, "ERROR: Provide at least one audio file path. Use --help for usage.\n");
         return 2;
@@ -401,10 +460,12 @@ int main(int argc, char** argv) {
     sdsp_config cfg;
     sdsp_config_default(&cfg);
     auto take = [](Item& it, const sdsp_result& r, const sdsp_overview* ov = nullptr,
-                   const sdsp_key_timeline* kt = nullptr, const sdsp_levels* lv = nullptr) {
+                   const sdsp_key_timeline* kt = nullptr, const sdsp_levels* lv = nullptr,
+                   const sdsp_tempo_map* tm = nullptr) {
         if (ov) it.overview = overview_json(*ov);
         if (kt) it.timeline = key_timeline_json(*kt);
         if (lv) it.levels = levels_json(*lv);
+        if (tm) it.tempo_map = tempo_map_json(*tm);
         if (r.status != 0) {
             it.error = std::string("analysis failed: ") + r.error_message;
             return;
@@ -428,6 +489,7 @@ int main(int argc, char** argv) {
         std::vector<sdsp_overview> ovs;
         std::vector<sdsp_key_timeline> kts;
         std::vector<sdsp_levels> lvs;
+        std::vector<sdsp_tempo_map> tms;
         sdsp_request_set set{};
     };
     auto requests = [&](size_t n) {
@@ -435,6 +497,7 @@ int main(int argc, char** argv) {
         q.ovs.resize(overview ? n : 0);  // (zeroed; without a request: the plain entry)
         q.kts.resize(timeline ? n : 0);
         q.lvs.resize(levels ? n : 0);
+        q.tms.resize(tempo_map ? n : 0);
         return q;
     };
     auto request_set = [&](Requests& q) {
@@ -442,13 +505,16 @@ int main(int argc, char** argv) {
         if (overview) q.set.ov_req = &ovreq, q.set.overviews = q.ovs.data();
         if (timeline) q.set.kt_req = &ktreq, q.set.timelines = q.kts.data();
         if (levels) q.set.lv_req = &lvreq, q.set.levels = q.lvs.data();
+        if (tempo_map) q.set.tm_req = &tmreq, q.set.tempo_maps = q.tms.data();
         return &q.set;
     };
     auto take_requests = [&](Item& it, const sdsp_result& r, Requests& q, size_t j) {
-        take(it, r, overview ? &q.ovs[j] : nullptr, timeline ? &q.kts[j] : nullptr, levels ? &q.lvs[j] : nullptr);
+        take(it, r, overview ? &q.ovs[j] : nullptr, timeline ? &q.kts[j] : nullptr, levels ? &q.lvs[j] : nullptr,
+             tempo_map ? &q.tms[j] : nullptr);
         if (overview) sdsp_overview_free(&q.ovs[j]);
         if (timeline) sdsp_key_timeline_free(&q.kts[j]);
         if (levels) sdsp_levels_free(&q.lvs[j]);
+        if (tempo_map) sdsp_tempo_map_free(&q.tms[j]);
     };
 
     if (gpu_decode) {
@@ -531,7 +597,7 @@ int main(int argc, char** argv) {
             ptrs.push_back(items[i].samples.data());
             lens.push_back(items[i].samples.size());
         }
-        if (overview || timeline || levels) {
+        if (overview || timeline || levels || tempo_map) {
             // the requests entry reads device-resident tracks: upload each group to the first device of
             // the mask in parts of at most 512 tracks or 2 Gi samples
             int dev = 0;
@@ -602,6 +668,10 @@ int main(int argc, char** argv) {
             if (!o.levels.empty()) {
                 std::fputs(",\"levels\":", stdout);
                 std::fputs(o.levels.c_str(), stdout);
+            }
+            if (!o.tempo_map.empty()) {
+                std::fputs(",\"tempo_map\":", stdout);
+                std::fputs(o.tempo_map.c_str(), stdout);
             }
             std::fputs("}\n", stdout);
         } else {

@@ -377,6 +377,19 @@ void launch_beat(const int* tracks, int n_items, const uint32_t* onsets, const u
 // dense beat/downbeat lists: pfx has 2 (n + 1) entries (beats, then downbeats)
 void launch_beat_compact(int n, const BeatOut* out, const uint64_t* beat_off, const float* beats, const float* downs,
                          uint64_t* pfx, float* cb, float* cd, hipStream_t st);
+// ---- k_tempo_map: the tempo map request (tempo_map_core.hpp has TmSeg, TmOut and the arithmetic) ----
+struct TmSeg;
+struct TmOut;
+// After launch_beat on the same stream, over the same onsets, tempo and lists: track t's map into
+// out[t] and its segments into segs[seg_off[t] ...], at most seg_off[t + 1] - seg_off[t] of them.
+// `scratch` is launch_beat's (free once k_beat has run): the onsets and HMM beats that outgrow LDS.
+void launch_tempo_map(int n_tracks, const uint32_t* onsets, const uint64_t* on_off, const int* on_n, uint32_t sr,
+                      const float* bpm, float* scratch, const uint64_t* beat_off, const int* beat_cap,
+                      const float* beats, const BeatOut* bout, const uint64_t* seg_off, TmSeg* segs, TmOut* out,
+                      hipStream_t st);
+// track t's on_n[t] onsets from onsets[on_off[t] ...] to dense[pfx[t] ...] (pfx: the host's prefix of on_n)
+void launch_onset_gather(int n_tracks, const uint32_t* onsets, const uint64_t* on_off, const int* on_n,
+                         const uint64_t* pfx, uint32_t* dense, hipStream_t st);
 void launch_mask(float* mags, int stride, int B, const uint64_t* frame_pfx, const int* tracks, int n_items, int margin,
                  float power, hipStream_t st, bool smooth_only = false);
 void launch_tuning(const float* mags, const uint64_t* frame_pfx, const int* tracks, int n_items, const TuningParams& P,

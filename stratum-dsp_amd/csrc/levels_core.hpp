@@ -224,6 +224,8 @@ inline const char* request_set_read(const sdsp_request_set* set, sdsp_request_se
     if (has(offsetof(sdsp_request_set, timelines))) out->timelines = set->timelines;
     if (has(offsetof(sdsp_request_set, lv_req))) out->lv_req = set->lv_req;
     if (has(offsetof(sdsp_request_set, levels))) out->levels = set->levels;
+    if (has(offsetof(sdsp_request_set, tm_req))) out->tm_req = set->tm_req;
+    if (has(offsetof(sdsp_request_set, tempo_maps))) out->tempo_maps = set->tempo_maps;
     return nullptr;
 }
 

@@ -13,8 +13,9 @@
 //   C  seed_tempo, escalate for ambiguous tracks: STFT 2048/256 and 2048/1024 of those tracks, the
 //      same feature/novelty/tempogram/scoring kernels, then multi-resolution fusion;
 //      perc_fallback, legacy_select (pipeline_tempo.hip)
-//   D  beat_grid; join_key (pipeline_key.hip): the previous sub-batch's key results, and this one's
-//      now or one sub-batch late; download_results, beat_sync_revote, fill_results
+//   D  beat_grid (with a tempo map request: tempo_map behind it); join_key (pipeline_key.hip): the
+//      previous sub-batch's key results, and this one's now or one sub-batch late; download_results,
+//      beat_sync_revote, fill_results
 //                                                        -> host reads results (sync 3)
 // Each stage returns a plain struct with what later stages read (pipeline.hpp).
 // pipeline_params.hip maps the configuration to launch parameters, pipeline_debug.hip has the
@@ -65,6 +66,7 @@ void Pipeline::run(const float* d_samples, const std::vector<uint64_t>& in_off, 
     if (ov_out_) ov_out_->assign(T, TrackOv{});
     if (kt_out_) kt_out_->assign(T, TrackKt{});
     if (lv_out_) lv_out_->assign(T, TrackLv{});
+    if (tm_out_) tm_out_->assign(T, TrackTm{});
     const std::string why = check_supported(cfg_, sr_);
     for (size_t i = 0; i < T; i++) {
         if (n_raw[i] == 0) {
@@ -128,6 +130,8 @@ void Pipeline::run(const float* d_samples, const std::vector<uint64_t>& in_off, 
             const double F = n / (fs_ / 2) + 1.0;
             need[i] += 64.0 + (map_on() ? F * 4.0 + (F / (double)(lv_min_frames(sr_, (uint64_t)fs_) + 1) + 2.0) * 2.0 * 16.0 : 0.0);
         }
+        if (tm_out_ && !bpm_only_)  // the segment lists and the gathered onsets (a few per second)
+            need[i] += (double)tm_segment_capacity((uint64_t)n, sr_) * sizeof(TmSeg) + n / std::max<uint32_t>(sr_, 1) * 16.0 * 4.0;
         total_need += need[i];
     }
     const double parts = std::max(1.0, std::ceil(total_need / budget));
@@ -255,8 +259,16 @@ void Pipeline::sub_batch(const float* d_samples, const std::vector<uint64_t>& in
     // D: beat grid, key joins, results
     const Beats bt = beat_grid(bin, bo, on, tp);
     tm.mark(5);
+    const TempoMapQ tq = tempo_map(bin, on, tp, bt);  // (nothing without a request)
+    if (tq.on) tm.mark(9);
     std::vector<KeyOut> kout = join_key(d_samples, in_off, n_raw, f, kl, htr, res);  // empty: joined one sub-batch late
-    const ResultsHost rh = download_results(bt, bin, bo);
+    const ResultsHost rh = download_results(bt, bin, bo, tq);
+    if (tq.on) {
+        tempo_map_results(rh, f, tp);
+        d_.last_tm.map_ms += tm.ms(5, 9);
+        d_.last_tm.beat_ms += tm.ms(4, 5);
+        d_.last_tm.tracks += (uint64_t)NR;
+    }
     overview_results(ov, f, bin, bo, tm);
     htr("D down");
     if (cfg_.enable_key_beat_synchronous && !cfg_.enable_key_log_frequency && !kl.K.empty()) {
@@ -568,14 +580,63 @@ Beats Pipeline::beat_grid(const TempoPassIn& bin, const TempoPassOut& bo, const 
     bt.d_beats = c_.dev<float>("D.beats", boff[(size_t)NR]);
     bt.d_downs = c_.dev<float>("D.downs", boff[(size_t)NR]);
     bt.d_bout = c_.dev<BeatOut>("D.bout", (size_t)NR);
+    bt.d_bscr = d_bscr;
+    bt.d_bcap = d_bcap;
     launch_beat(d_ident, NR, on.d_chosen, on.d_coff, on.d_cn, sr_, tp.d_fbpm, tp.d_fconf, d_bscr, bt.d_boff, d_bcap,
                 bt.d_beats, bt.d_downs, bt.d_bout, d_.stream);
     SDSP_HIP_CHECK(hipGetLastError());
     return bt;
 }
 
-// The beat lists compacted on the device and read back (sync 3), with the base pass's candidates.
-ResultsHost Pipeline::download_results(const Beats& bt, const TempoPassIn& bin, const TempoPassOut& bo) {
+// The tempo maps (include/stratum_hip.h, sdsp_tempo_map) of the surviving tracks, queued on the
+// main stream right behind k_beat: one wave per track over the same onsets, tempo and published
+// beats (k_tempo_map.hip).  Segment capacity per track: tm_segment_capacity.
+TempoMapQ Pipeline::tempo_map(const TempoPassIn& bin, const Onsets& on, const Tempo& tp, const Beats& bt) {
+    TempoMapQ tq;
+    if (!tm_out_) return tq;
+    tq.on = true;
+    const int NR = (int)bin.n_trim.size();
+    tq.soff.assign((size_t)NR + 1, 0);
+    for (int i = 0; i < NR; i++)
+        tq.soff[(size_t)i + 1] = tq.soff[(size_t)i] + tm_segment_capacity(bin.n_trim[(size_t)i], sr_);
+    uint64_t* d_soff = c_.up("D.tmsoff", tq.soff);
+    tq.d_segs = c_.dev<TmSeg>("D.tmsegs", tq.soff[(size_t)NR]);
+    tq.d_out = c_.dev<TmOut>("D.tmout", (size_t)NR);
+    tq.d_chosen = on.d_chosen;
+    tq.d_coff = on.d_coff;
+    tq.d_cn = on.d_cn;
+    launch_tempo_map(NR, on.d_chosen, on.d_coff, on.d_cn, sr_, tp.d_fbpm, bt.d_bscr, bt.d_boff, bt.d_bcap, bt.d_beats,
+                     bt.d_bout, d_soff, tq.d_segs, tq.d_out, d_.stream);
+    SDSP_HIP_CHECK(hipGetLastError());
+    return tq;
+}
+
+// The sub-batch's tempo maps into the call's per-track entries.
+void Pipeline::tempo_map_results(const ResultsHost& rh, const Front& f, const Tempo& tp) {
+    const size_t NR = f.R.size();
+    for (size_t i = 0; i < NR; i++)
+        (*tm_out_)[f.slot[i]] = track_tempo_map(rh, i, tp.fbpm_h[i], tp.fconf_h[i], f.ts[(size_t)f.R[i]]);
+}
+
+// Track i of a sub-batch's downloaded tempo maps.
+TrackTm Pipeline::track_tempo_map(const ResultsHost& rh, size_t i, float bpm, float conf, uint64_t first) const {
+    TrackTm m;
+    m.on = true;
+    m.o = rh.tm_out[i];
+    m.bpm = bpm;
+    m.conf = conf;
+    m.first = first;
+    if (m.o.ok > 0 && (tm_what_ & SDSP_TEMPO_MAP_SEGMENTS))
+        m.segs.assign(rh.tm_segs.begin() + (long)rh.tm_soff[i], rh.tm_segs.begin() + (long)(rh.tm_soff[i] + (uint64_t)m.o.n_seg));
+    if (!rh.tm_opfx.empty())
+        m.onsets.assign(rh.tm_onsets.begin() + (long)rh.tm_opfx[i], rh.tm_onsets.begin() + (long)rh.tm_opfx[i + 1]);
+    return m;
+}
+
+// The beat lists compacted on the device and read back (sync 3), with the base pass's candidates
+// and, with a tempo map request, the maps, their segments and the onset lists.
+ResultsHost Pipeline::download_results(const Beats& bt, const TempoPassIn& bin, const TempoPassOut& bo,
+                                       const TempoMapQ& tq) {
     ResultsHost rh;
     const size_t NR = bin.n_trim.size();
     uint64_t* d_bpfx = c_.dev<uint64_t>("D.bpfx", 2 * (NR + 1));
@@ -588,6 +649,20 @@ ResultsHost Pipeline::download_results(const Beats& bt, const TempoPassIn& bin, 
     rh.beats_h = c_.down(rh.d_cbeats, rh.bpfx[NR]);
     rh.downs_h = c_.down(d_cdowns, rh.bpfx[2 * NR + 1]);
     if (cfg_.emit_tempogram_candidates) rh.cand_h = c_.down(bo.cand, NR * (size_t)bin.cand_cap * 4);
+    if (tq.on) {
+        rh.tm_out = c_.down(tq.d_out, NR);
+        rh.tm_soff = tq.soff;
+        if (tm_what_ & SDSP_TEMPO_MAP_SEGMENTS) rh.tm_segs = c_.down(tq.d_segs, tq.soff[NR]);
+        if (tm_what_ & SDSP_TEMPO_MAP_ONSETS) {  // the lists gathered densely, by the counts just read
+            const std::vector<int> cn = c_.down(tq.d_cn, NR);
+            rh.tm_opfx.assign(NR + 1, 0);
+            for (size_t i = 0; i < NR; i++) rh.tm_opfx[i + 1] = rh.tm_opfx[i] + (uint64_t)std::max(cn[i], 0);
+            uint32_t* d_dense = c_.dev<uint32_t>("D.tmons", std::max<uint64_t>(rh.tm_opfx[NR], 1));
+            launch_onset_gather((int)NR, tq.d_chosen, tq.d_coff, tq.d_cn, c_.up("D.tmopfx", rh.tm_opfx), d_dense, d_.stream);
+            SDSP_HIP_CHECK(hipGetLastError());
+            rh.tm_onsets = c_.down(d_dense, rh.tm_opfx[NR]);
+        }
+    }
     return rh;
 }
 

@@ -23,6 +23,7 @@
 #include "../../include/stratum_hip_debug.h"
 #include "kernels.hpp"
 #include "levels_core.hpp"
+#include "tempo_map_core.hpp"
 #include "sdsp_runtime.hpp"
 
 namespace sdsp {
@@ -425,12 +426,31 @@ struct Beats {
     uint64_t* d_boff = nullptr;
     float *d_beats = nullptr, *d_downs = nullptr;
     BeatOut* d_bout = nullptr;
+    float* d_bscr = nullptr;  // k_beat's scratch and capacities (read again by Pipeline::tempo_map)
+    int* d_bcap = nullptr;
+};
+// The tempo maps of the surviving tracks as queued behind k_beat (Pipeline::tempo_map); nothing is
+// queued without a request.
+struct TempoMapQ {
+    bool on = false;
+    std::vector<uint64_t> soff{0};  // segment capacity prefix over the surviving tracks
+    TmSeg* d_segs = nullptr;
+    TmOut* d_out = nullptr;
+    const uint32_t* d_chosen = nullptr;  // the stage's consensus onsets (Onsets)
+    const uint64_t* d_coff = nullptr;
+    const int* d_cn = nullptr;
 };
 struct ResultsHost {
     std::vector<BeatOut> bout;
     std::vector<uint64_t> bpfx;
     std::vector<float> beats_h, downs_h, cand_h;
     float* d_cbeats = nullptr;
+    // with a tempo map request: the maps, their segments (track i's at tm_soff[i]) and the onsets
+    // (track i's at tm_opfx[i]; empty unless asked for)
+    std::vector<TmOut> tm_out;
+    std::vector<TmSeg> tm_segs;
+    std::vector<uint64_t> tm_soff, tm_opfx;
+    std::vector<uint32_t> tm_onsets;
 };
 // The overview envelopes of the surviving tracks as queued after the base pass (Pipeline::overview);
 // nothing is queued without a request.
@@ -464,6 +484,16 @@ struct TrackLv {
     float applied_gain = 1.0f;
     uint64_t n = 0, ts = 0, te = 0;
     std::vector<uint64_t> regions;  // (start, end) sample pairs, ascending
+};
+// One track's tempo map on the host (sdsp_tempo_map without its status).  `on`: the track reached
+// the beat stage.
+struct TrackTm {
+    bool on = false;
+    TmOut o{};
+    float bpm = 0.0f, conf = 0.0f;
+    uint64_t first = 0;
+    std::vector<TmSeg> segs;
+    std::vector<uint32_t> onsets;
 };
 // The levels folds as queued before the sub-batches (Pipeline::levels_prepass) and read at the
 // call's end (Pipeline::levels_join); nothing is queued without a request.
@@ -501,6 +531,9 @@ class Pipeline {
     void debug_beat_grid(const uint32_t* onsets, const uint64_t* n_onsets, const uint64_t* frames,
                          const uint64_t* n_trim, const float* bpm, const float* conf, uint64_t n_tracks,
                          sdsp_debug_beat_out* out);
+    void debug_tempo_map(const uint32_t* onsets, const uint64_t* n_onsets, const uint64_t* frames,
+                         const uint64_t* n_trim, const float* bpm, const float* conf, uint64_t n_tracks, uint32_t what,
+                         std::vector<TrackTm>* maps, sdsp_debug_beat_out* beats);
     void debug_tempo_select(const float* fft, const int32_t* fft_n, const float* acf, int NB, const int32_t present[5],
                             const int32_t* active, uint64_t n_tracks, int top_n, int cand_cap, int gate,
                             sdsp_debug_tempo_est* est, float* cand);
@@ -528,6 +561,13 @@ class Pipeline {
     void set_levels(uint32_t what, std::vector<TrackLv>* out) {
         lv_what_ = what;
         lv_out_ = out;
+    }
+    // Before run(): also compute every track's tempo map (include/stratum_hip.h, sdsp_tempo_map;
+    // `what` checked by tempo_map_request_error) into *out, one entry per track of the call.  A
+    // pipeline without a request queues nothing for it; nested pipelines get none.
+    void set_tempo_map(uint32_t what, std::vector<TrackTm>* out) {
+        tm_what_ = what;
+        tm_out_ = out;
     }
 
    private:
@@ -570,6 +610,8 @@ class Pipeline {
     uint32_t lv_what_ = 0;
     std::vector<TrackLv>* lv_out_ = nullptr;  // the call's levels (set_levels), else nullptr
     LevelsPending lv_pending_;
+    uint32_t tm_what_ = 0;
+    std::vector<TrackTm>* tm_out_ = nullptr;  // the call's tempo maps (set_tempo_map), else nullptr
     bool map_on() const { return lv_out_ && (lv_what_ & SDSP_LEVELS_SILENCE_MAP); }
 
     // force_legacy_bpm skips the tempogram estimate (src/lib.rs:337): no escalation, no
@@ -596,7 +638,11 @@ class Pipeline {
     Onsets onsets(const float* d_samples, const Front& f, const TempoPassIn& bin, const TempoPassOut& bo, const Hpss& hp);
     Onsets onset_lists(const float* d_erms, const uint64_t* d_nt, int HOP, const TempoPassOut& bo, const Hpss& hp);
     Beats beat_grid(const TempoPassIn& bin, const TempoPassOut& bo, const Onsets& on, const Tempo& tp);
-    ResultsHost download_results(const Beats& bt, const TempoPassIn& bin, const TempoPassOut& bo);
+    TempoMapQ tempo_map(const TempoPassIn& bin, const Onsets& on, const Tempo& tp, const Beats& bt);
+    ResultsHost download_results(const Beats& bt, const TempoPassIn& bin, const TempoPassOut& bo,
+                                 const TempoMapQ& tq = TempoMapQ{});
+    void tempo_map_results(const ResultsHost& rh, const Front& f, const Tempo& tp);
+    TrackTm track_tempo_map(const ResultsHost& rh, size_t i, float bpm, float conf, uint64_t first) const;
     Overview overview(const float* d_samples, const TempoPassIn& bin, const TempoPassOut& bo, Timers& tm);
     void overview_results(const Overview& ov, const Front& f, const TempoPassIn& bin, const TempoPassOut& bo, Timers& tm);
     void fill_results(const Front& f, const TempoPassIn& bin, const std::vector<TempoEst>& best, const Tempo& tp,

@@ -209,6 +209,64 @@ void fill_levels(const TrackLv& t, int status, const sdsp_config& cfg, uint32_t 
     o->n_regions = R;
 }
 
+// A checked tempo map request and where the maps go.
+struct TmCall {
+    uint32_t what = 0;
+    sdsp_tempo_map* out = nullptr;
+};
+// One track's tempo map: the analysis status and zeroed fields unless the track is SDSP_OK;
+// SDSP_ERR_PROCESSING for a map whose segments outgrew their capacity.  Both lists share one block.
+void fill_tempo_map(const TrackTm& t, int status, sdsp_tempo_map* o) {
+    std::memset(o, 0, sizeof(*o));
+    o->status = status;
+    if (status != SDSP_OK || !t.on) return;
+    if (t.o.ok < 0) {
+        o->status = SDSP_ERR_PROCESSING;
+        return;
+    }
+    o->nominal_bpm = t.bpm;
+    o->nominal_confidence = t.conf;
+    o->first_sample = t.first;
+    if (t.o.ok > 0) {
+        o->has_grid = 1;
+        o->has_variation = (int8_t)t.o.has_var;
+        o->refined = (int8_t)t.o.refined;
+        o->time_signature_scored = (int8_t)t.o.ts_scored;
+        o->hmm_beats = (uint32_t)t.o.hmm_beats;
+        o->beats_per_bar = (uint32_t)t.o.bpb;
+        o->time_signature_confidence = t.o.ts_conf;
+        for (int k = 0; k < 3; k++) o->time_signature_scores[k] = t.o.score[k];
+    }
+    const size_t S = t.segs.size(), N = t.onsets.size();
+    if (S + N == 0) return;
+    char* blk = (char*)std::malloc(S * sizeof(sdsp_tempo_segment) + N * sizeof(uint32_t));
+    if (!blk) throw std::bad_alloc();
+    if (S) {
+        o->segments = (sdsp_tempo_segment*)blk;
+        for (size_t k = 0; k < S; k++) {
+            sdsp_tempo_segment& e = o->segments[k];
+            const TmSeg& g = t.segs[k];
+            std::memset(&e, 0, sizeof e);
+            e.start_time = g.start;
+            e.end_time = g.end;
+            e.bpm = g.bpm;
+            e.confidence = g.conf;
+            e.is_variable = (uint8_t)(g.variable != 0);
+            e.updated = (uint8_t)(g.updated != 0);
+            e.n_onsets = g.n_onsets;
+            e.updated_bpm = g.ubpm;
+            e.updated_confidence = g.uconf;
+            e.n_beats = g.n_beats;
+        }
+        o->n_segments = S;
+    }
+    if (N) {
+        o->onsets = (uint32_t*)(blk + S * sizeof(sdsp_tempo_segment));
+        std::memcpy(o->onsets, t.onsets.data(), N * sizeof(uint32_t));
+        o->n_onsets = N;
+    }
+}
+
 // One device-resident batch on `device`.  The engine's main stream first waits for `user_stream`
 // (everything queued on it so far) and for `wait_ev` (a copy's completion), whichever are given.
 // The batch on a context whose mutex the caller holds (run_device, and sdsp_analyze_audio's
@@ -216,7 +274,7 @@ void fill_levels(const TrackLv& t, int status, const sdsp_config& cfg, uint32_t 
 int32_t run_locked(DeviceCtx& d, const float* d_samples, const uint64_t* offsets, const uint64_t* lens, uint64_t n,
                    uint32_t sr, const sdsp_config* cfg, void* user_stream, sdsp_result* outs, int stages,
                    hipEvent_t wait_ev, const sdsp_overview_request* req = nullptr, sdsp_overview* ovs = nullptr,
-                   const KtCall* ktc = nullptr, const LvCall* lvc = nullptr) {
+                   const KtCall* ktc = nullptr, const LvCall* lvc = nullptr, const TmCall* tmc = nullptr) {
     if (stages != SDSP_STAGES_FULL && stages != SDSP_STAGES_BPM_ONLY) throw HipError("unknown stage mask");
     if (user_stream) {
         hipEvent_t ev;
@@ -238,6 +296,9 @@ int32_t run_locked(DeviceCtx& d, const float* d_samples, const uint64_t* offsets
     std::vector<TrackLv> lvl;
     d.last_lv = sdsp_debug_levels_times{};
     if (lvc) p.set_levels(lvc->what, &lvl);
+    std::vector<TrackTm> tml;
+    d.last_tm = sdsp_debug_tempo_map_times{};
+    if (tmc) p.set_tempo_map(tmc->what, &tml);
     try {
         p.run(d_samples, off, ln, res);
         // Certified block energies: a track whose key vote had an energy-dependent
@@ -290,6 +351,8 @@ int32_t run_locked(DeviceCtx& d, const float* d_samples, const uint64_t* offsets
             fill_key_timeline(ktl[(size_t)i], res[(size_t)i].status, *cfg, sr, *ktc, &ktc->out[i]);
     if (lvc)
         for (uint64_t i = 0; i < n; i++) fill_levels(lvl[(size_t)i], res[(size_t)i].status, *cfg, sr, &lvc->out[i]);
+    if (tmc)
+        for (uint64_t i = 0; i < n; i++) fill_tempo_map(tml[(size_t)i], res[(size_t)i].status, &tmc->out[i]);
     return SDSP_OK;
 }
 
@@ -297,11 +360,12 @@ int32_t run_device(int device, const float* d_samples, const uint64_t* offsets, 
                    uint32_t sr, const sdsp_config* cfg, void* user_stream, sdsp_result* outs,
                    int stages = SDSP_STAGES_FULL, hipEvent_t wait_ev = nullptr,
                    const sdsp_overview_request* req = nullptr, sdsp_overview* ovs = nullptr,
-                   const KtCall* ktc = nullptr, const LvCall* lvc = nullptr) {
+                   const KtCall* ktc = nullptr, const LvCall* lvc = nullptr, const TmCall* tmc = nullptr) {
     DeviceCtx& d = device_ctx(device);
     std::lock_guard<std::mutex> lk(d.mu);
     SDSP_HIP_CHECK(hipSetDevice(device));
-    return run_locked(d, d_samples, offsets, lens, n, sr, cfg, user_stream, outs, stages, wait_ev, req, ovs, ktc, lvc);
+    return run_locked(d, d_samples, offsets, lens, n, sr, cfg, user_stream, outs, stages, wait_ev, req, ovs, ktc, lvc,
+                      tmc);
 }
 
 }  // namespace
@@ -488,7 +552,9 @@ int32_t sdsp_analyze_batch_device_with(const float* d_samples, const uint64_t* o
     sdsp_key_timeline* timelines = set.timelines;
     const sdsp_levels_request* lv_req = set.lv_req;
     sdsp_levels* levels = set.levels;
-    if (!set_err && !ov_req && !kt_req && !lv_req)
+    const sdsp_tempo_map_request* tm_req = set.tm_req;
+    sdsp_tempo_map* tempo_maps = set.tempo_maps;
+    if (!set_err && !ov_req && !kt_req && !lv_req && !tm_req)
         return sdsp_analyze_batch_device_ex(d_samples, offsets, lens, n_tracks, sample_rate, cfg, device, stream, stages,
                                             outs);
     auto fail_all = [&](int32_t status, const char* text) {
@@ -508,6 +574,10 @@ int32_t sdsp_analyze_batch_device_with(const float* d_samples, const uint64_t* o
                 std::memset(&levels[i], 0, sizeof(levels[i]));
                 levels[i].status = status;
             }
+            if (tm_req && tempo_maps) {
+                std::memset(&tempo_maps[i], 0, sizeof(tempo_maps[i]));
+                tempo_maps[i].status = status;
+            }
         }
         return status;
     };
@@ -519,6 +589,13 @@ int32_t sdsp_analyze_batch_device_with(const float* d_samples, const uint64_t* o
         if (!levels) return fail_all(SDSP_ERR_INVALID_INPUT, "Invalid input: levels request without a levels array");
         lc.what = lv_req->what;
         lc.out = levels;
+    }
+    TmCall tc;
+    if (tm_req) {
+        if (const char* why = tempo_map_request_error(tm_req->what, tempo_maps != nullptr, stages))
+            return fail_all(SDSP_ERR_INVALID_INPUT, why);
+        tc.what = tm_req->what;
+        tc.out = tempo_maps;
     }
     if (ov_req) {
         if (const char* why = overview_request_error(ov_req->columns, ov_req->frames_per_column, ov_req->low_max_hz,
@@ -547,12 +624,32 @@ int32_t sdsp_analyze_batch_device_with(const float* d_samples, const uint64_t* o
         return fail_all(SDSP_ERR_PROCESSING, "Processing error: no HIP device");
     try {
         return run_device(device, d_samples, offsets, lens, n_tracks, sample_rate, cfg, stream, outs, stages, nullptr,
-                          ov_req, overviews, kt_req ? &kc : nullptr, lv_req ? &lc : nullptr);
+                          ov_req, overviews, kt_req ? &kc : nullptr, lv_req ? &lc : nullptr, tm_req ? &tc : nullptr);
     } catch (const std::exception& e) {
         std::fprintf(stderr, "sdsp_analyze_batch_device_with: %s\n", e.what());
         char text[256];
         std::snprintf(text, sizeof text, "Processing error: %s", e.what());
         return fail_all(SDSP_ERR_PROCESSING, text);
+    }
+}
+
+void sdsp_tempo_map_free(sdsp_tempo_map* m) {
+    if (!m) return;
+    std::free(m->segments ? (void*)m->segments : (void*)m->onsets);  // one block (fill_tempo_map), segments first
+    m->segments = nullptr;
+    m->onsets = nullptr;
+    m->n_segments = m->n_onsets = 0;
+}
+
+int32_t sdsp_debug_last_tempo_map_times(int32_t device, sdsp_debug_tempo_map_times* out) {
+    try {
+        if (!out) return SDSP_ERR_INVALID_INPUT;
+        DeviceCtx& d = device_ctx(device);
+        std::lock_guard<std::mutex> lk(d.mu);
+        *out = d.last_tm;
+        return SDSP_OK;
+    } catch (const std::exception&) {
+        return SDSP_ERR_PROCESSING;
     }
 }
 
@@ -763,6 +860,32 @@ int32_t sdsp_debug_beat_grid(const uint32_t* onsets, const uint64_t* n_onsets, c
     return run_stage_probe("sdsp_debug_beat_grid", device, [&](DeviceCtx& d) {
         Pipeline p(d, *cfg, sample_rate, SDSP_STAGES_FULL, false, false, false, true);
         p.debug_beat_grid(onsets, n_onsets, frames, n_trim, bpm, conf, n_tracks, out);
+    });
+}
+
+int32_t sdsp_debug_tempo_map(const uint32_t* onsets, const uint64_t* n_onsets, const uint64_t* frames,
+                             const uint64_t* n_trim, const float* bpm, const float* conf, uint64_t n_tracks,
+                             uint32_t sample_rate, const sdsp_config* cfg, uint32_t what, sdsp_tempo_map* maps,
+                             sdsp_debug_beat_out* beats, int32_t device) {
+    if (!onsets || !n_onsets || !frames || !n_trim || !bpm || !conf || !cfg || !maps || n_tracks == 0 ||
+        n_tracks > (1u << 20) || sample_rate == 0 || tempo_map_request_error(what, true, SDSP_STAGES_FULL))
+        return SDSP_ERR_INVALID_INPUT;
+    if (beats && (!beats->ok || !beats->n_beats || !beats->n_down || !beats->stability || !beats->beats || !beats->downs))
+        return SDSP_ERR_INVALID_INPUT;
+    for (uint64_t t = 0; t < n_tracks; t++) {
+        if (frames[t] == 0 || frames[t] > (1u << 24) || n_trim[t] > (1ull << 40)) return SDSP_ERR_INVALID_INPUT;
+    }
+    for (uint64_t t = 0, at = 0; t < n_tracks; at += n_onsets[t], t++) {
+        if (n_onsets[t] > (1u << 26)) return SDSP_ERR_INVALID_INPUT;
+        for (uint64_t k = 1; k < n_onsets[t]; k++)
+            if (onsets[at + k] < onsets[at + k - 1]) return SDSP_ERR_INVALID_INPUT;  // ascending, as the consensus leaves them
+    }
+    for (uint64_t t = 0; t < n_tracks; t++) std::memset(&maps[t], 0, sizeof(maps[t]));
+    return run_stage_probe("sdsp_debug_tempo_map", device, [&](DeviceCtx& d) {
+        Pipeline p(d, *cfg, sample_rate, SDSP_STAGES_FULL, false, false, false, true);
+        std::vector<TrackTm> tml;
+        p.debug_tempo_map(onsets, n_onsets, frames, n_trim, bpm, conf, n_tracks, what, &tml, beats);
+        for (uint64_t t = 0; t < n_tracks; t++) fill_tempo_map(tml[(size_t)t], SDSP_OK, &maps[t]);
     });
 }
 

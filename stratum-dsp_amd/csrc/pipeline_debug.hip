@@ -584,6 +584,15 @@ void Pipeline::debug_onset_stages(const float* rms, const float* hfc, const floa
 void Pipeline::debug_beat_grid(const uint32_t* onsets, const uint64_t* n_onsets, const uint64_t* frames,
                                const uint64_t* n_trim, const float* bpm, const float* conf, uint64_t n_tracks,
                                sdsp_debug_beat_out* out) {
+    debug_tempo_map(onsets, n_onsets, frames, n_trim, bpm, conf, n_tracks, 0, nullptr, out);
+}
+
+// sdsp_debug_tempo_map: the same set-up and launches with Pipeline::tempo_map queued behind k_beat
+// and read by download_results, as the analysis call does with a tempo map request.  maps == nullptr:
+// sdsp_debug_beat_grid (no request); out == nullptr: the beat lists are not copied out.
+void Pipeline::debug_tempo_map(const uint32_t* onsets, const uint64_t* n_onsets, const uint64_t* frames,
+                               const uint64_t* n_trim, const float* bpm, const float* conf, uint64_t n_tracks,
+                               uint32_t what, std::vector<TrackTm>* maps, sdsp_debug_beat_out* out) {
     if (const std::string why = check_supported(cfg_, sr_); !why.empty()) throw HipError(why);
     const size_t T = (size_t)n_tracks;
     const uint64_t lists = hpss_on() ? 4 : 3;
@@ -611,8 +620,15 @@ void Pipeline::debug_beat_grid(const uint32_t* onsets, const uint64_t* n_onsets,
     Tempo tp;
     tp.d_fbpm = c_.up("C.fbpm", std::vector<float>(bpm, bpm + T));
     tp.d_fconf = c_.up("C.fconf", std::vector<float>(conf, conf + T));
+    if (maps) set_tempo_map(what, maps);
     const Beats bt = beat_grid(bin, bo, on, tp);
-    const ResultsHost rh = download_results(bt, bin, bo);
+    const TempoMapQ tq = tempo_map(bin, on, tp, bt);
+    const ResultsHost rh = download_results(bt, bin, bo, tq);
+    if (maps) {
+        maps->clear();
+        for (size_t t = 0; t < T; t++) maps->push_back(track_tempo_map(rh, t, bpm[t], conf[t], 0));
+    }
+    if (!out) return;
     for (size_t t = 0; t < T; t++) {
         out->ok[t] = rh.bout[t].ok;
         out->n_beats[t] = rh.bout[t].n_beats;

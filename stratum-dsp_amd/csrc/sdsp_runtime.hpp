@@ -90,6 +90,7 @@ struct DeviceCtx {
     uint64_t last_tail_reruns = 0;   // tracks the last call reran in place (Pipeline::rerun_tail)
     sdsp_debug_overview_times last_ov{};  // the last call with an overview request (Pipeline::overview)
     sdsp_debug_levels_times last_lv{};    // the last call with a levels request (Pipeline::levels_join)
+    sdsp_debug_tempo_map_times last_tm{}; // the last call with a tempo map request (Pipeline::sub_batch)
     DevBuf& buf(const std::string& name) {
         auto& b = bufs[name];
         if (!b) {

@@ -18,7 +18,8 @@ from sdsp_abi import (ERROR_NAMES, FLAG_NAMES, SdspAudioDecodeStats, SdspConfide
                       SdspDecodeStats, SdspFlacDecodeStats, SdspOverview, SdspOverviewRequest, SdspResult,
                       SdspStageTimes, OVERVIEW_ARRAYS, result_to_dict, SdspKeyChange, SdspKeySegment, SdspKeyTimeline,
                       SdspKeyTimelineRequest, SdspDebugLevelsTimes, SdspLevels, SdspLevelsRequest, SdspLoudness,
-                      SdspRequestSet, SdspSilenceRegion, LEVELS_BITS)
+                      SdspRequestSet, SdspSilenceRegion, LEVELS_BITS, SdspDebugTempoMapTimes, SdspTempoMap,
+                      SdspTempoMapRequest, SdspTempoSegment, TEMPO_MAP_BITS)
 
 PKG = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LIB_PATH = os.environ.get("SDSP_LIB_PATH") or os.path.join(PKG, "lib", "libstratum_hip.so")  # override: layout/ablation builds
@@ -90,6 +91,10 @@ def _load(path):
         L.sdsp_analyze_batch_device_with.restype = C.c_int32
         L.sdsp_levels_free.argtypes = [C.POINTER(SdspLevels)]
         L.sdsp_levels_free.restype = None
+        L.sdsp_tempo_map_free.argtypes = [C.POINTER(SdspTempoMap)]
+        L.sdsp_tempo_map_free.restype = None
+        L.sdsp_debug_last_tempo_map_times.argtypes = [C.c_int32, C.POINTER(SdspDebugTempoMapTimes)]
+        L.sdsp_debug_last_tempo_map_times.restype = C.c_int32
         L.sdsp_debug_last_levels_times.argtypes = [C.c_int32, C.POINTER(SdspDebugLevelsTimes)]
         L.sdsp_debug_last_levels_times.restype = C.c_int32
         L.sdsp_key_timeline_free.argtypes = [C.POINTER(SdspKeyTimeline)]
@@ -720,13 +725,54 @@ def levels_to_dict(l):
     return d
 
 
+TEMPO_SEGMENT_FIELDS = tuple(k for k, _ in SdspTempoSegment._fields_)
+
+
+def tempo_map_request(what=("segments", "onsets")):
+    """An sdsp_tempo_map_request: `what` is a mask of sdsp_tempo_map_what bits, or names out of
+    segments, onsets (the default asks for both)."""
+    if not isinstance(what, int):
+        mask = 0
+        for name in what:
+            mask |= TEMPO_MAP_BITS[name]
+        what = mask
+    return SdspTempoMapRequest(what)
+
+
+def tempo_map_to_dict(m):
+    """One sdsp_tempo_map: its integer fields as int, its float fields as np.float32,
+    time_signature_scores a float32 array of 3, `segments` a dict of numpy arrays, one per field of
+    TEMPO_SEGMENT_FIELDS, and `onsets` a uint32 array."""
+    d = {k: int(getattr(m, k)) for k in ("status", "has_grid", "has_variation", "refined", "time_signature_scored",
+                                         "hmm_beats", "beats_per_bar", "first_sample", "n_segments", "n_onsets")}
+    for k in ("nominal_bpm", "nominal_confidence", "time_signature_confidence"):
+        d[k] = np.float32(getattr(m, k))
+    d["time_signature_scores"] = np.array(list(m.time_signature_scores), np.float32)
+    seg = _records(m.segments, d["n_segments"], SdspTempoSegment)
+    d["segments"] = {k: seg[k].copy() for k in TEMPO_SEGMENT_FIELDS}
+    d["onsets"] = _records(m.onsets, d["n_onsets"], C.c_uint32).astype(np.uint32)
+    return d
+
+
+def tempo_map_times(device=0):
+    """sdsp_debug_last_tempo_map_times: k_tempo_map's and k_beat's event times of the last call with
+    a tempo map request on `device`."""
+    t = SdspDebugTempoMapTimes()
+    if lib().sdsp_debug_last_tempo_map_times(device, C.byref(t)) != 0:
+        raise RuntimeError("sdsp_debug_last_tempo_map_times failed")
+    return {k: getattr(t, k) for k, _ in SdspDebugTempoMapTimes._fields_}
+
+
 def analyze_batch_device_with(d_ptr, offsets, lens, sample_rate=44100, config=None, device=0, stream=None,
-                              stages=STAGES_FULL, overview=None, key_timeline=None, levels=None, request_set=True):
+                              stages=STAGES_FULL, overview=None, key_timeline=None, levels=None, request_set=True,
+                              tempo_map=None):
     """sdsp_analyze_batch_device_with: analyze_batch_device(raw=True) with any of the optional
     requests: an SdspOverviewRequest, an SdspKeyTimelineRequest, an SdspLevelsRequest
-    (levels_request()); None leaves a request out.  request_set=False passes set == NULL.  Returns
-    (ResultBatch, overviews, timelines, levels): levels[i] a levels_to_dict(); each list [] without
-    its request.  Raises AnalysisError when the call as a whole fails (a refused request)."""
+    (levels_request()), an SdspTempoMapRequest (tempo_map_request()); None leaves a request out.
+    request_set=False passes set == NULL.  Returns (ResultBatch, overviews, timelines, levels), and
+    with a tempo map request a fifth element, the tempo maps: levels[i] a levels_to_dict(), maps[i]
+    a tempo_map_to_dict(); each list [] without its request.  Raises AnalysisError when the call as
+    a whole fails (a refused request)."""
     offs = np.ascontiguousarray(offsets, dtype=np.uint64)
     ln = np.ascontiguousarray(lens, dtype=np.uint64)
     n = ln.size
@@ -734,6 +780,7 @@ def analyze_batch_device_with(d_ptr, offsets, lens, sample_rate=44100, config=No
     ovs = (SdspOverview * max(n, 1))() if overview is not None else None
     kts = (SdspKeyTimeline * max(n, 1))() if key_timeline is not None else None
     lvs = (SdspLevels * max(n, 1))() if levels is not None else None
+    tms = (SdspTempoMap * max(n, 1))() if tempo_map is not None else None
     cfg = config if config is not None else default_config()
     _schedule_from_env()
     rs = SdspRequestSet()
@@ -747,13 +794,16 @@ def analyze_batch_device_with(d_ptr, offsets, lens, sample_rate=44100, config=No
     if levels is not None:
         rs.lv_req = C.pointer(levels)
         rs.levels = lvs
+    if tempo_map is not None:
+        rs.tm_req = C.pointer(tempo_map)
+        rs.tempo_maps = tms
     u64p = C.POINTER(C.c_uint64)
     st = lib().sdsp_analyze_batch_device_with(C.c_void_p(d_ptr), offs.ctypes.data_as(u64p), ln.ctypes.data_as(u64p), n,
                                               sample_rate, C.byref(cfg), device, C.c_void_p(stream or 0), stages, outs,
                                               C.byref(rs) if request_set else None)
     if st != 0:
         raise AnalysisError(st, _batch_error(outs, n, "device batch failed"))
-    overviews, timelines, lv = [], [], []
+    overviews, timelines, lv, maps = [], [], [], []
     for i in range(n if request_set else 0):
         if ovs is not None:
             overviews.append(overview_to_dict(ovs[i]))
@@ -764,6 +814,11 @@ def analyze_batch_device_with(d_ptr, offsets, lens, sample_rate=44100, config=No
         if lvs is not None:
             lv.append(levels_to_dict(lvs[i]))
             lib().sdsp_levels_free(C.byref(lvs[i]))
+        if tms is not None:
+            maps.append(tempo_map_to_dict(tms[i]))
+            lib().sdsp_tempo_map_free(C.byref(tms[i]))
+    if tempo_map is not None:
+        return ResultBatch(outs, n), overviews, timelines, lv, maps
     return ResultBatch(outs, n), overviews, timelines, lv
 
 
@@ -1352,6 +1407,49 @@ def debug_beat_grid(tracks, sample_rate=44100, config=None, device=0):
         b0 += kb
         d0 += kd
     return out
+
+
+def debug_tempo_map(tracks, what=("segments", "onsets"), sample_rate=44100, config=None, device=0):
+    """The beat stage with the tempo map step behind it (sdsp_debug_tempo_map).  tracks: as
+    debug_beat_grid's.  Returns (maps, grids): per track a tempo_map_to_dict(), and what
+    debug_beat_grid returns, from the same launch."""
+    cfg = config if config is not None else default_config()
+    req = tempo_map_request(what)
+    T = len(tracks)
+    ons = [np.ascontiguousarray(t["onsets"], dtype=np.uint32).ravel() for t in tracks]
+    n_on = np.array([a.size for a in ons], np.uint64)
+    allon = np.ascontiguousarray(np.concatenate(ons + [np.zeros(1, np.uint32)]))
+    frames = np.array([int(t["frames"]) for t in tracks], np.uint64)
+    n_trim = np.array([int(t["n_trim"]) for t in tracks], np.uint64)
+    bpm = np.array([t["bpm"] for t in tracks], np.float32)
+    conf = np.array([t["conf"] for t in tracks], np.float32)
+    cap = sum(max(12 * (int(n) // sample_rate + 1) + 64, 3 * int(F) + 8) for n, F in zip(n_trim, frames))
+    ok, nb, nd = (np.zeros(max(T, 1), np.int32) for _ in range(3))
+    stab, beats, downs = np.zeros(max(T, 1), np.float32), np.zeros(max(cap, 1), np.float32), np.zeros(max(cap, 1), np.float32)
+    i32p, u64p = C.POINTER(C.c_int32), C.POINTER(C.c_uint64)
+    o = SdspDebugBeatOut(ok.ctypes.data_as(i32p), nb.ctypes.data_as(i32p), nd.ctypes.data_as(i32p), _fp(stab), _fp(beats),
+                         _fp(downs))
+    maps = (SdspTempoMap * max(T, 1))()
+    f = lib().sdsp_debug_tempo_map
+    fp = C.POINTER(C.c_float)
+    f.argtypes = [C.POINTER(C.c_uint32), u64p, u64p, u64p, fp, fp, C.c_uint64, C.c_uint32, C.POINTER(SdspConfig),
+                  C.c_uint32, C.POINTER(SdspTempoMap), C.POINTER(SdspDebugBeatOut), C.c_int32]
+    f.restype = C.c_int32
+    st = f(allon.ctypes.data_as(C.POINTER(C.c_uint32)), n_on.ctypes.data_as(u64p), frames.ctypes.data_as(u64p),
+           n_trim.ctypes.data_as(u64p), _fp(bpm), _fp(conf), T, sample_rate, C.byref(cfg), req.what, maps, C.byref(o),
+           device)
+    if st != 0:
+        raise AnalysisError(st, "debug_tempo_map failed")
+    out, grids, b0, d0 = [], [], 0, 0
+    for t in range(T):
+        out.append(tempo_map_to_dict(maps[t]))
+        lib().sdsp_tempo_map_free(C.byref(maps[t]))
+        kb, kd = (int(nb[t]), int(nd[t])) if ok[t] > 0 else (0, 0)
+        grids.append(dict(ok=int(ok[t]), beats=beats[b0:b0 + kb].copy(), downbeats=downs[d0:d0 + kd].copy(),
+                          stability=stab[t].copy()))
+        b0 += kb
+        d0 += kd
+    return out, grids
 
 
 def key_fft_bins(cfg):

@@ -443,6 +443,62 @@ class SdspLevels(C.Structure):
     ]
 
 
+TEMPO_MAP_SEGMENTS, TEMPO_MAP_ONSETS = 1, 2  # enum sdsp_tempo_map_what
+TEMPO_MAP_BITS = {"segments": TEMPO_MAP_SEGMENTS, "onsets": TEMPO_MAP_ONSETS}
+
+
+class SdspTempoMapRequest(C.Structure):
+    """sdsp_tempo_map_request: `what` is a mask of sdsp_tempo_map_what bits."""
+
+    _fields_ = [("what", u32)]
+
+
+class SdspTempoSegment(C.Structure):
+    """sdsp_tempo_segment: one TempoSegment and what the Bayesian refinement did with it."""
+
+    _fields_ = [
+        ("start_time", f32),
+        ("end_time", f32),
+        ("bpm", f32),
+        ("confidence", f32),
+        ("is_variable", C.c_uint8),
+        ("updated", C.c_uint8),
+        ("n_onsets", u32),
+        ("updated_bpm", f32),
+        ("updated_confidence", f32),
+        ("n_beats", u32),
+    ]
+
+
+class SdspTempoMap(C.Structure):
+    """sdsp_tempo_map: one track's tempo segments, time signature and consensus onsets (library-owned)."""
+
+    _fields_ = [
+        ("status", C.c_int32),
+        ("has_grid", C.c_int8),
+        ("has_variation", C.c_int8),
+        ("refined", C.c_int8),
+        ("time_signature_scored", C.c_int8),
+        ("nominal_bpm", f32),
+        ("nominal_confidence", f32),
+        ("hmm_beats", u32),
+        ("beats_per_bar", u32),
+        ("time_signature_confidence", f32),
+        ("time_signature_scores", f32 * 3),
+        ("first_sample", u64),
+        ("n_segments", u64),
+        ("segments", C.POINTER(SdspTempoSegment)),
+        ("n_onsets", u64),
+        ("onsets", C.POINTER(u32)),
+    ]
+
+
+class SdspDebugTempoMapTimes(C.Structure):
+    """sdsp_debug_tempo_map_times (include/stratum_hip_debug.h)."""
+
+    _fields_ = [("map_ms", C.c_double), ("beat_ms", C.c_double), ("tracks", u64)]
+
+
 class SdspRequestSet(C.Structure):
     """sdsp_request_set: the optional requests of sdsp_analyze_batch_device_with, by name."""
 
@@ -454,6 +510,8 @@ class SdspRequestSet(C.Structure):
         ("timelines", C.POINTER(SdspKeyTimeline)),
         ("lv_req", C.POINTER(SdspLevelsRequest)),
         ("levels", C.POINTER(SdspLevels)),
+        ("tm_req", C.POINTER(SdspTempoMapRequest)),
+        ("tempo_maps", C.POINTER(SdspTempoMap)),
     ]
 
 
