@@ -631,6 +631,86 @@ typedef struct sdsp_tempo_map {
 } sdsp_tempo_map;
 
 /*
+ * Sections: structural boundaries of a track and the energy of each part, a self-distance novelty
+ * (Foote's checkerboard) over short cells of the smoothed chroma rows and the base tempo pass's
+ * frame energies, both resident during the analysis call.  The reference has no counterpart; this
+ * definition is the contract.
+ *
+ * What the numbers are: a novelty of chroma change and energy change at cell resolution.  It is not
+ * a phrase or bar estimate, and energy_weight is the caller's trade between the two kinds of change
+ * (0: chroma alone).  Non-finite input samples are out of scope.
+ *
+ * Scope: a track whose key path runs (SDSP_STAGES_FULL, trimmed length n >= frame_size and n >= the
+ * key STFT's frame size).  Inputs:
+ *   kfs, khop  the key STFT's frame and hop; F = (n - kfs) / khop + 1 key frames with the rows
+ *              C[f][0..12) exactly as sdsp_key_timeline defines them
+ *   frame_size, hop_size  the base tempo pass; Fb = (n - frame_size) / hop_size + 1 frames with the
+ *              energies E[f] = the f32 sum over bins ascending of mag * mag (novelty.rs:511-515)
+ * Every sum below is f32, starts from 0 and runs in ascending index order; multiply and add are
+ * separate operations; division is IEEE f32.
+ * Cells: Cs = cell_samples, or (u64)(cell_seconds * (f32)sample_rate); exactly one of the two is
+ *   given (a form is given when its field is not 0).  Cs >= max(khop, hop_size).
+ *   n_cells = min(F * khop, Fb * hop_size) / Cs (integer division).  Cell c owns the key frames whose
+ *   start f * khop lies in [c Cs, (c + 1) Cs), and likewise the base frames by f * hop_size: integer
+ *   arithmetic only, and every cell owns at least one frame of each kind.
+ * Cell features:
+ *   m[c][i] = (sum over the cell's key frames of C[f][i]) / (f32)count
+ *   g[c]    = (sum over the cell's base frames of E[f]) / (f32)count
+ *   gmax = max over c of g[c];  e[c] = gmax > 0 ? g[c] / gmax : 0
+ * Distance: D(a, b) = sum over i = 0..11 of (m[a][i] - m[b][i])^2, then + energy_weight * (e[a] - e[b])^2
+ * Novelty, with K = kernel_cells (1 <= K <= 64), for c in [K, n_cells - K]:
+ *   cross = sum over a = c-K..c-1 (outer), b = c..c+K-1 (inner) of D(a, b)
+ *   wp    = sum over a = c-K..c-1, b = a+1..c-1 of D(a, b);  wf the same over [c, c + K)
+ *   N[c]  = cross / (f32)(K K) - (K > 1 ? (wp + wf) / (f32)(K (K - 1)) : 0);  N[c] = 0 for every other c
+ * Boundaries, with G = min_gap_cells and Nmax = max over c of N[c]: cell c is a boundary when
+ *   N[c] > 0, N[c] >= min_strength * Nmax, N[c] > N[j] for every valid j in [c - G, c) and
+ *   N[c] >= N[j] for every valid j in (c, c + G]: the first of two equal peaks wins.
+ * Sections: the runs of cells between boundaries, n_boundaries + 1 of them covering [0, n_cells)
+ *   (none when n_cells is 0).  start_time = (f32)(start_cell * Cs) / (f32)sample_rate on the time axis of
+ *   the result's beats (0 = first_sample), end_time alike; strength = N at start_cell (0 for the
+ *   first section); mean_energy = (sum of g[c] over its cells) / (f32)count; relative_energy =
+ *   mean_energy / the largest section mean_energy (0 when that is 0).  downbeat is the index of the
+ *   result's downbeat nearest to start_time (|downbeats[j] - start_time| in f32, the first on a tie)
+ *   if that distance is <= snap_seconds, and snapped_time that downbeat; otherwise downbeat = -1 and
+ *   snapped_time = start_time.
+ * SDSP_SECTIONS_LIST asks for the sections, SDSP_SECTIONS_CURVE for N[c] and g[c] per cell (n_* = 0 and
+ * NULL when not asked for).  n_cells, cell_samples, first_sample, gmax, nmax and status are always filled.
+ *
+ * Per track: an analysis status other than SDSP_OK gives that status and zeroed fields (cell_samples
+ * aside); a track whose key path is skipped gives n_cells 0 and leaves the status alone;
+ * n_cells < 2 K gives one section and no boundary.
+ */
+enum sdsp_sections_what { SDSP_SECTIONS_LIST = 1, SDSP_SECTIONS_CURVE = 2 }; /* bits of sdsp_sections_request.what */
+typedef struct sdsp_sections_request {
+    uint32_t what;
+    float cell_seconds;     /* the seconds form of Cs */
+    uint64_t cell_samples;  /* the samples form of Cs */
+    uint32_t kernel_cells;  /* K */
+    uint32_t min_gap_cells; /* G */
+    float energy_weight, min_strength, snap_seconds;
+} sdsp_sections_request;
+
+typedef struct sdsp_section {
+    uint64_t start_cell, end_cell; /* cells [start_cell, end_cell) */
+    float start_time, end_time;
+    float strength, mean_energy, relative_energy;
+    float snapped_time;
+    int32_t downbeat;              /* index into the result's downbeats, or -1 */
+} sdsp_section;
+
+typedef struct sdsp_sections {
+    int32_t status;         /* the track's sdsp_status */
+    uint64_t n_cells, cell_samples;
+    uint64_t first_sample;  /* trim start in the caller's track, as in sdsp_overview */
+    float gmax, nmax;
+    uint64_t n_sections;
+    sdsp_section* sections; /* library-owned, one allocation with the curves */
+    uint64_t n_curve;       /* n_cells with SDSP_SECTIONS_CURVE, else 0 */
+    float* novelty;         /* N[c] */
+    float* energy;          /* g[c] */
+} sdsp_sections;
+
+/*
  * The optional requests of one analysis call, by name: a later request is a new pair of fields at
  * the end, and a caller built against an older header (a smaller struct_size) keeps working.
  */
@@ -641,6 +721,19 @@ typedef struct sdsp_request_set {
     const sdsp_levels_request* lv_req;       sdsp_levels* levels;
     const sdsp_tempo_map_request* tm_req;    sdsp_tempo_map* tempo_maps;
 } sdsp_request_set;
+
+/*
+ * The request set with the pairs added after the tempo map.  sdsp_request_set itself stays at its
+ * four pairs (its size and last pair are pinned by the layout checks of callers built against it);
+ * this struct begins with it, so in memory the fifth pair lies right at its end, and a later request
+ * is a new pair at the end of this one.  Pass &ext.base with ext.base.struct_size = sizeof(ext): the
+ * library reads sc_req / sections only when struct_size covers them, so a caller that passes a plain
+ * sdsp_request_set (a smaller struct_size) keeps working.
+ */
+typedef struct sdsp_request_set_ext {
+    sdsp_request_set base;
+    const sdsp_sections_request* sc_req;     sdsp_sections* sections;
+} sdsp_request_set_ext;
 
 /*
  * sdsp_analyze_batch_device_ex with any of the optional requests from one analysis: overviews and
@@ -654,6 +747,12 @@ typedef struct sdsp_request_set {
  * Tempo maps (n_tracks entries, freed one by one with sdsp_tempo_map_free) as above; also refused:
  * a tempo map request with what == 0 or unknown bits, or with SDSP_STAGES_BPM_ONLY, which has no
  * beat stage.  The nested exact key reruns never see a request.
+ * Sections (sdsp_request_set_ext: n_tracks entries, freed one by one with sdsp_sections_free) as above.  Also refused with
+ * SDSP_ERR_INVALID_INPUT: both cell forms or neither; a float that is not finite or is negative;
+ * what == 0 or unknown bits; K == 0 or K > 64; G >= 2^31; Cs < max(khop, hop_size) or Cs >= 2^31; no
+ * output array; SDSP_STAGES_BPM_ONLY.  With SDSP_ERR_NOT_IMPLEMENTED: force_legacy_bpm (no feature
+ * pass, so no E), and enable_key_beat_synchronous without enable_key_log_frequency (the rows are
+ * beats, as for the key timeline).
  */
 int32_t sdsp_analyze_batch_device_with(const float* d_samples, const uint64_t* offsets, const uint64_t* lens,
                                        uint64_t n_tracks, uint32_t sample_rate, const sdsp_config* cfg,
@@ -663,6 +762,8 @@ int32_t sdsp_analyze_batch_device_with(const float* d_samples, const uint64_t* o
 void sdsp_levels_free(sdsp_levels* l);
 /* Frees the arrays owned by one tempo map (they share one allocation: never free() them one by one). */
 void sdsp_tempo_map_free(sdsp_tempo_map* m);
+/* Frees the arrays owned by one sdsp_sections (they share one allocation: never free() them one by one). */
+void sdsp_sections_free(sdsp_sections* s);
 
 /*
  * Synthetic track generator on device: writes n_tracks tracks of `len`

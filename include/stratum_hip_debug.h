@@ -310,6 +310,41 @@ typedef struct sdsp_debug_tempo_map_times {
 int32_t sdsp_debug_last_tempo_map_times(int32_t device, sdsp_debug_tempo_map_times* out);
 
 /*
+ * Stage probe of the sections request (include/stratum_hip.h, sdsp_sections): the four kernels of
+ * k_sections.hip over uploaded rows and energies, taken as the rows C and the energies E of the
+ * definition.  host_chroma: the tracks' rows back to back, frames[t] rows of 12 floats for track t,
+ * khop samples apart; host_energy: base_frames[t] energies for track t, hop samples apart (0 frames
+ * allowed for either).  req is checked as an analysis call checks it against khop and hop.  Track t
+ * has n_cells[t] = min(frames[t] khop, base_frames[t] hop) / Cs cells; with P the prefix of n_cells,
+ * out->m receives m[c][0..12) at 12 (P[t] + c), out->g, out->novelty and out->boundary their values at
+ * P[t] + c.  The caller sizes the arrays from the same plan; cell_capacity is their length in cells,
+ * and a call that needs more is refused.  SDSP_ERR_INVALID_INPUT for a refused request.
+ */
+typedef struct sdsp_debug_sections_out {
+    uint64_t cell_capacity;
+    uint64_t* n_cells; /* n_tracks */
+    float* m;          /* 12 x cell_capacity */
+    float* g;
+    float* novelty;
+    uint8_t* boundary;
+} sdsp_debug_sections_out;
+int32_t sdsp_debug_sections(const float* host_chroma, const uint64_t* frames, const float* host_energy,
+                            const uint64_t* base_frames, uint64_t n_tracks, uint32_t sample_rate, uint32_t khop,
+                            uint32_t hop, const sdsp_sections_request* req, sdsp_debug_sections_out* out, int32_t device);
+
+/*
+ * The sections step of the last sdsp_analyze_batch_device_with call with a sections request on
+ * `device`, summed over its sub-batches: HIP event times of k_section_energy (main stream),
+ * k_section_chroma and k_section_novelty with k_section_pick (vote stream), and the cells folded.
+ * All zero after a call without a request.
+ */
+typedef struct sdsp_debug_sections_times {
+    double energy_ms, chroma_ms, novelty_ms;
+    uint64_t cells;
+} sdsp_debug_sections_times;
+int32_t sdsp_debug_last_sections_times(int32_t device, sdsp_debug_sections_times* out);
+
+/*
  * Stage probe of the candidate selection: the pipeline's own select launch (k_tempo_select with the
  * parameters an analysis call derives from cfg: Pipeline::pass_select from its offset tables on) over
  * uploaded tempogram lists instead of a novelty curve.  Per track t and variant v (full, low, mid,

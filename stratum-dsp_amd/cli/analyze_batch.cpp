@@ -35,9 +35,14 @@
 // (include/stratum_hip.h, sdsp_tempo_map): the tempo segments with what the Bayesian refinement did in
 // each, the time signature with its three scores, and the consensus onsets (LIST out of
 // segments,onsets; both without a list).  It combines with the other three in one analysis.
+// --sections[=CELL_SEC[:K[:GAP[:EWEIGHT[:MINSTRENGTH]]]]] (opt-in; JSONL only): each line's object gets a
+// "sections" member (include/stratum_hip.h, sdsp_sections): the sections between the structural
+// boundaries with their energies, each start snapped to a downbeat within one cell, and the novelty
+// and energy curves per cell.  Defaults 0.5 s, K 16, GAP 8, EWEIGHT 1, MINSTRENGTH 0.5.
 //
 //   analyze_batch [--jobs N] [--devices MASK] [--json] [--gpu-decode] [--overview N | --overview-frames K]
-//                 [--key-timeline SEC[:OVERLAP[:MINCONF]]] [--levels [LIST]] [--tempo-map[=LIST]] <file1> <file2> ...
+//                 [--key-timeline SEC[:OVERLAP[:MINCONF]]] [--levels [LIST]] [--tempo-map[=LIST]]
+//                 [--sections[=CELL_SEC[:K[:GAP[:EWEIGHT[:MINSTRENGTH]]]]]] <file1> <file2> ...
 #include <algorithm>
 #include <atomic>
 #include <chrono>
@@ -67,6 +72,7 @@ struct Item {
     std::string timeline;  // --key-timeline: the "key_timeline" member's value
     std::string levels;    // --levels: the "levels" member's value
     std::string tempo_map; // --tempo-map: the "tempo_map" member's value
+    std::string sections;  // --sections: the "sections" member's value
 };
 
 // floats so that an f32 round-trips
@@ -198,6 +204,36 @@ std::string tempo_map_json(const sdsp_tempo_map& m) {
     return s + "]}";
 }
 
+std::string sections_json(const sdsp_sections& m) {
+    char b[512];
+    std::snprintf(b, sizeof b,
+                  "{\"status\":%d,\"n_cells\":%llu,\"cell_samples\":%llu,\"first_sample\":%llu,\"gmax\":%.9g,"
+                  "\"nmax\":%.9g",
+                  m.status, (unsigned long long)m.n_cells, (unsigned long long)m.cell_samples,
+                  (unsigned long long)m.first_sample, (double)m.gmax, (double)m.nmax);
+    std::string s = b;
+    // a section: [start_cell, end_cell, start_time, end_time, strength, mean_energy, relative_energy, snapped_time, downbeat]
+    s += ",\"n_sections\":" + std::to_string((unsigned long long)m.n_sections) + ",\"sections\":[";
+    for (uint64_t i = 0; i < m.n_sections; i++) {
+        const sdsp_section& e = m.sections[i];
+        std::snprintf(b, sizeof b, "%s[%llu,%llu,%.9g,%.9g,%.9g,%.9g,%.9g,%.9g,%d]", i ? "," : "",
+                      (unsigned long long)e.start_cell, (unsigned long long)e.end_cell, (double)e.start_time,
+                      (double)e.end_time, (double)e.strength, (double)e.mean_energy, (double)e.relative_energy,
+                      (double)e.snapped_time, e.downbeat);
+        s += b;
+    }
+    s += "],\"n_curve\":" + std::to_string((unsigned long long)m.n_curve);
+    for (int k = 0; k < 2; k++) {
+        s += k ? "],\"energy\":[" : ",\"novelty\":[";
+        const float* v = k ? m.energy : m.novelty;
+        for (uint64_t i = 0; i < m.n_curve; i++) {
+            std::snprintf(b, sizeof b, i ? ",%.9g" : "%.9g", (double)v[i]);
+            s += b;
+        }
+    }
+    return s + "]}";
+}
+
 // percentile as the example computes it: sort, index round((len-1) * p)
 float percentile(std::vector<float> xs, float p) {
     std::sort(xs.begin(), xs.end());
@@ -281,6 +317,14 @@ int main(int argc, char** argv) {
     bool levels = false;
     sdsp_tempo_map_request tmreq{SDSP_TEMPO_MAP_SEGMENTS | SDSP_TEMPO_MAP_ONSETS};
     bool tempo_map = false;
+    sdsp_sections_request screq{};
+    screq.what = SDSP_SECTIONS_LIST | SDSP_SECTIONS_CURVE;
+    screq.cell_seconds = 0.5f;
+    screq.kernel_cells = 16;
+    screq.min_gap_cells = 8;
+    screq.energy_weight = 1.0f;
+    screq.min_strength = 0.5f;
+    bool sections = false;
     std::vector<std::string> paths;
     for (size_t i = 0; i < a.size(); i++) {
         const std::string& s = a[i];
@@ -376,10 +420,42 @@ int main(int argc, char** argv) {
                 }
                 tmreq.what = what;
             }
+        } else if (s == "--sections" || s.rfind("--sections=", 0) == 0) {
+            sections = true;
+            if (s.size() > 10) {  // =CELL_SEC[:K[:GAP[:EWEIGHT[:MINSTRENGTH]]]]
+                const std::string w = s.substr(11);
+                double v[5] = {0.5, 16, 8, 1.0, 0.5};
+                int n = 0;
+                bool good = !w.empty();
+                for (size_t p0 = 0; good;) {
+                    const size_t p1 = std::min(w.find(':', p0), w.size());
+                    char* end = nullptr;
+                    const std::string part = w.substr(p0, p1 - p0);
+                    good = n < 5 && !part.empty();
+                    if (good) v[n] = std::strtod(part.c_str(), &end), good = end && *end == 0;
+                    n++;
+                    if (p1 == w.size()) break;
+                    p0 = p1 + 1;
+                }
+                if (!good || !(v[0] > 0.0) || !(v[1] >= 1.0 && v[1] <= 64.0) || v[1] != (double)(uint32_t)v[1] ||
+                    !(v[2] >= 0.0 && v[2] < 2147483648.0) || v[2] != (double)(uint32_t)v[2] || !(v[3] >= 0.0) || !(v[4] >= 0.0)) {
+                    std::fprintf(stderr,
+                                 "Error: --sections takes CELL_SEC[:K[:GAP[:EWEIGHT[:MINSTRENGTH]]]] with CELL_SEC > 0, K in "
+                                 "[1, 64], whole GAP >= 0, EWEIGHT and MINSTRENGTH >= 0\n");
+                    return 1;
+                }
+                screq.cell_seconds = (float)v[0];
+                screq.kernel_cells = (uint32_t)v[1];
+                screq.min_gap_cells = (uint32_t)v[2];
+                screq.energy_weight = (float)v[3];
+                screq.min_strength = (float)v[4];
+            }
+            screq.snap_seconds = screq.cell_seconds;
         } else if (s == "--help" || s == "-h") {
             std::fprintf(stderr,
                          "Usage: analyze_batch [--jobs N] [--devices MASK] [--json] [--gpu-decode] [--overview N | "
-                         "--overview-frames K] [--key-timeline SEC[:OVERLAP[:MINCONF]]] [--levels [LIST]] [--tempo-map[=LIST]] <file1> <file2> ...\n\n"
+                         "--overview-frames K] [--key-timeline SEC[:OVERLAP[:MINCONF]]] [--levels [LIST]] [--tempo-map[=LIST]] "
+                         "[--sections[=CELL_SEC[:K[:GAP[:EWEIGHT[:MINSTRENGTH]]]]]] <file1> <file2> ...\n\n"
                          "--jobs N        Decode workers (default: CPU-1)\n"
                          "--devices MASK  GPU bitmask (default: all visible GPUs)\n"
                          "--json          Emit one JSON object per line (JSONL)\n"
@@ -392,7 +468,10 @@ int main(int argc, char** argv) {
                          "--levels [LIST] With --json: add each track's loudness metadata and silence regions (\"levels\");\n"
                          "                LIST out of peak,rms,loudness,silence (default: all four)\n"
                          "--tempo-map[=LIST]  With --json: add each track's tempo segments, time signature and consensus\n"
-                         "                onsets (\"tempo_map\"); LIST out of segments,onsets (default: both)\n");
+                         "                onsets (\"tempo_map\"); LIST out of segments,onsets (default: both)\n"
+                         "--sections[=CELL_SEC[:K[:GAP[:EWEIGHT[:MINSTRENGTH]]]]]  With --json: add each track's sections between\n"
+                         "                structural boundaries with their energies, and the novelty and energy curves\n"
+                         "                (\"sections\"); defaults 0.5:16:8:1:0.5, starts snapped to downbeats within a cell\n");
             return 0;
         } else {
             paths.push_back(s);
@@ -406,6 +485,7 @@ int main(int argc, char** argv) {
     if (timeline && !json) std::fprintf(stderr, "Note: --key-timeline adds to the --json lines only\n");
     if (levels && !json) std::fprintf(stderr, "Note: --levels adds to the --json lines only\n");
     if (tempo_map && !json) std::fprintf(stderr, "Note: --tempo-map adds to the --json lines only\n");
+    if (sections && !json) std::fprintf(stderr, "Note: --sections adds to the --json lines only\n");
     if (paths.empty()) {
         std::fprintf(stderr, "ERROR: Provide at least one audio file path. Use --help for usage.\n");
         return 2;
@@ -461,11 +541,12 @@ int main(int argc, char** argv) {
     sdsp_config_default(&cfg);
     auto take = [](Item& it, const sdsp_result& r, const sdsp_overview* ov = nullptr,
                    const sdsp_key_timeline* kt = nullptr, const sdsp_levels* lv = nullptr,
-                   const sdsp_tempo_map* tm = nullptr) {
+                   const sdsp_tempo_map* tm = nullptr, const sdsp_sections* sc = nullptr) {
         if (ov) it.overview = overview_json(*ov);
         if (kt) it.timeline = key_timeline_json(*kt);
         if (lv) it.levels = levels_json(*lv);
         if (tm) it.tempo_map = tempo_map_json(*tm);
+        if (sc) it.sections = sections_json(*sc);
         if (r.status != 0) {
             it.error = std::string("analysis failed: ") + r.error_message;
             return;
@@ -490,7 +571,8 @@ int main(int argc, char** argv) {
         std::vector<sdsp_key_timeline> kts;
         std::vector<sdsp_levels> lvs;
         std::vector<sdsp_tempo_map> tms;
-        sdsp_request_set set{};
+        std::vector<sdsp_sections> scs;
+        sdsp_request_set_ext ext{};
     };
     auto requests = [&](size_t n) {
         Requests q;
@@ -498,23 +580,27 @@ int main(int argc, char** argv) {
         q.kts.resize(timeline ? n : 0);
         q.lvs.resize(levels ? n : 0);
         q.tms.resize(tempo_map ? n : 0);
+        q.scs.resize(sections ? n : 0);
         return q;
     };
     auto request_set = [&](Requests& q) {
-        q.set.struct_size = (uint32_t)sizeof(q.set);
-        if (overview) q.set.ov_req = &ovreq, q.set.overviews = q.ovs.data();
-        if (timeline) q.set.kt_req = &ktreq, q.set.timelines = q.kts.data();
-        if (levels) q.set.lv_req = &lvreq, q.set.levels = q.lvs.data();
-        if (tempo_map) q.set.tm_req = &tmreq, q.set.tempo_maps = q.tms.data();
-        return &q.set;
+        sdsp_request_set& set = q.ext.base;
+        set.struct_size = (uint32_t)sizeof(q.ext);
+        if (overview) set.ov_req = &ovreq, set.overviews = q.ovs.data();
+        if (timeline) set.kt_req = &ktreq, set.timelines = q.kts.data();
+        if (levels) set.lv_req = &lvreq, set.levels = q.lvs.data();
+        if (tempo_map) set.tm_req = &tmreq, set.tempo_maps = q.tms.data();
+        if (sections) q.ext.sc_req = &screq, q.ext.sections = q.scs.data();
+        return &set;
     };
     auto take_requests = [&](Item& it, const sdsp_result& r, Requests& q, size_t j) {
         take(it, r, overview ? &q.ovs[j] : nullptr, timeline ? &q.kts[j] : nullptr, levels ? &q.lvs[j] : nullptr,
-             tempo_map ? &q.tms[j] : nullptr);
+             tempo_map ? &q.tms[j] : nullptr, sections ? &q.scs[j] : nullptr);
         if (overview) sdsp_overview_free(&q.ovs[j]);
         if (timeline) sdsp_key_timeline_free(&q.kts[j]);
         if (levels) sdsp_levels_free(&q.lvs[j]);
         if (tempo_map) sdsp_tempo_map_free(&q.tms[j]);
+        if (sections) sdsp_sections_free(&q.scs[j]);
     };
 
     if (gpu_decode) {
@@ -597,7 +683,7 @@ int main(int argc, char** argv) {
             ptrs.push_back(items[i].samples.data());
             lens.push_back(items[i].samples.size());
         }
-        if (overview || timeline || levels || tempo_map) {
+        if (overview || timeline || levels || tempo_map || sections) {
             // the requests entry reads device-resident tracks: upload each group to the first device of
             // the mask in parts of at most 512 tracks or 2 Gi samples
             int dev = 0;
@@ -672,6 +758,10 @@ int main(int argc, char** argv) {
             if (!o.tempo_map.empty()) {
                 std::fputs(",\"tempo_map\":", stdout);
                 std::fputs(o.tempo_map.c_str(), stdout);
+            }
+            if (!o.sections.empty()) {
+                std::fputs(",\"sections\":", stdout);
+                std::fputs(o.sections.c_str(), stdout);
             }
             std::fputs("}\n", stdout);
         } else {

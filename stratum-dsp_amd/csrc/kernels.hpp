@@ -465,4 +465,17 @@ struct KtSeg {
 void launch_key_timeline(const float* chroma_s, const uint64_t* frame_pfx, const uint64_t* seg_pfx, int n_tracks,
                          uint64_t n_segs, uint32_t L, uint32_t H, const float* tmpl, KtSeg* out, hipStream_t st);
 
+// ---- k_sections: the sections request (sections_core.hpp has the arithmetic) ----
+// Cells of all tracks back to back: track t's at cell_pfx[t], sc_cells(...) of them; tile_pfx counts
+// its 64-cell tiles.  g[u]: the mean of E[row0[t] + f] over cell u's base frames (hop apart).
+void launch_section_energy(const float* E, const uint64_t* row0, const uint64_t* cell_pfx, int n_tracks, uint64_t n_cells,
+                           uint64_t Cs, uint64_t hop, float* g, hipStream_t st);
+// m[12 u + i]: the mean of chroma_s row f's class i over cell u's key frames (khop apart)
+void launch_section_chroma(const float* chroma_s, const uint64_t* frame_pfx, const uint64_t* cell_pfx, int n_tracks,
+                           uint64_t n_cells, uint64_t Cs, uint64_t khop, float* m, hipStream_t st);
+// N[u] (k_section_novelty), then the boundary flag of every cell (k_section_pick)
+void launch_section_novelty(const float* m, const float* g, const uint64_t* cell_pfx, const uint64_t* tile_pfx,
+                            int n_tracks, uint64_t n_tiles, int K, float w, uint64_t G, float min_strength, float* N,
+                            uint8_t* boundary, hipStream_t st);
+
 }  // namespace sdsp

@@ -9,6 +9,8 @@
 //   B  tempo_pass (pipeline_tempo.hip): STFT 2048/512 (frame_size / hop_size); frame features;
 //      novelty (5 variants); FFT + ACF tempograms; candidate scoring + gate
 //                                                        -> host reads estimates (sync 2)
+//      (with a sections request: section_novelty, pipeline_key.hip, the cell energies behind the
+//      pass and the novelty on the vote stream behind them)
 //      hpss, onsets: energy RMS + energy-flux onsets; spectral/HFC (/HPSS) onsets; consensus
 //   C  seed_tempo, escalate for ambiguous tracks: STFT 2048/256 and 2048/1024 of those tracks, the
 //      same feature/novelty/tempogram/scoring kernels, then multi-resolution fusion;
@@ -67,6 +69,7 @@ void Pipeline::run(const float* d_samples, const std::vector<uint64_t>& in_off, 
     if (kt_out_) kt_out_->assign(T, TrackKt{});
     if (lv_out_) lv_out_->assign(T, TrackLv{});
     if (tm_out_) tm_out_->assign(T, TrackTm{});
+    if (sc_out_) sc_out_->assign(T, TrackSc{});
     const std::string why = check_supported(cfg_, sr_);
     for (size_t i = 0; i < T; i++) {
         if (n_raw[i] == 0) {
@@ -132,6 +135,8 @@ void Pipeline::run(const float* d_samples, const std::vector<uint64_t>& in_off, 
         }
         if (tm_out_ && !bpm_only_)  // the segment lists and the gathered onsets (a few per second)
             need[i] += (double)tm_segment_capacity((uint64_t)n, sr_) * sizeof(TmSeg) + n / std::max<uint32_t>(sr_, 1) * 16.0 * 4.0;
+        if (sc_out_ && !bpm_only_)  // both parities' cell means, novelty and flags
+            need[i] += (n / (double)sc_Cs_ + 1.0) * 2.0 * (12.0 * 4.0 + 4.0 + 4.0 + 1.0);
         total_need += need[i];
     }
     const double parts = std::max(1.0, std::ceil(total_need / budget));
@@ -227,6 +232,7 @@ void Pipeline::sub_batch(const float* d_samples, const std::vector<uint64_t>& in
     TempoPassOut bo;
     tempo_pass("B.", bin, bo);
     add_pass_times(bo);
+    section_novelty(kl, bo);  // (nothing without a request)
     tm.mark(2);
     const Overview ov = overview(d_samples, bin, bo, tm);  // (nothing without a request)
     const std::vector<TempoEst> best = c_.down(bo.est, (size_t)NR);

@@ -23,6 +23,7 @@
 #include "../../include/stratum_hip_debug.h"
 #include "kernels.hpp"
 #include "levels_core.hpp"
+#include "sections_core.hpp"
 #include "tempo_map_core.hpp"
 #include "sdsp_runtime.hpp"
 
@@ -335,6 +336,17 @@ struct KeyTimelineOut {
     std::vector<uint64_t> frames;   // F of each key track
     KtSeg* d_out = nullptr;
 };
+// The sections request's buffers of a sub-batch's key tracks: the cell means queued behind the vote
+// (Pipeline::launch_key) and behind the base pass's features, the novelty and the boundary flags
+// behind both (Pipeline::section_novelty); nothing is queued without a request.  All per-parity
+// buffers, like the key timeline's: the late join reads them after the next sub-batch has launched.
+struct SectionsOut {
+    std::vector<uint64_t> cpfx{0}, tpfx{0};  // cell and 64-cell tile prefix over the key tracks
+    uint64_t *d_cpfx = nullptr, *d_tpfx = nullptr;
+    float *d_m = nullptr, *d_g = nullptr, *d_N = nullptr;
+    uint8_t* d_b = nullptr;
+    bool queued = false;  // the novelty is queued: the joins wait for ev[13], not ev[2]
+};
 // Late key join: a sub-batch's key results are read after the next sub-batch's tempo path is
 // queued, so the key stream's tail (mask, HPCP, vote) runs beside that tempo path instead of
 // holding the main stream back.  Uploads read by the key stream and the key output live in
@@ -344,6 +356,7 @@ struct KeyPending {
     std::unique_ptr<Timers> kt;
     KeyOut* d_kout = nullptr;
     KeyTimelineOut ktl;
+    SectionsOut sc;
     std::vector<size_t> at;  // result slot of each key track
     std::vector<uint64_t> first;  // its trim start in the caller's track (the key timeline's first_sample)
     KeyTail tail;
@@ -379,6 +392,7 @@ struct KeyLaunch {
     KeyOut* d_kout = nullptr;
     KeyDbg* d_kdbg = nullptr;
     KeyTimelineOut ktl;
+    SectionsOut sc;
     // the key spectrogram, frame prefix, templates and vote parameters; with tail.ok the band
     // path's state for rerun_tail
     KeyTail tail;
@@ -485,6 +499,14 @@ struct TrackLv {
     uint64_t n = 0, ts = 0, te = 0;
     std::vector<uint64_t> regions;  // (start, end) sample pairs, ascending
 };
+// One track's sections on the host: the cell energies, the novelty and the boundary flags as the
+// kernels wrote them; `on` marks a track whose key path ran.
+struct TrackSc {
+    bool on = false;
+    uint64_t first = 0;
+    std::vector<float> g, N;
+    std::vector<uint8_t> b;
+};
 // One track's tempo map on the host (sdsp_tempo_map without its status).  `on`: the track reached
 // the beat stage.
 struct TrackTm {
@@ -570,6 +592,15 @@ class Pipeline {
         tm_out_ = out;
     }
 
+    // Before run(): also compute every track's sections (include/stratum_hip.h, sdsp_sections; the
+    // request checked by sections_request_error, Cs its cell) into *out, one entry per track of the
+    // call.  A pipeline without a request queues nothing for it; nested pipelines get none.
+    void set_sections(const sdsp_sections_request& req, uint64_t Cs, std::vector<TrackSc>* out) {
+        sc_req_ = req;
+        sc_Cs_ = Cs;
+        sc_out_ = out;
+    }
+
    private:
     Ctx c_;
     DeviceCtx& d_;
@@ -612,6 +643,9 @@ class Pipeline {
     LevelsPending lv_pending_;
     uint32_t tm_what_ = 0;
     std::vector<TrackTm>* tm_out_ = nullptr;  // the call's tempo maps (set_tempo_map), else nullptr
+    sdsp_sections_request sc_req_{};
+    uint64_t sc_Cs_ = 0;
+    std::vector<TrackSc>* sc_out_ = nullptr;  // the call's sections (set_sections), else nullptr
     bool map_on() const { return lv_out_ && (lv_what_ & SDSP_LEVELS_SILENCE_MAP); }
 
     // force_legacy_bpm skips the tempogram estimate (src/lib.rs:337): no escalation, no
@@ -674,6 +708,9 @@ class Pipeline {
     KeyCond key_condition(const std::string& EP, float* mags8, const std::vector<uint64_t>& kpfx,
                           const std::vector<uint64_t>& ktile, uint64_t* d_kpfx, uint64_t* d_ktile, int* d_kid,
                           hipStream_t st2, Timers& kt);
+    void section_novelty(KeyLaunch& kl, const TempoPassOut& bo);
+    void sections_results(const SectionsOut& sc, Timers& kt, const std::vector<size_t>& at,
+                          const std::vector<uint64_t>& first);
     void key_timeline_results(const KeyTimelineOut& ktl, const std::vector<size_t>& at, const std::vector<uint64_t>& first);
     void join_key_only(KeyLaunch& kl, const Front& f, std::vector<TrackRes>& res);
     std::vector<KeyOut> join_key(const float* d_samples, const std::vector<uint64_t>& in_off,

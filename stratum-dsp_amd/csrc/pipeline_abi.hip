@@ -10,6 +10,7 @@
 #include "key_timeline_plan.hpp"
 #include "overview_plan.hpp"
 #include "pipeline.hpp"
+#include "sections_core.hpp"
 
 namespace sdsp {
 namespace {
@@ -267,6 +268,51 @@ void fill_tempo_map(const TrackTm& t, int status, sdsp_tempo_map* o) {
     }
 }
 
+// A checked sections request: its cell Cs, and where the sections go.
+struct ScCall {
+    sdsp_sections_request req{};
+    uint64_t Cs = 0;
+    sdsp_sections* out = nullptr;
+};
+// One track's sections from its cell energies, novelty and boundary flags as the kernels wrote
+// them: gmax and nmax (order-free maxima), the section list with its energies, and the snap to the
+// result's downbeats (sections_core.hpp) on the host.  The list and the curves share one block.
+void fill_sections(const TrackSc& t, const TrackRes& r, uint32_t sr, const ScCall& sc, sdsp_sections* o) {
+    std::memset(o, 0, sizeof(*o));
+    o->status = r.status;
+    o->cell_samples = sc.Cs;
+    if (r.status != SDSP_OK || !t.on) return;  // (not on: the key path did not run, n_cells 0)
+    o->first_sample = t.first;
+    const uint64_t nc = t.g.size();
+    o->n_cells = nc;
+    if (nc == 0) return;
+    float gmax = t.g[0], nmax = t.N[0];
+    for (uint64_t c = 1; c < nc; c++) gmax = sd_maxf(gmax, t.g[(size_t)c]), nmax = sd_maxf(nmax, t.N[(size_t)c]);
+    o->gmax = gmax;
+    o->nmax = nmax;
+    std::vector<sdsp_section> secs;
+    if (sc.req.what & SDSP_SECTIONS_LIST)
+        secs = sc_assemble(t.g.data(), t.N.data(), t.b.data(), nc, sc.Cs, sr, r.downs.data(), r.downs.size(),
+                           sc.req.snap_seconds);
+    const size_t S = secs.size(), NC = (sc.req.what & SDSP_SECTIONS_CURVE) ? (size_t)nc : 0;
+    if (S + NC == 0) return;
+    static_assert(sizeof(sdsp_section) % alignof(float) == 0, "the curves follow the sections");
+    char* blk = (char*)std::malloc(S * sizeof(sdsp_section) + 2 * NC * sizeof(float));
+    if (!blk) throw std::bad_alloc();
+    if (S) {
+        o->sections = (sdsp_section*)blk;
+        std::memcpy(o->sections, secs.data(), S * sizeof(sdsp_section));
+        o->n_sections = S;
+    }
+    if (NC) {
+        o->novelty = (float*)(blk + S * sizeof(sdsp_section));
+        o->energy = o->novelty + NC;
+        std::memcpy(o->novelty, t.N.data(), NC * sizeof(float));
+        std::memcpy(o->energy, t.g.data(), NC * sizeof(float));
+        o->n_curve = NC;
+    }
+}
+
 // One device-resident batch on `device`.  The engine's main stream first waits for `user_stream`
 // (everything queued on it so far) and for `wait_ev` (a copy's completion), whichever are given.
 // The batch on a context whose mutex the caller holds (run_device, and sdsp_analyze_audio's
@@ -274,7 +320,8 @@ void fill_tempo_map(const TrackTm& t, int status, sdsp_tempo_map* o) {
 int32_t run_locked(DeviceCtx& d, const float* d_samples, const uint64_t* offsets, const uint64_t* lens, uint64_t n,
                    uint32_t sr, const sdsp_config* cfg, void* user_stream, sdsp_result* outs, int stages,
                    hipEvent_t wait_ev, const sdsp_overview_request* req = nullptr, sdsp_overview* ovs = nullptr,
-                   const KtCall* ktc = nullptr, const LvCall* lvc = nullptr, const TmCall* tmc = nullptr) {
+                   const KtCall* ktc = nullptr, const LvCall* lvc = nullptr, const TmCall* tmc = nullptr,
+                   const ScCall* scc = nullptr) {
     if (stages != SDSP_STAGES_FULL && stages != SDSP_STAGES_BPM_ONLY) throw HipError("unknown stage mask");
     if (user_stream) {
         hipEvent_t ev;
@@ -299,6 +346,9 @@ int32_t run_locked(DeviceCtx& d, const float* d_samples, const uint64_t* offsets
     std::vector<TrackTm> tml;
     d.last_tm = sdsp_debug_tempo_map_times{};
     if (tmc) p.set_tempo_map(tmc->what, &tml);
+    std::vector<TrackSc> scl;
+    d.last_sc = sdsp_debug_sections_times{};
+    if (scc) p.set_sections(scc->req, scc->Cs, &scl);
     try {
         p.run(d_samples, off, ln, res);
         // Certified block energies: a track whose key vote had an energy-dependent
@@ -353,6 +403,8 @@ int32_t run_locked(DeviceCtx& d, const float* d_samples, const uint64_t* offsets
         for (uint64_t i = 0; i < n; i++) fill_levels(lvl[(size_t)i], res[(size_t)i].status, *cfg, sr, &lvc->out[i]);
     if (tmc)
         for (uint64_t i = 0; i < n; i++) fill_tempo_map(tml[(size_t)i], res[(size_t)i].status, &tmc->out[i]);
+    if (scc)
+        for (uint64_t i = 0; i < n; i++) fill_sections(scl[(size_t)i], res[(size_t)i], sr, *scc, &scc->out[i]);
     return SDSP_OK;
 }
 
@@ -360,12 +412,13 @@ int32_t run_device(int device, const float* d_samples, const uint64_t* offsets, 
                    uint32_t sr, const sdsp_config* cfg, void* user_stream, sdsp_result* outs,
                    int stages = SDSP_STAGES_FULL, hipEvent_t wait_ev = nullptr,
                    const sdsp_overview_request* req = nullptr, sdsp_overview* ovs = nullptr,
-                   const KtCall* ktc = nullptr, const LvCall* lvc = nullptr, const TmCall* tmc = nullptr) {
+                   const KtCall* ktc = nullptr, const LvCall* lvc = nullptr, const TmCall* tmc = nullptr,
+                   const ScCall* scc = nullptr) {
     DeviceCtx& d = device_ctx(device);
     std::lock_guard<std::mutex> lk(d.mu);
     SDSP_HIP_CHECK(hipSetDevice(device));
     return run_locked(d, d_samples, offsets, lens, n, sr, cfg, user_stream, outs, stages, wait_ev, req, ovs, ktc, lvc,
-                      tmc);
+                      tmc, scc);
 }
 
 }  // namespace
@@ -554,7 +607,10 @@ int32_t sdsp_analyze_batch_device_with(const float* d_samples, const uint64_t* o
     sdsp_levels* levels = set.levels;
     const sdsp_tempo_map_request* tm_req = set.tm_req;
     sdsp_tempo_map* tempo_maps = set.tempo_maps;
-    if (!set_err && !ov_req && !kt_req && !lv_req && !tm_req)
+    const sdsp_sections_request* sc_req = nullptr;  // (sdsp_request_set_ext's pair, when struct_size covers it)
+    sdsp_sections* sections = nullptr;
+    if (!set_err) request_set_ext_read(caller_set, &sc_req, &sections);
+    if (!set_err && !ov_req && !kt_req && !lv_req && !tm_req && !sc_req)
         return sdsp_analyze_batch_device_ex(d_samples, offsets, lens, n_tracks, sample_rate, cfg, device, stream, stages,
                                             outs);
     auto fail_all = [&](int32_t status, const char* text) {
@@ -577,6 +633,10 @@ int32_t sdsp_analyze_batch_device_with(const float* d_samples, const uint64_t* o
             if (tm_req && tempo_maps) {
                 std::memset(&tempo_maps[i], 0, sizeof(tempo_maps[i]));
                 tempo_maps[i].status = status;
+            }
+            if (sc_req && sections) {
+                std::memset(&sections[i], 0, sizeof(sections[i]));
+                sections[i].status = status;
             }
         }
         return status;
@@ -619,18 +679,106 @@ int32_t sdsp_analyze_batch_device_with(const float* d_samples, const uint64_t* o
         kc.min_conf = kt_req->min_change_confidence;
         kc.out = timelines;
     }
+    ScCall sc;
+    if (sc_req) {
+        int32_t why_status = SDSP_OK;
+        if (const char* why = sections_request_error(
+                *sc_req, sections != nullptr, stages, sample_rate, kt_khop(*cfg), cfg->hop_size, cfg->force_legacy_bpm != 0,
+                cfg->enable_key_beat_synchronous && !cfg->enable_key_log_frequency, &sc.Cs, &why_status))
+            return fail_all(why_status, why);
+        sc.req = *sc_req;
+        sc.out = sections;
+    }
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
         return fail_all(SDSP_ERR_PROCESSING, "Processing error: no HIP device");
     try {
         return run_device(device, d_samples, offsets, lens, n_tracks, sample_rate, cfg, stream, outs, stages, nullptr,
-                          ov_req, overviews, kt_req ? &kc : nullptr, lv_req ? &lc : nullptr, tm_req ? &tc : nullptr);
+                          ov_req, overviews, kt_req ? &kc : nullptr, lv_req ? &lc : nullptr, tm_req ? &tc : nullptr,
+                          sc_req ? &sc : nullptr);
     } catch (const std::exception& e) {
         std::fprintf(stderr, "sdsp_analyze_batch_device_with: %s\n", e.what());
         char text[256];
         std::snprintf(text, sizeof text, "Processing error: %s", e.what());
         return fail_all(SDSP_ERR_PROCESSING, text);
     }
+}
+
+void sdsp_sections_free(sdsp_sections* s) {
+    if (!s) return;
+    std::free(s->sections ? (void*)s->sections : (void*)s->novelty);  // one block (fill_sections), sections first
+    s->sections = nullptr;
+    s->novelty = s->energy = nullptr;
+    s->n_sections = s->n_curve = 0;
+}
+
+int32_t sdsp_debug_last_sections_times(int32_t device, sdsp_debug_sections_times* out) {
+    try {
+        if (!out) return SDSP_ERR_INVALID_INPUT;
+        DeviceCtx& d = device_ctx(device);
+        std::lock_guard<std::mutex> lk(d.mu);
+        *out = d.last_sc;
+        return SDSP_OK;
+    } catch (const std::exception&) {
+        return SDSP_ERR_PROCESSING;
+    }
+}
+
+// The sections kernels over uploaded chroma rows and frame energies (include/stratum_hip_debug.h).
+int32_t sdsp_debug_sections(const float* host_chroma, const uint64_t* frames, const float* host_energy,
+                            const uint64_t* base_frames, uint64_t n_tracks, uint32_t sample_rate, uint32_t khop,
+                            uint32_t hop, const sdsp_sections_request* req, sdsp_debug_sections_out* out, int32_t device) {
+    if (!frames || !base_frames || !req || !out || !out->n_cells || n_tracks == 0 || n_tracks > (1u << 20) || khop == 0 ||
+        hop == 0)
+        return SDSP_ERR_INVALID_INPUT;
+    uint64_t Cs = 0;
+    int32_t why_status = SDSP_OK;
+    if (sections_request_error(*req, true, SDSP_STAGES_FULL, sample_rate, khop, hop, false, false, &Cs, &why_status))
+        return SDSP_ERR_INVALID_INPUT;
+    std::vector<uint64_t> kpfx(1, 0), bpfx(1, 0), cpfx(1, 0), tpfx(1, 0);
+    for (uint64_t t = 0; t < n_tracks; t++) {
+        if (frames[t] > (1u << 24) || base_frames[t] > (1u << 24)) return SDSP_ERR_INVALID_INPUT;
+        kpfx.push_back(kpfx.back() + frames[t]);
+        bpfx.push_back(bpfx.back() + base_frames[t]);
+        const uint64_t nc = sc_cells(frames[t], khop, base_frames[t], hop, Cs);
+        cpfx.push_back(cpfx.back() + nc);
+        tpfx.push_back(tpfx.back() + (nc + SC_TILE - 1) / SC_TILE);
+    }
+    if ((kpfx.back() > 0 && !host_chroma) || (bpfx.back() > 0 && !host_energy)) return SDSP_ERR_INVALID_INPUT;
+    const uint64_t cells = cpfx.back();
+    if (cells > out->cell_capacity || cells / 16 >= 0x7FFFFFFFull) return SDSP_ERR_INVALID_INPUT;
+    if (cells > 0 && (!out->m || !out->g || !out->novelty || !out->boundary)) return SDSP_ERR_INVALID_INPUT;
+    for (uint64_t t = 0; t < n_tracks; t++) out->n_cells[t] = cpfx[(size_t)t + 1] - cpfx[(size_t)t];
+    if (cells == 0) return SDSP_OK;
+    return run_stage_probe("sdsp_debug_sections", device, [&](DeviceCtx& d) {
+        Ctx c(d);
+        c.pre = "D.";
+        const std::vector<float> rows(host_chroma, host_chroma + kpfx.back() * 12);
+        const std::vector<float> en(host_energy, host_energy + bpfx.back());
+        bpfx.pop_back();  // row0 of each track
+        float* d_cs = c.up("sc_chroma", rows);
+        float* d_E = c.up("sc_E", en);
+        uint64_t* d_kpfx = c.up("sc_kpfx", kpfx);
+        uint64_t* d_row0 = c.up("sc_row0", bpfx);
+        uint64_t* d_cpfx = c.up("sc_cpfx", cpfx);
+        uint64_t* d_tpfx = c.up("sc_tpfx", tpfx);
+        float* d_m = c.dev<float>("sc_m", 12 * (size_t)cells);
+        float* d_g = c.dev<float>("sc_g", (size_t)cells);
+        float* d_N = c.dev<float>("sc_N", (size_t)cells);
+        uint8_t* d_b = c.dev<uint8_t>("sc_b", (size_t)cells);
+        launch_section_energy(d_E, d_row0, d_cpfx, (int)n_tracks, cells, Cs, hop, d_g, d.stream);
+        launch_section_chroma(d_cs, d_kpfx, d_cpfx, (int)n_tracks, cells, Cs, khop, d_m, d.stream);
+        launch_section_novelty(d_m, d_g, d_cpfx, d_tpfx, (int)n_tracks, tpfx.back(), (int)req->kernel_cells,
+                               req->energy_weight, req->min_gap_cells, req->min_strength, d_N, d_b, d.stream);
+        SDSP_HIP_CHECK(hipGetLastError());
+        const std::vector<float> m = c.down(d_m, 12 * (size_t)cells), g = c.down(d_g, (size_t)cells),
+                                 N = c.down(d_N, (size_t)cells);
+        const std::vector<uint8_t> b = c.down(d_b, (size_t)cells);
+        std::memcpy(out->m, m.data(), m.size() * sizeof(float));
+        std::memcpy(out->g, g.data(), g.size() * sizeof(float));
+        std::memcpy(out->novelty, N.data(), N.size() * sizeof(float));
+        std::memcpy(out->boundary, b.data(), b.size());
+    });
 }
 
 void sdsp_tempo_map_free(sdsp_tempo_map* m) {

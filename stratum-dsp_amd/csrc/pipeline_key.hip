@@ -97,6 +97,25 @@ KeyLaunch Pipeline::launch_key(const float* d_samples, const TempoPassIn& bin) {
         d_kspfx = c_.up(EP + "kt_spfx", o.spfx);
         o.d_out = c_.dev<KtSeg>(EP + "kt_out", (size_t)std::max<uint64_t>(o.spfx.back(), 1));
     }
+    // the sections request's cell plan (a request only): uploaded on the main stream alike
+    if (sc_out_) {
+        SectionsOut& o = kl.sc;
+        for (int k = 0; k < NK; k++) {
+            const uint64_t n = bin.n_trim[(size_t)kl.K[(size_t)k]];
+            const uint64_t Fb = (n - (uint64_t)fs_) / (uint64_t)bin.hop + 1;  // (n >= fs_: a key track)
+            const uint64_t nc = sc_cells(t.kpfx[(size_t)k + 1] - t.kpfx[(size_t)k], (uint64_t)KHOP, Fb, (uint64_t)bin.hop, sc_Cs_);
+            o.cpfx.push_back(o.cpfx.back() + nc);
+            o.tpfx.push_back(o.tpfx.back() + (nc + SC_TILE - 1) / SC_TILE);
+        }
+        if (o.cpfx.back() / 16 >= 0x7FFFFFFFull) throw HipError("sections: too many cells for one launch");
+        const size_t cells = (size_t)std::max<uint64_t>(o.cpfx.back(), 1);
+        o.d_cpfx = c_.up(EP + "sc_cpfx", o.cpfx);
+        o.d_tpfx = c_.up(EP + "sc_tpfx", o.tpfx);
+        o.d_m = c_.dev<float>(EP + "sc_m", 12 * cells);
+        o.d_g = c_.dev<float>(EP + "sc_g", cells);
+        o.d_N = c_.dev<float>(EP + "sc_N", cells);
+        o.d_b = c_.dev<uint8_t>(EP + "sc_b", cells);
+    }
     // the template upload above is on the main stream too; the vote follows the chroma on st2
     kt.mark(8);
     kt.mark(11, st2);
@@ -115,6 +134,13 @@ KeyLaunch Pipeline::launch_key(const float* d_samples, const TempoPassIn& bin) {
     if (d_kspfx) {
         launch_key_timeline(d_cs, t.d_kpfx, d_kspfx, NK, kl.ktl.spfx.back(), kt_L_, kt_H_, t.d_tpl, kl.ktl.d_out, st3);
         SDSP_HIP_CHECK(hipGetLastError());
+    }
+    // The sections request's chroma cell means read the same rows, under the same ordering.
+    if (sc_out_ && kl.sc.cpfx.back() > 0) {
+        kt.mark(3, st3);
+        launch_section_chroma(d_cs, t.d_kpfx, kl.sc.d_cpfx, NK, kl.sc.cpfx.back(), sc_Cs_, (uint64_t)KHOP, kl.sc.d_m, st3);
+        SDSP_HIP_CHECK(hipGetLastError());
+        kt.mark(4, st3);
     }
     kt.mark(2, st3);
     if (!nested_) SDSP_HIP_CHECK(hipEventRecord(d_.vote_done, st3));
@@ -267,15 +293,17 @@ std::vector<KeyOut> Pipeline::join_key(const float* d_samples, const std::vector
         for (int i : kl.K) key_pending_->at.push_back(f.slot[(size_t)i]);
         for (int i : kl.K) key_pending_->first.push_back(f.ts[(size_t)f.R[(size_t)i]]);
         key_pending_->ktl = std::move(kl.ktl);
+        key_pending_->sc = std::move(kl.sc);
         key_pending_->tail = std::move(kl.tail);
     } else if (NK > 0) {  // join the key stream
-        SDSP_HIP_CHECK(hipStreamWaitEvent(d_.stream, kl.kt->ev[2], 0));
+        SDSP_HIP_CHECK(hipStreamWaitEvent(d_.stream, kl.kt->ev[kl.sc.queued ? 13 : 2], 0));
         kout = c_.down(kl.d_kout, NK);
-        if (kt_out_) {
+        if (kt_out_ || sc_out_) {
             std::vector<size_t> at;
             std::vector<uint64_t> first;
             for (int i : kl.K) at.push_back(f.slot[(size_t)i]), first.push_back(f.ts[(size_t)f.R[(size_t)i]]);
             key_timeline_results(kl.ktl, at, first);
+            sections_results(kl.sc, *kl.kt, at, first);
         }
         htr("E join");
         times_.stft8192_ms += kl.kt->ms(0, 1);
@@ -299,15 +327,73 @@ void Pipeline::key_timeline_results(const KeyTimelineOut& ktl, const std::vector
     }
 }
 
+// The sections request behind the base pass (sub_batch calls it right after tempo_pass, whose E is
+// only valid until the next pass with the same tag): k_section_energy on the main stream over the
+// key tracks' base frames, then, on the vote stream behind an event wait on it and behind the chroma
+// cell means queued by launch_key, the novelty and the boundary flags.  ev[13] follows ev[2] on the
+// vote stream, so a join that waits for it has waited for the vote too; the next sub-batch's vote
+// follows in stream order.
+void Pipeline::section_novelty(KeyLaunch& kl, const TempoPassOut& bo) {
+    SectionsOut& o = kl.sc;
+    if (!sc_out_ || kl.K.empty() || o.cpfx.back() == 0) return;
+    Timers& kt = *kl.kt;
+    const std::string EP = sb_parity_ ? "E1." : "E0.";
+    hipStream_t st3 = kl.serial_streams ? d_.stream : d_.stream3;
+    std::vector<uint64_t> row0;
+    for (int i : kl.K) row0.push_back(bo.fpfx[(size_t)i]);
+    uint64_t* d_row0 = c_.up(EP + "sc_row0", row0);
+    kt.mark(5);
+    launch_section_energy(bo.E, d_row0, o.d_cpfx, (int)kl.K.size(), o.cpfx.back(), sc_Cs_, (uint64_t)cfg_.hop_size, o.d_g,
+                          d_.stream);
+    SDSP_HIP_CHECK(hipGetLastError());
+    kt.mark(6);
+    SDSP_HIP_CHECK(hipStreamWaitEvent(st3, kt.ev[6], 0));
+    kt.mark(12, st3);
+    launch_section_novelty(o.d_m, o.d_g, o.d_cpfx, o.d_tpfx, (int)kl.K.size(), o.tpfx.back(), (int)sc_req_.kernel_cells,
+                           sc_req_.energy_weight, (uint64_t)sc_req_.min_gap_cells, sc_req_.min_strength, o.d_N, o.d_b, st3);
+    SDSP_HIP_CHECK(hipGetLastError());
+    kt.mark(13, st3);
+    o.queued = true;
+}
+
+// A joined sub-batch's cell energies, novelty and boundary flags into the call's per-track entries.
+void Pipeline::sections_results(const SectionsOut& sc, Timers& kt, const std::vector<size_t>& at,
+                                const std::vector<uint64_t>& first) {
+    if (!sc_out_ || sc.cpfx.size() != at.size() + 1) return;
+    const size_t cells = (size_t)sc.cpfx.back();
+    std::vector<float> g, N;
+    std::vector<uint8_t> b;
+    if (sc.queued) {
+        g = c_.down(sc.d_g, cells);
+        N = c_.down(sc.d_N, cells);
+        b = c_.down(sc.d_b, cells);
+        d_.last_sc.energy_ms += kt.ms(5, 6);
+        d_.last_sc.chroma_ms += kt.ms(3, 4);
+        d_.last_sc.novelty_ms += kt.ms(12, 13);
+        d_.last_sc.cells += cells;
+    }
+    for (size_t k = 0; k < at.size(); k++) {
+        TrackSc& o = (*sc_out_)[at[k]];
+        o.on = true;
+        o.first = first[k];
+        if (!sc.queued) continue;
+        const ptrdiff_t a = (ptrdiff_t)sc.cpfx[k], e = (ptrdiff_t)sc.cpfx[k + 1];
+        o.g.assign(g.begin() + a, g.begin() + e);
+        o.N.assign(N.begin() + a, N.begin() + e);
+        o.b.assign(b.begin() + a, b.begin() + e);
+    }
+}
+
 // The pending key results (the previous sub-batch's, or at the end of run() the last one's) into
 // their result slots; returns the tracks whose vote was near a decision.
 std::vector<size_t> Pipeline::finish_key(std::vector<TrackRes>& res, bool keep_tail) {
     std::vector<size_t> near;
     if (!key_pending_) return near;
     std::unique_ptr<KeyPending> kp = std::move(key_pending_);
-    SDSP_HIP_CHECK(hipStreamWaitEvent(d_.stream, kp->kt->ev[2], 0));
+    SDSP_HIP_CHECK(hipStreamWaitEvent(d_.stream, kp->kt->ev[kp->sc.queued ? 13 : 2], 0));
     const std::vector<KeyOut> kout = c_.down(kp->d_kout, kp->at.size());
     key_timeline_results(kp->ktl, kp->at, kp->first);
+    sections_results(kp->sc, *kp->kt, kp->at, kp->first);
     for (size_t k = 0; k < kp->at.size(); k++) {
         TrackRes& r = res[kp->at[k]];
         const KeyOut& ko = kout[k];

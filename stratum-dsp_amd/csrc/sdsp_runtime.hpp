@@ -91,6 +91,7 @@ struct DeviceCtx {
     sdsp_debug_overview_times last_ov{};  // the last call with an overview request (Pipeline::overview)
     sdsp_debug_levels_times last_lv{};    // the last call with a levels request (Pipeline::levels_join)
     sdsp_debug_tempo_map_times last_tm{}; // the last call with a tempo map request (Pipeline::sub_batch)
+    sdsp_debug_sections_times last_sc{};  // the last call with a sections request (Pipeline::sections_results)
     DevBuf& buf(const std::string& name) {
         auto& b = bufs[name];
         if (!b) {

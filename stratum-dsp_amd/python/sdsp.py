@@ -19,7 +19,8 @@ from sdsp_abi import (ERROR_NAMES, FLAG_NAMES, SdspAudioDecodeStats, SdspConfide
                       SdspStageTimes, OVERVIEW_ARRAYS, result_to_dict, SdspKeyChange, SdspKeySegment, SdspKeyTimeline,
                       SdspKeyTimelineRequest, SdspDebugLevelsTimes, SdspLevels, SdspLevelsRequest, SdspLoudness,
                       SdspRequestSet, SdspSilenceRegion, LEVELS_BITS, SdspDebugTempoMapTimes, SdspTempoMap,
-                      SdspTempoMapRequest, SdspTempoSegment, TEMPO_MAP_BITS)
+                      SdspTempoMapRequest, SdspTempoSegment, TEMPO_MAP_BITS, SdspDebugSectionsOut,
+                      SdspDebugSectionsTimes, SdspSection, SdspSections, SdspSectionsRequest, SECTIONS_BITS, SdspRequestSetExt)
 
 PKG = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LIB_PATH = os.environ.get("SDSP_LIB_PATH") or os.path.join(PKG, "lib", "libstratum_hip.so")  # override: layout/ablation builds
@@ -91,6 +92,10 @@ def _load(path):
         L.sdsp_analyze_batch_device_with.restype = C.c_int32
         L.sdsp_levels_free.argtypes = [C.POINTER(SdspLevels)]
         L.sdsp_levels_free.restype = None
+        L.sdsp_sections_free.argtypes = [C.POINTER(SdspSections)]
+        L.sdsp_sections_free.restype = None
+        L.sdsp_debug_last_sections_times.argtypes = [C.c_int32, C.POINTER(SdspDebugSectionsTimes)]
+        L.sdsp_debug_last_sections_times.restype = C.c_int32
         L.sdsp_tempo_map_free.argtypes = [C.POINTER(SdspTempoMap)]
         L.sdsp_tempo_map_free.restype = None
         L.sdsp_debug_last_tempo_map_times.argtypes = [C.c_int32, C.POINTER(SdspDebugTempoMapTimes)]
@@ -763,16 +768,55 @@ def tempo_map_times(device=0):
     return {k: getattr(t, k) for k, _ in SdspDebugTempoMapTimes._fields_}
 
 
+SECTION_FIELDS = tuple(k for k, _ in SdspSection._fields_)
+
+
+def sections_request(cell_seconds=0.0, cell_samples=0, kernel_cells=16, min_gap_cells=8, energy_weight=1.0,
+                     min_strength=0.5, snap_seconds=0.0, what=("list", "curve")):
+    """An sdsp_sections_request: the cell as cell_seconds or cell_samples (exactly one), K, G, the
+    energy weight, the strength floor and the snap distance; `what` is a mask of sdsp_sections_what
+    bits, or names out of list, curve (the default asks for both)."""
+    if not isinstance(what, int):
+        mask = 0
+        for name in what:
+            mask |= SECTIONS_BITS[name]
+        what = mask
+    return SdspSectionsRequest(what, cell_seconds, cell_samples, kernel_cells, min_gap_cells, energy_weight, min_strength,
+                               snap_seconds)
+
+
+def sections_to_dict(s):
+    """One sdsp_sections: its integer fields as int, gmax and nmax as np.float32, `sections` a dict
+    of numpy arrays, one per field of SECTION_FIELDS, `novelty` and `energy` float32 arrays."""
+    d = {k: int(getattr(s, k)) for k in ("status", "n_cells", "cell_samples", "first_sample", "n_sections", "n_curve")}
+    d["gmax"], d["nmax"] = np.float32(s.gmax), np.float32(s.nmax)
+    sec = _records(s.sections, d["n_sections"], SdspSection)
+    d["sections"] = {k: sec[k].copy() for k in SECTION_FIELDS}
+    d["novelty"] = _records(s.novelty, d["n_curve"], C.c_float).astype(np.float32)
+    d["energy"] = _records(s.energy, d["n_curve"], C.c_float).astype(np.float32)
+    return d
+
+
+def sections_times(device=0):
+    """sdsp_debug_last_sections_times: the event times of the three section steps of the last call
+    with a sections request on `device`."""
+    t = SdspDebugSectionsTimes()
+    if lib().sdsp_debug_last_sections_times(device, C.byref(t)) != 0:
+        raise RuntimeError("sdsp_debug_last_sections_times failed")
+    return {k: getattr(t, k) for k, _ in SdspDebugSectionsTimes._fields_}
+
+
 def analyze_batch_device_with(d_ptr, offsets, lens, sample_rate=44100, config=None, device=0, stream=None,
                               stages=STAGES_FULL, overview=None, key_timeline=None, levels=None, request_set=True,
-                              tempo_map=None):
+                              tempo_map=None, sections=None):
     """sdsp_analyze_batch_device_with: analyze_batch_device(raw=True) with any of the optional
     requests: an SdspOverviewRequest, an SdspKeyTimelineRequest, an SdspLevelsRequest
     (levels_request()), an SdspTempoMapRequest (tempo_map_request()); None leaves a request out.
     request_set=False passes set == NULL.  Returns (ResultBatch, overviews, timelines, levels), and
     with a tempo map request a fifth element, the tempo maps: levels[i] a levels_to_dict(), maps[i]
     a tempo_map_to_dict(); each list [] without its request.  Raises AnalysisError when the call as
-    a whole fails (a refused request)."""
+    a whole fails (a refused request).  With a sections request (sections_request()) the sections,
+    each a sections_to_dict(), are one more element at the end of the tuple."""
     offs = np.ascontiguousarray(offsets, dtype=np.uint64)
     ln = np.ascontiguousarray(lens, dtype=np.uint64)
     n = ln.size
@@ -781,10 +825,12 @@ def analyze_batch_device_with(d_ptr, offsets, lens, sample_rate=44100, config=No
     kts = (SdspKeyTimeline * max(n, 1))() if key_timeline is not None else None
     lvs = (SdspLevels * max(n, 1))() if levels is not None else None
     tms = (SdspTempoMap * max(n, 1))() if tempo_map is not None else None
+    scs = (SdspSections * max(n, 1))() if sections is not None else None
     cfg = config if config is not None else default_config()
     _schedule_from_env()
-    rs = SdspRequestSet()
-    rs.struct_size = C.sizeof(SdspRequestSet)
+    ext = SdspRequestSetExt()  # (a call without a sections request passes the plain set's size)
+    rs = ext.base
+    rs.struct_size = C.sizeof(SdspRequestSetExt if sections is not None else SdspRequestSet)
     if overview is not None:
         rs.ov_req = C.pointer(overview)
         rs.overviews = ovs
@@ -797,13 +843,16 @@ def analyze_batch_device_with(d_ptr, offsets, lens, sample_rate=44100, config=No
     if tempo_map is not None:
         rs.tm_req = C.pointer(tempo_map)
         rs.tempo_maps = tms
+    if sections is not None:
+        ext.sc_req = C.pointer(sections)
+        ext.sections = scs
     u64p = C.POINTER(C.c_uint64)
     st = lib().sdsp_analyze_batch_device_with(C.c_void_p(d_ptr), offs.ctypes.data_as(u64p), ln.ctypes.data_as(u64p), n,
                                               sample_rate, C.byref(cfg), device, C.c_void_p(stream or 0), stages, outs,
                                               C.byref(rs) if request_set else None)
     if st != 0:
         raise AnalysisError(st, _batch_error(outs, n, "device batch failed"))
-    overviews, timelines, lv, maps = [], [], [], []
+    overviews, timelines, lv, maps, secs = [], [], [], [], []
     for i in range(n if request_set else 0):
         if ovs is not None:
             overviews.append(overview_to_dict(ovs[i]))
@@ -817,9 +866,15 @@ def analyze_batch_device_with(d_ptr, offsets, lens, sample_rate=44100, config=No
         if tms is not None:
             maps.append(tempo_map_to_dict(tms[i]))
             lib().sdsp_tempo_map_free(C.byref(tms[i]))
+        if scs is not None:
+            secs.append(sections_to_dict(scs[i]))
+            lib().sdsp_sections_free(C.byref(scs[i]))
+    ret = (ResultBatch(outs, n), overviews, timelines, lv)
     if tempo_map is not None:
-        return ResultBatch(outs, n), overviews, timelines, lv, maps
-    return ResultBatch(outs, n), overviews, timelines, lv
+        ret += (maps,)
+    if sections is not None:
+        ret += (secs,)
+    return ret
 
 
 def levels_times(device=0):
@@ -1406,6 +1461,42 @@ def debug_beat_grid(tracks, sample_rate=44100, config=None, device=0):
                         stability=stab[t].copy()))
         b0 += kb
         d0 += kd
+    return out
+
+
+def debug_sections(rows, energies, request, sample_rate=44100, khop=512, hop=512, device=0):
+    """The sections kernels over uploaded chroma rows and frame energies (sdsp_debug_sections).
+    rows[t]: (F_t, 12) float32, khop samples apart; energies[t]: (Fb_t,) float32, hop samples apart.
+    Returns per track a dict with n_cells, m (n_cells, 12), g, novelty (float32) and boundary (uint8)."""
+    T = len(rows)
+    rs = [np.ascontiguousarray(r, np.float32).reshape(-1, 12) for r in rows]
+    es = [np.ascontiguousarray(e, np.float32).ravel() for e in energies]
+    frames = np.array([r.shape[0] for r in rs], np.uint64)
+    bframes = np.array([e.size for e in es], np.uint64)
+    allr = np.ascontiguousarray(np.concatenate([r.ravel() for r in rs] + [np.zeros(12, np.float32)]))
+    alle = np.ascontiguousarray(np.concatenate(es + [np.zeros(1, np.float32)]))
+    cs = int(request.cell_samples) or int(np.float32(request.cell_seconds) * np.float32(sample_rate))
+    cap = sum(min(int(f) * khop, int(b) * hop) // cs for f, b in zip(frames, bframes)) if cs > 0 else 0
+    nc = np.zeros(max(T, 1), np.uint64)
+    m, g, nov = np.zeros(12 * max(cap, 1), np.float32), np.zeros(max(cap, 1), np.float32), np.zeros(max(cap, 1), np.float32)
+    bnd = np.zeros(max(cap, 1), np.uint8)
+    u64p = C.POINTER(C.c_uint64)
+    o = SdspDebugSectionsOut(cap, nc.ctypes.data_as(u64p), _fp(m), _fp(g), _fp(nov), bnd.ctypes.data_as(C.POINTER(C.c_uint8)))
+    f = lib().sdsp_debug_sections
+    fp = C.POINTER(C.c_float)
+    f.argtypes = [fp, u64p, fp, u64p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(SdspSectionsRequest),
+                  C.POINTER(SdspDebugSectionsOut), C.c_int32]
+    f.restype = C.c_int32
+    st = f(_fp(allr), frames.ctypes.data_as(u64p), _fp(alle), bframes.ctypes.data_as(u64p), T, sample_rate, khop, hop,
+           C.byref(request), C.byref(o), device)
+    if st != 0:
+        raise AnalysisError(st, "debug_sections failed")
+    out, at = [], 0
+    for t in range(T):
+        k = int(nc[t])
+        out.append(dict(n_cells=k, m=m[12 * at:12 * (at + k)].reshape(k, 12).copy(), g=g[at:at + k].copy(),
+                        novelty=nov[at:at + k].copy(), boundary=bnd[at:at + k].copy()))
+        at += k
     return out
 
 

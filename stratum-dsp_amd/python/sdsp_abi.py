@@ -499,6 +499,78 @@ class SdspDebugTempoMapTimes(C.Structure):
     _fields_ = [("map_ms", C.c_double), ("beat_ms", C.c_double), ("tracks", u64)]
 
 
+SECTIONS_LIST, SECTIONS_CURVE = 1, 2  # enum sdsp_sections_what
+SECTIONS_BITS = {"list": SECTIONS_LIST, "curve": SECTIONS_CURVE}
+
+
+class SdspSectionsRequest(C.Structure):
+    """sdsp_sections_request: the cell (seconds or samples form, exactly one), K, G and the weights."""
+
+    _fields_ = [
+        ("what", u32),
+        ("cell_seconds", f32),
+        ("cell_samples", u64),
+        ("kernel_cells", u32),
+        ("min_gap_cells", u32),
+        ("energy_weight", f32),
+        ("min_strength", f32),
+        ("snap_seconds", f32),
+    ]
+
+
+class SdspSection(C.Structure):
+    """sdsp_section: one run of cells between two boundaries."""
+
+    _fields_ = [
+        ("start_cell", u64),
+        ("end_cell", u64),
+        ("start_time", f32),
+        ("end_time", f32),
+        ("strength", f32),
+        ("mean_energy", f32),
+        ("relative_energy", f32),
+        ("snapped_time", f32),
+        ("downbeat", C.c_int32),
+    ]
+
+
+class SdspSections(C.Structure):
+    """sdsp_sections: one track's sections and curves (library-owned arrays)."""
+
+    _fields_ = [
+        ("status", C.c_int32),
+        ("n_cells", u64),
+        ("cell_samples", u64),
+        ("first_sample", u64),
+        ("gmax", f32),
+        ("nmax", f32),
+        ("n_sections", u64),
+        ("sections", C.POINTER(SdspSection)),
+        ("n_curve", u64),
+        ("novelty", C.POINTER(f32)),
+        ("energy", C.POINTER(f32)),
+    ]
+
+
+class SdspDebugSectionsOut(C.Structure):
+    """sdsp_debug_sections_out (include/stratum_hip_debug.h): caller-owned arrays."""
+
+    _fields_ = [
+        ("cell_capacity", u64),
+        ("n_cells", C.POINTER(u64)),
+        ("m", C.POINTER(f32)),
+        ("g", C.POINTER(f32)),
+        ("novelty", C.POINTER(f32)),
+        ("boundary", C.POINTER(C.c_uint8)),
+    ]
+
+
+class SdspDebugSectionsTimes(C.Structure):
+    """sdsp_debug_sections_times (include/stratum_hip_debug.h)."""
+
+    _fields_ = [("energy_ms", C.c_double), ("chroma_ms", C.c_double), ("novelty_ms", C.c_double), ("cells", u64)]
+
+
 class SdspRequestSet(C.Structure):
     """sdsp_request_set: the optional requests of sdsp_analyze_batch_device_with, by name."""
 
@@ -512,6 +584,17 @@ class SdspRequestSet(C.Structure):
         ("levels", C.POINTER(SdspLevels)),
         ("tm_req", C.POINTER(SdspTempoMapRequest)),
         ("tempo_maps", C.POINTER(SdspTempoMap)),
+    ]
+
+
+class SdspRequestSetExt(C.Structure):
+    """sdsp_request_set_ext: sdsp_request_set, then the pairs added after the tempo map.  Pass
+    byref(ext.base) with ext.base.struct_size = sizeof(ext)."""
+
+    _fields_ = [
+        ("base", SdspRequestSet),
+        ("sc_req", C.POINTER(SdspSectionsRequest)),
+        ("sections", C.POINTER(SdspSections)),
     ]
 
 
