@@ -736,6 +736,88 @@ typedef struct sdsp_request_set_ext {
 } sdsp_request_set_ext;
 
 /*
+ * ---- Programme loudness (ITU-R BS.1770-4 / EBU R 128) of every track of an analysis call ----
+ *
+ * Integrated loudness in LUFS with the absolute and the relative gate, the loudness range (EBU Tech
+ * 3342), the maximum momentary and short-term loudness, the sample peak and a 4x-oversampled true
+ * peak, from the samples the call already holds on the device.  (The levels request's "LUFS" is the
+ * reference crate's own measure, one shelving stage and no relative gate; it is unchanged.)
+ *
+ * The definition.  All arithmetic is f32, every sum starts from 0 and runs in ascending index order,
+ * multiply and add are separate operations, log10 is sdsp_libm.h's.  x[0..n) is the caller's raw
+ * track (before normalisation and trim, as for levels), sr the call's sample rate, step = sr / 10,
+ * J = n / step (integer divisions).
+ *   Coefficients, computed in double and rounded to f32 (returned in shelf[] / highpass[] as
+ *   b0 b1 b2 a1 a2).  Shelf: K = tan(pi * 1681.974450955533 / sr), Vh = 10^(3.999843853973347 / 20),
+ *   Vb = Vh^0.4996667741545416, Q = 0.7071752369554196, a0 = 1 + K/Q + K*K,
+ *   b = {(Vh + Vb*K/Q + K*K)/a0, 2(K*K - Vh)/a0, (Vh - Vb*K/Q + K*K)/a0}, a = {2(K*K - 1)/a0,
+ *   (1 - K/Q + K*K)/a0}.  High-pass: K = tan(pi * 38.13547087602444 / sr), Q = 0.5003270373238773,
+ *   b = {1, -2, 1}, a as above.  At 48 kHz these are the standard's table to its printed digits.
+ *   Step energies.  For step j both filters start from zero state at sample max(j - 1, 0) * step and
+ *   run, Direct Form II transposed (o = b0*s + x1; x1 = (b1*s + x2) - a1*o; x2 = b2*s - a2*o), the
+ *   shelf feeding the high-pass, through sample (j + 1) * step - 1.  z[j] is the sum of o*o of the
+ *   high-pass output over step j's own samples.  Samples past J * step are not measured.
+ *   Blocks.  Momentary m[j] = (((z[j] + z[j+1]) + z[j+2]) + z[j+3]) / (f32)(4 * step), j in [0, J - 3);
+ *   short-term s[j] = (the ascending sum of z[j .. j+30)) / (f32)(30 * step), j in [0, J - 29).
+ *   L(e) = -0.691f + 10 log10(e).
+ *   Integrated.  Ga = 10^((-70 + 0.691) / 10) (the levels request's gate constant).  A = the blocks
+ *   with m > Ga, Gr = mean(A) * 0.1f; integrated_lufs = L(mean of the m with m > Ga and m > Gr), both
+ *   means in block order; n_gated_momentary is the second mean's count.
+ *   Range.  Of the s > Ga, the mean times 0.01f is the relative gate; the s above both gates, sorted
+ *   ascending, are e[0..M): range_low = L(e[((M-1)*10 + 50) / 100]), range_high = L(e[((M-1)*95 + 50)
+ *   / 100]), range_lu = range_high - range_low; has_range = 0 and the three fields 0 when M == 0.
+ *   n_gated_short_term = M.
+ *   Maxima.  L of the largest m and of the largest s, ungated; -inf without a block.
+ *   Peaks.  sample_peak = max |x[i]|.  true_peak = the larger of sample_peak and the maximum over
+ *   i in [0, n), p in {1, 2, 3} of |sum over k = 0..11 of h[p][k] * x[i + k - 5]|, x = 0 outside the
+ *   track, h[p][k] = sinc(t) * (0.5 + 0.5 cos(pi t / 6)), t = (k - 5) - p/4, in double rounded to f32:
+ *   4x oversampling with a 48-tap Hann-windowed sinc, the size of BS.1770 Annex 2's filter but not its
+ *   table.  dB values are 20 log10; the dB of 0 is -inf.
+ *
+ * What these numbers are.  The engine holds the mono mix: this is BS.1770 with one channel of weight
+ * 1, and a centre-panned stereo file reads 3.01 LU below its stereo programme loudness.  The filter
+ * is restarted one step before each step instead of running through the track; its slowest pole
+ * (the 38 Hz high-pass) has decayed below f32 rounding by then, and on noise, a DC-offset track and
+ * a two-level track the integrated, momentary and short-term values lie within 0.00006 LU of an
+ * unbroken f64 filter's at 48 kHz (tests/test_r128_ref.py; the bound asserted there is 0.01 LU).  The 4x grid
+ * under-reads peaks of tones near Nyquist by up to 0.44 dB (cos 18 degrees), as the standard notes.
+ * Non-finite samples are out of scope.
+ *
+ * SDSP_R128_CURVES needs SDSP_R128_LOUDNESS.  Without SDSP_R128_LOUDNESS only the peak fields (and
+ * n_samples, step_samples, the coefficients) are filled; without SDSP_R128_TRUE_PEAK true_peak is 0
+ * and true_peak_dbtp -inf.  A track with n > 0 under a supported configuration has SDSP_OK whatever its
+ * analysis status (as for levels); another has the analysis status and zeroed fields.
+ */
+enum sdsp_r128_what { SDSP_R128_LOUDNESS = 1, SDSP_R128_TRUE_PEAK = 2, SDSP_R128_CURVES = 4 }; /* bits of sdsp_r128_request.what */
+typedef struct sdsp_r128_request { uint32_t what; } sdsp_r128_request;
+
+typedef struct sdsp_r128 {
+    int32_t status;
+    int8_t has_integrated, has_range;      /* 0: no block passed the gates */
+    float integrated_lufs;                 /* -inf when has_integrated is 0 */
+    float range_lu, range_low_lufs, range_high_lufs;
+    float max_momentary_lufs, max_short_term_lufs;  /* -inf without a block */
+    float sample_peak, true_peak;          /* linear; true_peak 0 without SDSP_R128_TRUE_PEAK */
+    float sample_peak_db, true_peak_dbtp;
+    uint64_t n_samples;                    /* the caller's track length */
+    uint32_t step_samples;                 /* sample_rate / 10 */
+    uint64_t n_steps, n_momentary, n_short_term, n_gated_momentary, n_gated_short_term;
+    float shelf[5], highpass[5];           /* b0 b1 b2 a1 a2 as f32: a caller can recompute every field */
+    float *momentary, *short_term;         /* mean squares per block, library-owned, one allocation; CURVES only */
+} sdsp_r128;
+
+/*
+ * The request set with the pair added after sections: it begins with sdsp_request_set_ext (whose
+ * last pair callers' layout checks pin), as that one begins with sdsp_request_set.  Pass
+ * &ext2.base.base with ext2.base.base.struct_size = sizeof(ext2); the library reads r128_req / r128
+ * only when struct_size covers them, so callers that pass either older struct keep working.
+ */
+typedef struct sdsp_request_set_ext2 {
+    sdsp_request_set_ext base;
+    const sdsp_r128_request* r128_req;       sdsp_r128* r128;
+} sdsp_request_set_ext2;
+
+/*
  * sdsp_analyze_batch_device_ex with any of the optional requests from one analysis: overviews and
  * key timelines as in sdsp_analyze_batch_device_requests (which forwards here), levels (n_tracks
  * entries, freed one by one with sdsp_levels_free) as above, with SDSP_STAGES_FULL and
@@ -753,6 +835,10 @@ typedef struct sdsp_request_set_ext {
  * output array; SDSP_STAGES_BPM_ONLY.  With SDSP_ERR_NOT_IMPLEMENTED: force_legacy_bpm (no feature
  * pass, so no E), and enable_key_beat_synchronous without enable_key_log_frequency (the rows are
  * beats, as for the key timeline).
+ * Programme loudness (sdsp_request_set_ext2: n_tracks entries, freed one by one with sdsp_r128_free)
+ * as above, with SDSP_STAGES_FULL and SDSP_STAGES_BPM_ONLY alike.  Also refused with
+ * SDSP_ERR_INVALID_INPUT: what == 0 or unknown bits; SDSP_R128_CURVES without SDSP_R128_LOUDNESS; no
+ * output array; a sample rate under 8000 Hz.
  */
 int32_t sdsp_analyze_batch_device_with(const float* d_samples, const uint64_t* offsets, const uint64_t* lens,
                                        uint64_t n_tracks, uint32_t sample_rate, const sdsp_config* cfg,
@@ -764,6 +850,8 @@ void sdsp_levels_free(sdsp_levels* l);
 void sdsp_tempo_map_free(sdsp_tempo_map* m);
 /* Frees the arrays owned by one sdsp_sections (they share one allocation: never free() them one by one). */
 void sdsp_sections_free(sdsp_sections* s);
+/* Frees the curves owned by one sdsp_r128 (they share one allocation: never free() them one by one). */
+void sdsp_r128_free(sdsp_r128* r);
 
 /*
  * Synthetic track generator on device: writes n_tracks tracks of `len`

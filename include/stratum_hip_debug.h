@@ -345,6 +345,19 @@ typedef struct sdsp_debug_sections_times {
 int32_t sdsp_debug_last_sections_times(int32_t device, sdsp_debug_sections_times* out);
 
 /*
+ * The programme loudness kernels of the last sdsp_analyze_batch_device_with call with an r128 request
+ * on `device`: HIP event times of k_r128_steps, k_r128_peak and k_r128_track (0 for one that did not
+ * run), the tracks and the steps measured.  The events lie on the vote stream, so beside a running
+ * analysis they include what the kernels shared the device with.  All zero after a call without a
+ * request.
+ */
+typedef struct sdsp_debug_r128_times {
+    double steps_ms, peak_ms, track_ms;
+    uint64_t tracks, steps;
+} sdsp_debug_r128_times;
+int32_t sdsp_debug_last_r128_times(int32_t device, sdsp_debug_r128_times* out);
+
+/*
  * Stage probe of the candidate selection: the pipeline's own select launch (k_tempo_select with the
  * parameters an analysis call derives from cfg: Pipeline::pass_select from its offset tables on) over
  * uploaded tempogram lists instead of a novelty curve.  Per track t and variant v (full, low, mid,

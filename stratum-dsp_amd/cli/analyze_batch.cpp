@@ -42,7 +42,12 @@
 //
 //   analyze_batch [--jobs N] [--devices MASK] [--json] [--gpu-decode] [--overview N | --overview-frames K]
 //                 [--key-timeline SEC[:OVERLAP[:MINCONF]]] [--levels [LIST]] [--tempo-map[=LIST]]
-//                 [--sections[=CELL_SEC[:K[:GAP[:EWEIGHT[:MINSTRENGTH]]]]]] <file1> <file2> ...
+//                 [--sections[=CELL_SEC[:K[:GAP[:EWEIGHT[:MINSTRENGTH]]]]]] [--loudness[=true-peak,curves]]
+//                 <file1> <file2> ...
+// --loudness[=LIST] (opt-in; JSONL only): each line's object gets a "loudness" member
+// (include/stratum_hip.h, sdsp_r128): BS.1770 integrated loudness, loudness range, maximum momentary
+// and short-term loudness and the sample peak; LIST out of true-peak (the 4x true peak) and curves
+// (the momentary and short-term mean squares per block).
 #include <algorithm>
 #include <atomic>
 #include <chrono>
@@ -73,6 +78,7 @@ struct Item {
     std::string levels;    // --levels: the "levels" member's value
     std::string tempo_map; // --tempo-map: the "tempo_map" member's value
     std::string sections;  // --sections: the "sections" member's value
+    std::string loudness;  // --loudness: the "loudness" member's value
 };
 
 // floats so that an f32 round-trips
@@ -234,6 +240,41 @@ std::string sections_json(const sdsp_sections& m) {
     return s + "]}";
 }
 
+std::string r128_json(const sdsp_r128& m, uint32_t what) {
+    char b[768];
+    std::snprintf(b, sizeof b,
+                  "{\"status\":%d,\"n_samples\":%llu,\"step_samples\":%u,\"n_steps\":%llu,\"integrated_lufs\":%s,"
+                  "\"range_lu\":%s,\"range_low_lufs\":%s,\"range_high_lufs\":%s,\"max_momentary_lufs\":%s,"
+                  "\"max_short_term_lufs\":%s,\"sample_peak\":%.9g,\"sample_peak_db\":%s,\"n_momentary\":%llu,"
+                  "\"n_short_term\":%llu,\"n_gated_momentary\":%llu,\"n_gated_short_term\":%llu",
+                  m.status, (unsigned long long)m.n_samples, m.step_samples, (unsigned long long)m.n_steps,
+                  m.has_integrated ? json_db(m.integrated_lufs).c_str() : "null",
+                  m.has_range ? json_db(m.range_lu).c_str() : "null", m.has_range ? json_db(m.range_low_lufs).c_str() : "null",
+                  m.has_range ? json_db(m.range_high_lufs).c_str() : "null", json_db(m.max_momentary_lufs).c_str(),
+                  json_db(m.max_short_term_lufs).c_str(), (double)m.sample_peak, json_db(m.sample_peak_db).c_str(),
+                  (unsigned long long)m.n_momentary, (unsigned long long)m.n_short_term,
+                  (unsigned long long)m.n_gated_momentary, (unsigned long long)m.n_gated_short_term);
+    std::string s = b;
+    if (what & SDSP_R128_TRUE_PEAK) {
+        std::snprintf(b, sizeof b, ",\"true_peak\":%.9g,\"true_peak_dbtp\":%s", (double)m.true_peak,
+                      json_db(m.true_peak_dbtp).c_str());
+        s += b;
+    }
+    if (what & SDSP_R128_CURVES) {
+        for (int k = 0; k < 2; k++) {
+            s += k ? "],\"short_term\":[" : ",\"momentary\":[";
+            const float* v = k ? m.short_term : m.momentary;
+            const uint64_t n = v ? (k ? m.n_short_term : m.n_momentary) : 0;
+            for (uint64_t i = 0; i < n; i++) {
+                std::snprintf(b, sizeof b, i ? ",%.9g" : "%.9g", (double)v[i]);
+                s += b;
+            }
+        }
+        s += "]";
+    }
+    return s + "}";
+}
+
 // percentile as the example computes it: sort, index round((len-1) * p)
 float percentile(std::vector<float> xs, float p) {
     std::sort(xs.begin(), xs.end());
@@ -325,6 +366,8 @@ int main(int argc, char** argv) {
     screq.energy_weight = 1.0f;
     screq.min_strength = 0.5f;
     bool sections = false;
+    sdsp_r128_request r128req{SDSP_R128_LOUDNESS};
+    bool loudness = false;
     std::vector<std::string> paths;
     for (size_t i = 0; i < a.size(); i++) {
         const std::string& s = a[i];
@@ -451,11 +494,33 @@ int main(int argc, char** argv) {
                 screq.min_strength = (float)v[4];
             }
             screq.snap_seconds = screq.cell_seconds;
+        } else if (s == "--loudness" || s.rfind("--loudness=", 0) == 0) {
+            loudness = true;
+            if (s.size() > 10) {  // =LIST
+                const std::string w = s.substr(11);
+                bool good = !w.empty();
+                for (size_t p0 = 0; good;) {
+                    const size_t p1 = std::min(w.find(',', p0), w.size());
+                    const std::string part = w.substr(p0, p1 - p0);
+                    if (part == "true-peak")
+                        r128req.what |= SDSP_R128_TRUE_PEAK;
+                    else if (part == "curves")
+                        r128req.what |= SDSP_R128_CURVES;
+                    else
+                        good = false;
+                    if (p1 == w.size()) break;
+                    p0 = p1 + 1;
+                }
+                if (!good) {
+                    std::fprintf(stderr, "Error: --loudness=LIST takes a list out of true-peak,curves\n");
+                    return 1;
+                }
+            }
         } else if (s == "--help" || s == "-h") {
             std::fprintf(stderr,
                          "Usage: analyze_batch [--jobs N] [--devices MASK] [--json] [--gpu-decode] [--overview N | "
                          "--overview-frames K] [--key-timeline SEC[:OVERLAP[:MINCONF]]] [--levels [LIST]] [--tempo-map[=LIST]] "
-                         "[--sections[=CELL_SEC[:K[:GAP[:EWEIGHT[:MINSTRENGTH]]]]]] <file1> <file2> ...\n\n"
+                         "[--sections[=CELL_SEC[:K[:GAP[:EWEIGHT[:MINSTRENGTH]]]]]] [--loudness[=LIST]] <file1> <file2> ...\n\n"
                          "--jobs N        Decode workers (default: CPU-1)\n"
                          "--devices MASK  GPU bitmask (default: all visible GPUs)\n"
                          "--json          Emit one JSON object per line (JSONL)\n"
@@ -471,7 +536,10 @@ int main(int argc, char** argv) {
                          "                onsets (\"tempo_map\"); LIST out of segments,onsets (default: both)\n"
                          "--sections[=CELL_SEC[:K[:GAP[:EWEIGHT[:MINSTRENGTH]]]]]  With --json: add each track's sections between\n"
                          "                structural boundaries with their energies, and the novelty and energy curves\n"
-                         "                (\"sections\"); defaults 0.5:16:8:1:0.5, starts snapped to downbeats within a cell\n");
+                         "                (\"sections\"); defaults 0.5:16:8:1:0.5, starts snapped to downbeats within a cell\n"
+                         "--loudness[=LIST]  With --json: add each track's BS.1770 integrated loudness, loudness range, maximum\n"
+                         "                momentary and short-term loudness and sample peak (\"loudness\"); LIST out of\n"
+                         "                true-peak,curves adds the 4x true peak and the per-block mean squares\n");
             return 0;
         } else {
             paths.push_back(s);
@@ -486,6 +554,7 @@ int main(int argc, char** argv) {
     if (levels && !json) std::fprintf(stderr, "Note: --levels adds to the --json lines only\n");
     if (tempo_map && !json) std::fprintf(stderr, "Note: --tempo-map adds to the --json lines only\n");
     if (sections && !json) std::fprintf(stderr, "Note: --sections adds to the --json lines only\n");
+    if (loudness && !json) std::fprintf(stderr, "Note: --loudness adds to the --json lines only\n");
     if (paths.empty()) {
         std::fprintf(stderr, "ERROR: Provide at least one audio file path. Use --help for usage.\n");
         return 2;
@@ -539,14 +608,16 @@ int main(int argc, char** argv) {
 
     sdsp_config cfg;
     sdsp_config_default(&cfg);
-    auto take = [](Item& it, const sdsp_result& r, const sdsp_overview* ov = nullptr,
-                   const sdsp_key_timeline* kt = nullptr, const sdsp_levels* lv = nullptr,
-                   const sdsp_tempo_map* tm = nullptr, const sdsp_sections* sc = nullptr) {
+    auto take = [&r128req](Item& it, const sdsp_result& r, const sdsp_overview* ov = nullptr,
+                           const sdsp_key_timeline* kt = nullptr, const sdsp_levels* lv = nullptr,
+                           const sdsp_tempo_map* tm = nullptr, const sdsp_sections* sc = nullptr,
+                           const sdsp_r128* ld = nullptr) {
         if (ov) it.overview = overview_json(*ov);
         if (kt) it.timeline = key_timeline_json(*kt);
         if (lv) it.levels = levels_json(*lv);
         if (tm) it.tempo_map = tempo_map_json(*tm);
         if (sc) it.sections = sections_json(*sc);
+        if (ld) it.loudness = r128_json(*ld, r128req.what);
         if (r.status != 0) {
             it.error = std::string("analysis failed: ") + r.error_message;
             return;
@@ -572,7 +643,8 @@ int main(int argc, char** argv) {
         std::vector<sdsp_levels> lvs;
         std::vector<sdsp_tempo_map> tms;
         std::vector<sdsp_sections> scs;
-        sdsp_request_set_ext ext{};
+        std::vector<sdsp_r128> lds;
+        sdsp_request_set_ext2 ext2{};
     };
     auto requests = [&](size_t n) {
         Requests q;
@@ -581,26 +653,29 @@ int main(int argc, char** argv) {
         q.lvs.resize(levels ? n : 0);
         q.tms.resize(tempo_map ? n : 0);
         q.scs.resize(sections ? n : 0);
+        q.lds.resize(loudness ? n : 0);
         return q;
     };
     auto request_set = [&](Requests& q) {
-        sdsp_request_set& set = q.ext.base;
-        set.struct_size = (uint32_t)sizeof(q.ext);
+        sdsp_request_set& set = q.ext2.base.base;
+        set.struct_size = (uint32_t)sizeof(q.ext2);
         if (overview) set.ov_req = &ovreq, set.overviews = q.ovs.data();
         if (timeline) set.kt_req = &ktreq, set.timelines = q.kts.data();
         if (levels) set.lv_req = &lvreq, set.levels = q.lvs.data();
         if (tempo_map) set.tm_req = &tmreq, set.tempo_maps = q.tms.data();
-        if (sections) q.ext.sc_req = &screq, q.ext.sections = q.scs.data();
+        if (sections) q.ext2.base.sc_req = &screq, q.ext2.base.sections = q.scs.data();
+        if (loudness) q.ext2.r128_req = &r128req, q.ext2.r128 = q.lds.data();
         return &set;
     };
     auto take_requests = [&](Item& it, const sdsp_result& r, Requests& q, size_t j) {
         take(it, r, overview ? &q.ovs[j] : nullptr, timeline ? &q.kts[j] : nullptr, levels ? &q.lvs[j] : nullptr,
-             tempo_map ? &q.tms[j] : nullptr, sections ? &q.scs[j] : nullptr);
+             tempo_map ? &q.tms[j] : nullptr, sections ? &q.scs[j] : nullptr, loudness ? &q.lds[j] : nullptr);
         if (overview) sdsp_overview_free(&q.ovs[j]);
         if (timeline) sdsp_key_timeline_free(&q.kts[j]);
         if (levels) sdsp_levels_free(&q.lvs[j]);
         if (tempo_map) sdsp_tempo_map_free(&q.tms[j]);
         if (sections) sdsp_sections_free(&q.scs[j]);
+        if (loudness) sdsp_r128_free(&q.lds[j]);
     };
 
     if (gpu_decode) {
@@ -683,7 +758,7 @@ int main(int argc, char** argv) {
             ptrs.push_back(items[i].samples.data());
             lens.push_back(items[i].samples.size());
         }
-        if (overview || timeline || levels || tempo_map || sections) {
+        if (overview || timeline || levels || tempo_map || sections || loudness) {
             // the requests entry reads device-resident tracks: upload each group to the first device of
             // the mask in parts of at most 512 tracks or 2 Gi samples
             int dev = 0;
@@ -762,6 +837,10 @@ int main(int argc, char** argv) {
             if (!o.sections.empty()) {
                 std::fputs(",\"sections\":", stdout);
                 std::fputs(o.sections.c_str(), stdout);
+            }
+            if (!o.loudness.empty()) {
+                std::fputs(",\"loudness\":", stdout);
+                std::fputs(o.loudness.c_str(), stdout);
             }
             std::fputs("}\n", stdout);
         } else {

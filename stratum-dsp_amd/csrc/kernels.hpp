@@ -320,6 +320,27 @@ void launch_levels_gain(const unsigned int* peak_bits, const float* sums, const 
 void launch_silence_map(const float* rms, const uint64_t* frame_pfx, const uint64_t* base_pfx, int stride, int T,
                         const uint64_t* n_raw, int hop, float thr, uint64_t min_frames, const uint64_t* cap_pfx,
                         uint64_t* regions, int* count, uint64_t* pfx, uint64_t* dense, hipStream_t st);
+// ---- k_r128: the programme loudness request (r128_core.hpp has the arithmetic, R128Params, R128Folds) ----
+struct R128Params;
+struct R128Folds;
+struct R128StepArgs {
+    const float* x;
+    const uint64_t* in_off;
+    const uint64_t* n_raw;
+    const uint64_t* bpfx;  // workgroups before track t (r128_step_blocks of its steps); [T] in all
+    const uint64_t* zpfx;  // steps before track t; [T] in all
+    float* z;              // step j of track t -> z[zpfx[t] + j]
+    int T;
+};
+uint64_t r128_step_blocks(uint64_t J);  // workgroups of a track of J steps
+uint64_t r128_peak_blocks(uint64_t n);  // workgroups of a track of n samples
+void launch_r128_steps(const R128StepArgs& A, uint64_t n_blocks, const R128Params& P, hipStream_t st);
+// peak_bits: 2 * T words, zeroed here; [t] the sample peak's bits, [T + t] the true peak's (0 without tp)
+void launch_r128_peak(const float* x, const uint64_t* in_off, const uint64_t* n_raw, const uint64_t* cpfx, int T,
+                      uint64_t n_blocks, const R128Params& P, bool tp, unsigned int* peak_bits, hipStream_t st);
+// track t's folds to out[t]; curves (or NULL): its momentary blocks at curves[cvpfx[t] ...], the short-term behind
+void launch_r128_track(const float* z, const uint64_t* zpfx, const uint64_t* cvpfx, int T, const R128Params& P,
+                       R128Folds* out, float* curves, hipStream_t st);
 void launch_frame_rms(const float* x, const uint64_t* src_off, const float* gain, const uint64_t* n_len,
                       const uint64_t* frame_pfx, int T, uint64_t total, int fs, int hop, float* rms, hipStream_t st, bool per_frame_kernel = false);
 // base_pfx / stride: trim frame f of track t at rms[base_pfx[t] + f * stride] (default: frame_pfx, 1)

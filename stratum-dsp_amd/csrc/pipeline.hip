@@ -70,6 +70,7 @@ void Pipeline::run(const float* d_samples, const std::vector<uint64_t>& in_off, 
     if (lv_out_) lv_out_->assign(T, TrackLv{});
     if (tm_out_) tm_out_->assign(T, TrackTm{});
     if (sc_out_) sc_out_->assign(T, TrackSc{});
+    if (r128_out_) r128_out_->assign(T, TrackR128{});
     const std::string why = check_supported(cfg_, sr_);
     for (size_t i = 0; i < T; i++) {
         if (n_raw[i] == 0) {
@@ -115,6 +116,8 @@ void Pipeline::run(const float* d_samples, const std::vector<uint64_t>& in_off, 
         levels_prepass(d_samples, in_off, n_raw, res);
     else if (cfg_.enable_normalization && cfg_.normalization != SDSP_NORM_PEAK && why.empty())
         loudness_prepass(d_samples, in_off, n_raw, res);
+    // the programme loudness kernels, on the vote stream beside the first sub-batch (nothing without a request)
+    if (r128_out_ && why.empty()) r128_prepass(d_samples, in_off, n_raw, res);
     // equal shares: the fewest sub-batches that fit the budget, each near total / count (a
     // short last sub-batch runs at a fraction of the chip)
     std::vector<double> need(T, 0.0);
@@ -137,6 +140,7 @@ void Pipeline::run(const float* d_samples, const std::vector<uint64_t>& in_off, 
             need[i] += (double)tm_segment_capacity((uint64_t)n, sr_) * sizeof(TmSeg) + n / std::max<uint32_t>(sr_, 1) * 16.0 * 4.0;
         if (sc_out_ && !bpm_only_)  // both parities' cell means, novelty and flags
             need[i] += (n / (double)sc_Cs_ + 1.0) * 2.0 * (12.0 * 4.0 + 4.0 + 4.0 + 1.0);
+        if (r128_out_) need[i] += n / (double)std::max<uint32_t>(sr_ / 10, 1) * 12.0 + 64.0;  // z and both curves
         total_need += need[i];
     }
     const double parts = std::max(1.0, std::ceil(total_need / budget));
@@ -160,6 +164,7 @@ void Pipeline::run(const float* d_samples, const std::vector<uint64_t>& in_off, 
     // otherwise by run_locked
     rerun_tail(finish_key(res, true), res);
     levels_join();  // the one join of the levels folds (nothing without a request)
+    r128_join();    // ... and of the programme loudness kernels
     times_.total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     times_.key_reruns = reruns_;  // in-flight reruns (rerun_near), their time inside total_ms
     times_.rerun_ms = rerun_ms_;

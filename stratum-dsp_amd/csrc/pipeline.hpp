@@ -23,6 +23,7 @@
 #include "../../include/stratum_hip_debug.h"
 #include "kernels.hpp"
 #include "levels_core.hpp"
+#include "r128_core.hpp"
 #include "sections_core.hpp"
 #include "tempo_map_core.hpp"
 #include "sdsp_runtime.hpp"
@@ -530,6 +531,27 @@ struct LevelsPending {
     std::unique_ptr<Timers> tm;  // events 0-1: the first launch (peak and folds), 1-2: the second
 };
 
+// One track's programme loudness on the host (sdsp_r128 with its curves still in vectors).  `on`:
+// the track was measured (n > 0, a supported configuration), whatever its analysis status.
+struct TrackR128 {
+    bool on = false;
+    sdsp_r128 r{};
+    std::vector<float> curves;  // momentary blocks, then short-term blocks (SDSP_R128_CURVES)
+};
+// The programme loudness kernels as queued before the sub-batches (Pipeline::r128_prepass) and read
+// at the call's end (Pipeline::r128_join); nothing is queued without a request.
+struct R128Pending {
+    bool on = false;
+    std::vector<size_t> at;  // result slot of each measured track
+    std::vector<uint64_t> n, cvpfx;
+    R128Params P{};
+    unsigned int* d_peak = nullptr;
+    R128Folds* d_folds = nullptr;
+    float* d_curves = nullptr;
+    uint64_t steps = 0;
+    std::unique_ptr<Timers> tm;  // events 0-1: the steps, 1-2: the per-track kernel, 2-3: the peaks
+};
+
 }  // namespace detail
 using namespace detail;
 
@@ -601,6 +623,14 @@ class Pipeline {
         sc_out_ = out;
     }
 
+    // Before run(): also measure every track's programme loudness (include/stratum_hip.h, sdsp_r128;
+    // `what` checked by r128_request_error) into *out, one entry per track of the call.  A pipeline
+    // without a request queues nothing for it; nested pipelines get none.
+    void set_r128(uint32_t what, std::vector<TrackR128>* out) {
+        r128_what_ = what;
+        r128_out_ = out;
+    }
+
    private:
     Ctx c_;
     DeviceCtx& d_;
@@ -646,6 +676,9 @@ class Pipeline {
     sdsp_sections_request sc_req_{};
     uint64_t sc_Cs_ = 0;
     std::vector<TrackSc>* sc_out_ = nullptr;  // the call's sections (set_sections), else nullptr
+    uint32_t r128_what_ = 0;
+    std::vector<TrackR128>* r128_out_ = nullptr;  // the call's programme loudness (set_r128), else nullptr
+    R128Pending r128_pending_;
     bool map_on() const { return lv_out_ && (lv_what_ & SDSP_LEVELS_SILENCE_MAP); }
 
     // force_legacy_bpm skips the tempogram estimate (src/lib.rs:337): no escalation, no
@@ -663,6 +696,10 @@ class Pipeline {
     void levels_prepass(const float* d_samples, const std::vector<uint64_t>& in_off, const std::vector<uint64_t>& n_raw,
                         std::vector<TrackRes>& res);
     void levels_join();
+    // pipeline_r128.hip
+    void r128_prepass(const float* d_samples, const std::vector<uint64_t>& in_off, const std::vector<uint64_t>& n_raw,
+                      const std::vector<TrackRes>& res);
+    void r128_join();
     void sub_batch(const float* d_samples, const std::vector<uint64_t>& in_off, const std::vector<uint64_t>& n_raw,
                    const std::vector<int>& idx, std::vector<TrackRes>& res);
     Front front(const float* d_samples, const std::vector<uint64_t>& in_off, const std::vector<uint64_t>& n_raw,

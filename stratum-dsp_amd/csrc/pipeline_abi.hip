@@ -313,6 +313,28 @@ void fill_sections(const TrackSc& t, const TrackRes& r, uint32_t sr, const ScCal
     }
 }
 
+// A checked programme loudness request and where the results go.
+struct R128Call {
+    uint32_t what = 0;
+    sdsp_r128* out = nullptr;
+};
+// One track's programme loudness: every field for a measured track (TrackR128::on: status SDSP_OK
+// whatever the analysis status), else the analysis status and zeroed fields.  Both curves share one
+// block, the momentary curve first.
+void fill_r128(const TrackR128& t, int status, sdsp_r128* o) {
+    std::memset(o, 0, sizeof(*o));
+    o->status = t.on ? (int32_t)SDSP_OK : status;
+    if (!t.on) return;
+    *o = t.r;
+    o->momentary = o->short_term = nullptr;
+    if (t.curves.empty()) return;
+    float* blk = (float*)std::malloc(t.curves.size() * sizeof(float));
+    if (!blk) throw std::bad_alloc();
+    std::memcpy(blk, t.curves.data(), t.curves.size() * sizeof(float));
+    o->momentary = blk;
+    o->short_term = blk + o->n_momentary;
+}
+
 // One device-resident batch on `device`.  The engine's main stream first waits for `user_stream`
 // (everything queued on it so far) and for `wait_ev` (a copy's completion), whichever are given.
 // The batch on a context whose mutex the caller holds (run_device, and sdsp_analyze_audio's
@@ -321,7 +343,7 @@ int32_t run_locked(DeviceCtx& d, const float* d_samples, const uint64_t* offsets
                    uint32_t sr, const sdsp_config* cfg, void* user_stream, sdsp_result* outs, int stages,
                    hipEvent_t wait_ev, const sdsp_overview_request* req = nullptr, sdsp_overview* ovs = nullptr,
                    const KtCall* ktc = nullptr, const LvCall* lvc = nullptr, const TmCall* tmc = nullptr,
-                   const ScCall* scc = nullptr) {
+                   const ScCall* scc = nullptr, const R128Call* rc = nullptr) {
     if (stages != SDSP_STAGES_FULL && stages != SDSP_STAGES_BPM_ONLY) throw HipError("unknown stage mask");
     if (user_stream) {
         hipEvent_t ev;
@@ -349,6 +371,9 @@ int32_t run_locked(DeviceCtx& d, const float* d_samples, const uint64_t* offsets
     std::vector<TrackSc> scl;
     d.last_sc = sdsp_debug_sections_times{};
     if (scc) p.set_sections(scc->req, scc->Cs, &scl);
+    std::vector<TrackR128> r128l;
+    d.last_r128 = sdsp_debug_r128_times{};
+    if (rc) p.set_r128(rc->what, &r128l);
     try {
         p.run(d_samples, off, ln, res);
         // Certified block energies: a track whose key vote had an energy-dependent
@@ -405,6 +430,8 @@ int32_t run_locked(DeviceCtx& d, const float* d_samples, const uint64_t* offsets
         for (uint64_t i = 0; i < n; i++) fill_tempo_map(tml[(size_t)i], res[(size_t)i].status, &tmc->out[i]);
     if (scc)
         for (uint64_t i = 0; i < n; i++) fill_sections(scl[(size_t)i], res[(size_t)i], sr, *scc, &scc->out[i]);
+    if (rc)
+        for (uint64_t i = 0; i < n; i++) fill_r128(r128l[(size_t)i], res[(size_t)i].status, &rc->out[i]);
     return SDSP_OK;
 }
 
@@ -413,12 +440,12 @@ int32_t run_device(int device, const float* d_samples, const uint64_t* offsets, 
                    int stages = SDSP_STAGES_FULL, hipEvent_t wait_ev = nullptr,
                    const sdsp_overview_request* req = nullptr, sdsp_overview* ovs = nullptr,
                    const KtCall* ktc = nullptr, const LvCall* lvc = nullptr, const TmCall* tmc = nullptr,
-                   const ScCall* scc = nullptr) {
+                   const ScCall* scc = nullptr, const R128Call* rc = nullptr) {
     DeviceCtx& d = device_ctx(device);
     std::lock_guard<std::mutex> lk(d.mu);
     SDSP_HIP_CHECK(hipSetDevice(device));
     return run_locked(d, d_samples, offsets, lens, n, sr, cfg, user_stream, outs, stages, wait_ev, req, ovs, ktc, lvc,
-                      tmc, scc);
+                      tmc, scc, rc);
 }
 
 }  // namespace
@@ -610,7 +637,10 @@ int32_t sdsp_analyze_batch_device_with(const float* d_samples, const uint64_t* o
     const sdsp_sections_request* sc_req = nullptr;  // (sdsp_request_set_ext's pair, when struct_size covers it)
     sdsp_sections* sections = nullptr;
     if (!set_err) request_set_ext_read(caller_set, &sc_req, &sections);
-    if (!set_err && !ov_req && !kt_req && !lv_req && !tm_req && !sc_req)
+    const sdsp_r128_request* r128_req = nullptr;  // (sdsp_request_set_ext2's pair, likewise)
+    sdsp_r128* r128 = nullptr;
+    if (!set_err) request_set_ext2_read(caller_set, &r128_req, &r128);
+    if (!set_err && !ov_req && !kt_req && !lv_req && !tm_req && !sc_req && !r128_req)
         return sdsp_analyze_batch_device_ex(d_samples, offsets, lens, n_tracks, sample_rate, cfg, device, stream, stages,
                                             outs);
     auto fail_all = [&](int32_t status, const char* text) {
@@ -637,6 +667,10 @@ int32_t sdsp_analyze_batch_device_with(const float* d_samples, const uint64_t* o
             if (sc_req && sections) {
                 std::memset(&sections[i], 0, sizeof(sections[i]));
                 sections[i].status = status;
+            }
+            if (r128_req && r128) {
+                std::memset(&r128[i], 0, sizeof(r128[i]));
+                r128[i].status = status;
             }
         }
         return status;
@@ -689,13 +723,20 @@ int32_t sdsp_analyze_batch_device_with(const float* d_samples, const uint64_t* o
         sc.req = *sc_req;
         sc.out = sections;
     }
+    R128Call rc;
+    if (r128_req) {
+        if (const char* why = r128_request_error(r128_req->what, r128 != nullptr, sample_rate))
+            return fail_all(SDSP_ERR_INVALID_INPUT, why);
+        rc.what = r128_req->what;
+        rc.out = r128;
+    }
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
         return fail_all(SDSP_ERR_PROCESSING, "Processing error: no HIP device");
     try {
         return run_device(device, d_samples, offsets, lens, n_tracks, sample_rate, cfg, stream, outs, stages, nullptr,
                           ov_req, overviews, kt_req ? &kc : nullptr, lv_req ? &lc : nullptr, tm_req ? &tc : nullptr,
-                          sc_req ? &sc : nullptr);
+                          sc_req ? &sc : nullptr, r128_req ? &rc : nullptr);
     } catch (const std::exception& e) {
         std::fprintf(stderr, "sdsp_analyze_batch_device_with: %s\n", e.what());
         char text[256];
@@ -710,6 +751,24 @@ void sdsp_sections_free(sdsp_sections* s) {
     s->sections = nullptr;
     s->novelty = s->energy = nullptr;
     s->n_sections = s->n_curve = 0;
+}
+
+void sdsp_r128_free(sdsp_r128* r) {
+    if (!r) return;
+    std::free(r->momentary);  // one block (fill_r128), the momentary curve first
+    r->momentary = r->short_term = nullptr;
+}
+
+int32_t sdsp_debug_last_r128_times(int32_t device, sdsp_debug_r128_times* out) {
+    try {
+        if (!out) return SDSP_ERR_INVALID_INPUT;
+        DeviceCtx& d = device_ctx(device);
+        std::lock_guard<std::mutex> lk(d.mu);
+        *out = d.last_r128;
+        return SDSP_OK;
+    } catch (const std::exception&) {
+        return SDSP_ERR_PROCESSING;
+    }
 }
 
 int32_t sdsp_debug_last_sections_times(int32_t device, sdsp_debug_sections_times* out) {

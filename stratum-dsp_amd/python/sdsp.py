@@ -20,7 +20,8 @@ from sdsp_abi import (ERROR_NAMES, FLAG_NAMES, SdspAudioDecodeStats, SdspConfide
                       SdspKeyTimelineRequest, SdspDebugLevelsTimes, SdspLevels, SdspLevelsRequest, SdspLoudness,
                       SdspRequestSet, SdspSilenceRegion, LEVELS_BITS, SdspDebugTempoMapTimes, SdspTempoMap,
                       SdspTempoMapRequest, SdspTempoSegment, TEMPO_MAP_BITS, SdspDebugSectionsOut,
-                      SdspDebugSectionsTimes, SdspSection, SdspSections, SdspSectionsRequest, SECTIONS_BITS, SdspRequestSetExt)
+                      SdspDebugSectionsTimes, SdspSection, SdspSections, SdspSectionsRequest, SECTIONS_BITS, SdspRequestSetExt,
+                      SdspDebugR128Times, SdspR128, SdspR128Request, SdspRequestSetExt2, R128_BITS)
 
 PKG = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LIB_PATH = os.environ.get("SDSP_LIB_PATH") or os.path.join(PKG, "lib", "libstratum_hip.so")  # override: layout/ablation builds
@@ -96,6 +97,10 @@ def _load(path):
         L.sdsp_sections_free.restype = None
         L.sdsp_debug_last_sections_times.argtypes = [C.c_int32, C.POINTER(SdspDebugSectionsTimes)]
         L.sdsp_debug_last_sections_times.restype = C.c_int32
+        L.sdsp_r128_free.argtypes = [C.POINTER(SdspR128)]
+        L.sdsp_r128_free.restype = None
+        L.sdsp_debug_last_r128_times.argtypes = [C.c_int32, C.POINTER(SdspDebugR128Times)]
+        L.sdsp_debug_last_r128_times.restype = C.c_int32
         L.sdsp_tempo_map_free.argtypes = [C.POINTER(SdspTempoMap)]
         L.sdsp_tempo_map_free.restype = None
         L.sdsp_debug_last_tempo_map_times.argtypes = [C.c_int32, C.POINTER(SdspDebugTempoMapTimes)]
@@ -806,9 +811,49 @@ def sections_times(device=0):
     return {k: getattr(t, k) for k, _ in SdspDebugSectionsTimes._fields_}
 
 
+R128_FLOATS = ("integrated_lufs", "range_lu", "range_low_lufs", "range_high_lufs", "max_momentary_lufs",
+               "max_short_term_lufs", "sample_peak", "true_peak", "sample_peak_db", "true_peak_dbtp")
+R128_INTS = ("status", "has_integrated", "has_range", "n_samples", "step_samples", "n_steps", "n_momentary", "n_short_term",
+             "n_gated_momentary", "n_gated_short_term")
+
+
+def loudness_request(what=("loudness", "true-peak")):
+    """An sdsp_r128_request: `what` is a mask of sdsp_r128_what bits, or names out of loudness,
+    true-peak, curves."""
+    if not isinstance(what, int):
+        mask = 0
+        for name in what:
+            mask |= R128_BITS[name]
+        what = mask
+    return SdspR128Request(what)
+
+
+def r128_to_dict(r):
+    """One sdsp_r128: its integer fields as int, its floats as np.float32, `shelf` and `highpass`
+    float32 arrays of b0 b1 b2 a1 a2, `momentary` and `short_term` float32 arrays (empty without the
+    curves)."""
+    d = {k: int(getattr(r, k)) for k in R128_INTS}
+    for k in R128_FLOATS:
+        d[k] = np.float32(getattr(r, k))
+    d["shelf"] = np.array(list(r.shelf), np.float32)
+    d["highpass"] = np.array(list(r.highpass), np.float32)
+    d["momentary"] = _records(r.momentary, d["n_momentary"] if r.momentary else 0, C.c_float).astype(np.float32)
+    d["short_term"] = _records(r.short_term, d["n_short_term"] if r.momentary else 0, C.c_float).astype(np.float32)
+    return d
+
+
+def r128_times(device=0):
+    """sdsp_debug_last_r128_times: the event times of the three programme loudness kernels of the
+    last call with a loudness request on `device`."""
+    t = SdspDebugR128Times()
+    if lib().sdsp_debug_last_r128_times(device, C.byref(t)) != 0:
+        raise RuntimeError("sdsp_debug_last_r128_times failed")
+    return {k: getattr(t, k) for k, _ in SdspDebugR128Times._fields_}
+
+
 def analyze_batch_device_with(d_ptr, offsets, lens, sample_rate=44100, config=None, device=0, stream=None,
                               stages=STAGES_FULL, overview=None, key_timeline=None, levels=None, request_set=True,
-                              tempo_map=None, sections=None):
+                              tempo_map=None, sections=None, loudness=None):
     """sdsp_analyze_batch_device_with: analyze_batch_device(raw=True) with any of the optional
     requests: an SdspOverviewRequest, an SdspKeyTimelineRequest, an SdspLevelsRequest
     (levels_request()), an SdspTempoMapRequest (tempo_map_request()); None leaves a request out.
@@ -816,7 +861,8 @@ def analyze_batch_device_with(d_ptr, offsets, lens, sample_rate=44100, config=No
     with a tempo map request a fifth element, the tempo maps: levels[i] a levels_to_dict(), maps[i]
     a tempo_map_to_dict(); each list [] without its request.  Raises AnalysisError when the call as
     a whole fails (a refused request).  With a sections request (sections_request()) the sections,
-    each a sections_to_dict(), are one more element at the end of the tuple."""
+    each a sections_to_dict(), are one more element at the end of the tuple, and with a loudness
+    request (loudness_request()) the programme loudness, each an r128_to_dict(), one more after that."""
     offs = np.ascontiguousarray(offsets, dtype=np.uint64)
     ln = np.ascontiguousarray(lens, dtype=np.uint64)
     n = ln.size
@@ -828,9 +874,12 @@ def analyze_batch_device_with(d_ptr, offsets, lens, sample_rate=44100, config=No
     scs = (SdspSections * max(n, 1))() if sections is not None else None
     cfg = config if config is not None else default_config()
     _schedule_from_env()
-    ext = SdspRequestSetExt()  # (a call without a sections request passes the plain set's size)
+    r128s = (SdspR128 * max(n, 1))() if loudness is not None else None
+    ext2 = SdspRequestSetExt2()  # (a call without the later requests passes the older structs' sizes)
+    ext = ext2.base
     rs = ext.base
-    rs.struct_size = C.sizeof(SdspRequestSetExt if sections is not None else SdspRequestSet)
+    rs.struct_size = C.sizeof(SdspRequestSetExt2 if loudness is not None else
+                              SdspRequestSetExt if sections is not None else SdspRequestSet)
     if overview is not None:
         rs.ov_req = C.pointer(overview)
         rs.overviews = ovs
@@ -846,13 +895,16 @@ def analyze_batch_device_with(d_ptr, offsets, lens, sample_rate=44100, config=No
     if sections is not None:
         ext.sc_req = C.pointer(sections)
         ext.sections = scs
+    if loudness is not None:
+        ext2.r128_req = C.pointer(loudness)
+        ext2.r128 = r128s
     u64p = C.POINTER(C.c_uint64)
     st = lib().sdsp_analyze_batch_device_with(C.c_void_p(d_ptr), offs.ctypes.data_as(u64p), ln.ctypes.data_as(u64p), n,
                                               sample_rate, C.byref(cfg), device, C.c_void_p(stream or 0), stages, outs,
                                               C.byref(rs) if request_set else None)
     if st != 0:
         raise AnalysisError(st, _batch_error(outs, n, "device batch failed"))
-    overviews, timelines, lv, maps, secs = [], [], [], [], []
+    overviews, timelines, lv, maps, secs, louds = [], [], [], [], [], []
     for i in range(n if request_set else 0):
         if ovs is not None:
             overviews.append(overview_to_dict(ovs[i]))
@@ -869,11 +921,16 @@ def analyze_batch_device_with(d_ptr, offsets, lens, sample_rate=44100, config=No
         if scs is not None:
             secs.append(sections_to_dict(scs[i]))
             lib().sdsp_sections_free(C.byref(scs[i]))
+        if r128s is not None:
+            louds.append(r128_to_dict(r128s[i]))
+            lib().sdsp_r128_free(C.byref(r128s[i]))
     ret = (ResultBatch(outs, n), overviews, timelines, lv)
     if tempo_map is not None:
         ret += (maps,)
     if sections is not None:
         ret += (secs,)
+    if loudness is not None:
+        ret += (louds,)
     return ret
 
 

@@ -598,6 +598,65 @@ class SdspRequestSetExt(C.Structure):
     ]
 
 
+R128_LOUDNESS, R128_TRUE_PEAK, R128_CURVES = 1, 2, 4
+R128_BITS = {"loudness": R128_LOUDNESS, "true-peak": R128_TRUE_PEAK, "curves": R128_CURVES}
+
+
+class SdspR128Request(C.Structure):
+    """sdsp_r128_request: a mask of sdsp_r128_what bits."""
+
+    _fields_ = [("what", u32)]
+
+
+class SdspR128(C.Structure):
+    """sdsp_r128: one track's programme loudness (the two curves library-owned, one allocation)."""
+
+    _fields_ = [
+        ("status", C.c_int32),
+        ("has_integrated", C.c_int8),
+        ("has_range", C.c_int8),
+        ("integrated_lufs", f32),
+        ("range_lu", f32),
+        ("range_low_lufs", f32),
+        ("range_high_lufs", f32),
+        ("max_momentary_lufs", f32),
+        ("max_short_term_lufs", f32),
+        ("sample_peak", f32),
+        ("true_peak", f32),
+        ("sample_peak_db", f32),
+        ("true_peak_dbtp", f32),
+        ("n_samples", u64),
+        ("step_samples", u32),
+        ("n_steps", u64),
+        ("n_momentary", u64),
+        ("n_short_term", u64),
+        ("n_gated_momentary", u64),
+        ("n_gated_short_term", u64),
+        ("shelf", f32 * 5),
+        ("highpass", f32 * 5),
+        ("momentary", C.POINTER(f32)),
+        ("short_term", C.POINTER(f32)),
+    ]
+
+
+class SdspRequestSetExt2(C.Structure):
+    """sdsp_request_set_ext2: sdsp_request_set_ext, then the pair added after sections.  Pass
+    byref(ext2.base.base) with ext2.base.base.struct_size = sizeof(ext2)."""
+
+    _fields_ = [
+        ("base", SdspRequestSetExt),
+        ("r128_req", C.POINTER(SdspR128Request)),
+        ("r128", C.POINTER(SdspR128)),
+    ]
+
+
+class SdspDebugR128Times(C.Structure):
+    """sdsp_debug_r128_times (include/stratum_hip_debug.h)."""
+
+    _fields_ = [("steps_ms", C.c_double), ("peak_ms", C.c_double), ("track_ms", C.c_double), ("tracks", u64),
+                ("steps", u64)]
+
+
 class SdspDebugLevelsTimes(C.Structure):
     """sdsp_debug_levels_times (include/stratum_hip_debug.h)."""
 
