@@ -818,6 +818,98 @@ typedef struct sdsp_request_set_ext2 {
 } sdsp_request_set_ext2;
 
 /*
+ * ---- Fingerprints: a chroma fingerprint per track and the duplicate pairs of an analysis call ----
+ *
+ * The one request that relates the tracks of a call to each other: the same recording twice (another
+ * encoding, a re-download, a rip with a different lead-in).  A gain-invariant binary fingerprint from
+ * short cells of the smoothed chroma rows, and every pair of the call's tracks compared on the device
+ * at every alignment within max_offset_words.  The reference has no counterpart; this definition is
+ * the contract.  Every output is an integer or one f32 quotient of two integers.
+ *
+ * What the numbers are: on synthetic material (24 s of non-repeating random triads, default
+ * configuration, Cs = 5512, max_offset_words = 16, min_overlap_words = 32; CPU numbers of
+ * tests/fingerprint_ref.py over the oracle's rows, tests/test_fingerprint_ref.py) copies of a track
+ * with another gain, white noise 30 and 20 dB below its level or up to half a second cut from its
+ * start read a bit error rate of at most 0.194 at the right offset (the noise 20 dB below), unrelated
+ * tracks at least 0.460 at their best; at Cs = 11025 at most 0.171 and at least 0.442.  These are the
+ * values that test measures.  That is no claim about real music; max_ber is the caller's decision.
+ *
+ * Scope: a track whose key path runs (SDSP_STAGES_FULL, trimmed length n >= frame_size and n >= the
+ * key STFT's frame size).  kfs, khop, F and the rows C[f][0..12) are exactly as sdsp_key_timeline
+ * defines them.  All float arithmetic is f32, sums start from 0 in ascending order, multiply and add
+ * are separate operations.
+ * Cells: Cs = cell_samples, or (u64)(cell_seconds * (f32)sample_rate); exactly one of the two is given
+ *   (a form is given when its field is not 0).  khop <= Cs < 2^31.  n_cells = (F * khop) / Cs (integer
+ *   division).  Cell c owns the key frames whose start f * khop lies in [c Cs, (c + 1) Cs), and
+ *   m[c][i] = (sum over the cell's frames of C[f][i]) / (f32)count: the sections request's cell rule
+ *   and fold over the key frames alone.
+ * Words: W = n_cells >= 3 ? n_cells - 2 : 0.  For w in [0, W), i in [0, 12), j = (i + 1) % 12, with
+ *   d(c) = m[c][i] - m[c][j]: bit i of word[w] is (d(w + 1) - d(w)) > 0, bit 12 + i is
+ *   (d(w + 2) - d(w)) > 0, bits 24 to 31 are 0.  The twelve cyclic differences of a lag sum to zero, so
+ *   a word is 0 exactly where the cell means did not move: silence, or a held constant (whose means
+ *   are equal when the cells own equally many frames or their sums are exact; cells of 43 and of 44
+ *   frames may round the mean of one value apart by an ulp and set bits).
+ * Pairs: tracks a < b of the call, both with analysis status SDSP_OK and W >= 1; O = max_offset_words
+ *   (0 to 255).  For o in [-O, O] the positions p run over [max(0, -o), min(W_a, W_b - o)); p is
+ *   counted when (A[p] | B[p + o]) != 0; n(o) is the number of counted positions, e(o) the sum of
+ *   popcount(A[p] ^ B[p + o]) over them.  o is eligible when n(o) >= max(min_overlap_words, 1).  The
+ *   best offset minimises e / n (e1 * n2 < e2 * n1 in u64); on equality the smaller |o|, then the
+ *   negative one.  A pair without an eligible offset has no best offset.  ber = (f32)e / (f32)(24 * n);
+ *   the pair is a match when it has a best offset and ber <= max_ber.
+ * Outputs: per track an sdsp_fingerprint (words with SDSP_FP_WORDS, else NULL; n_matches the matches
+ *   the track takes part in, 0 without SDSP_FP_MATCH); per call, with SDSP_FP_MATCH, one
+ *   sdsp_fingerprint_matches: n_compared the tracks with status SDSP_OK and W >= 1, n_pairs =
+ *   n_compared (n_compared - 1) / 2, and the matches sorted by (a, b).  offset_samples =
+ *   (first_sample_b + o * Cs) - first_sample_a: sample s of a's caller buffer meets sample
+ *   s + offset_samples of b's.  bits_compared = 24 n.
+ * Per track: an analysis status other than SDSP_OK gives that status and zeroed fields (cell_samples
+ * aside) and the track is not compared; a track whose key path is skipped gives n_cells 0.  A track of
+ * 2^27 words or more fails the call.
+ */
+enum sdsp_fingerprint_what { SDSP_FP_WORDS = 1, SDSP_FP_MATCH = 2 }; /* bits of sdsp_fingerprint_request.what */
+typedef struct sdsp_fingerprint_request {
+    uint32_t what;
+    float cell_seconds;         /* the seconds form of Cs */
+    uint64_t cell_samples;      /* the samples form of Cs */
+    uint32_t max_offset_words;  /* O */
+    uint32_t min_overlap_words;
+    float max_ber;
+} sdsp_fingerprint_request;
+
+typedef struct sdsp_fingerprint {
+    int32_t status;             /* the track's sdsp_status */
+    uint64_t n_cells, n_words, cell_samples;
+    uint64_t first_sample;      /* trim start in the caller's track, as in sdsp_overview */
+    uint64_t n_matches;
+    uint32_t* words;            /* library-owned; NULL without SDSP_FP_WORDS */
+} sdsp_fingerprint;
+
+typedef struct sdsp_fingerprint_match {
+    uint64_t a, b;              /* track indices in the call, a < b */
+    int32_t offset_words;
+    int64_t offset_samples;
+    uint64_t bit_errors, bits_compared;
+    float ber;
+} sdsp_fingerprint_match;
+
+typedef struct sdsp_fingerprint_matches {
+    uint64_t n_compared, n_pairs, n_matches;
+    sdsp_fingerprint_match* matches; /* library-owned, sorted by (a, b) */
+} sdsp_fingerprint_matches;
+
+/*
+ * The request set with the fields added after programme loudness: it begins with
+ * sdsp_request_set_ext2, as that one begins with sdsp_request_set_ext.  Pass &ext3.base.base.base with
+ * its struct_size = sizeof(ext3); the library reads fp_req / fingerprints / fp_matches only when
+ * struct_size covers them, so callers that pass any of the three older structs keep working.
+ */
+typedef struct sdsp_request_set_ext3 {
+    sdsp_request_set_ext2 base;
+    const sdsp_fingerprint_request* fp_req;  sdsp_fingerprint* fingerprints;
+    sdsp_fingerprint_matches* fp_matches;    /* one struct per call; needed with SDSP_FP_MATCH */
+} sdsp_request_set_ext3;
+
+/*
  * sdsp_analyze_batch_device_ex with any of the optional requests from one analysis: overviews and
  * key timelines as in sdsp_analyze_batch_device_requests (which forwards here), levels (n_tracks
  * entries, freed one by one with sdsp_levels_free) as above, with SDSP_STAGES_FULL and
@@ -839,6 +931,13 @@ typedef struct sdsp_request_set_ext2 {
  * as above, with SDSP_STAGES_FULL and SDSP_STAGES_BPM_ONLY alike.  Also refused with
  * SDSP_ERR_INVALID_INPUT: what == 0 or unknown bits; SDSP_R128_CURVES without SDSP_R128_LOUDNESS; no
  * output array; a sample rate under 8000 Hz.
+ * Fingerprints (sdsp_request_set_ext3: n_tracks entries, freed one by one with sdsp_fingerprint_free,
+ * and one sdsp_fingerprint_matches, freed with sdsp_fingerprint_matches_free) as above.  Also refused
+ * with SDSP_ERR_INVALID_INPUT: what == 0 or unknown bits; both cell forms or neither; a float that is
+ * not finite or is negative; max_ber > 1; Cs < khop or Cs >= 2^31; max_offset_words > 255;
+ * SDSP_FP_MATCH without the matches struct; no output array; SDSP_STAGES_BPM_ONLY.  With
+ * SDSP_ERR_NOT_IMPLEMENTED: enable_key_beat_synchronous without enable_key_log_frequency.
+ * force_legacy_bpm is accepted: no frame energies are used.
  */
 int32_t sdsp_analyze_batch_device_with(const float* d_samples, const uint64_t* offsets, const uint64_t* lens,
                                        uint64_t n_tracks, uint32_t sample_rate, const sdsp_config* cfg,
@@ -852,6 +951,9 @@ void sdsp_tempo_map_free(sdsp_tempo_map* m);
 void sdsp_sections_free(sdsp_sections* s);
 /* Frees the curves owned by one sdsp_r128 (they share one allocation: never free() them one by one). */
 void sdsp_r128_free(sdsp_r128* r);
+/* Frees the words owned by one sdsp_fingerprint, and the list owned by one sdsp_fingerprint_matches. */
+void sdsp_fingerprint_free(sdsp_fingerprint* f);
+void sdsp_fingerprint_matches_free(sdsp_fingerprint_matches* m);
 
 /*
  * Synthetic track generator on device: writes n_tracks tracks of `len`

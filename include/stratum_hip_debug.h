@@ -358,6 +358,53 @@ typedef struct sdsp_debug_r128_times {
 int32_t sdsp_debug_last_r128_times(int32_t device, sdsp_debug_r128_times* out);
 
 /*
+ * Stage probes of the fingerprint request (include/stratum_hip.h, sdsp_fingerprint).
+ *
+ * sdsp_debug_fingerprint: k_fp_cells and k_fp_words over uploaded rows, taken as the rows C of the
+ * definition.  host_chroma: the tracks' rows back to back, frames[t] rows of 12 floats for track t,
+ * khop samples apart (0 frames allowed).  req is checked as an analysis call checks it against khop
+ * (its `what` and match fields are not used).  Track t has n_cells[t] = frames[t] khop / Cs cells and
+ * n_words[t] words; out->m receives m[c][0..12) at 12 (P[t] + c) with P the prefix of n_cells,
+ * out->words word w at Q[t] + w with Q the prefix of n_words.  The caller sizes the arrays from the
+ * same plan; a call that needs more than the capacities is refused.
+ *
+ * sdsp_debug_fingerprint_match: k_fp_match over uploaded word arrays, every track compared: track t's
+ * n_words[t] words (>= 1 each) back to back in host_words.  rec receives n_tracks * n_tracks records,
+ * the pair (a, b), a < b, at a * n_tracks + b, the others zero; eligible == 0 (and the rest 0) for a
+ * pair without an eligible offset.  Only max_offset_words and min_overlap_words of the request are
+ * used: the records are before the max_ber filter.
+ */
+typedef struct sdsp_debug_fingerprint_out {
+    uint64_t cell_capacity, word_capacity;
+    uint64_t* n_cells; /* n_tracks */
+    uint64_t* n_words; /* n_tracks */
+    float* m;          /* 12 x cell_capacity */
+    uint32_t* words;   /* word_capacity */
+} sdsp_debug_fingerprint_out;
+int32_t sdsp_debug_fingerprint(const float* host_chroma, const uint64_t* frames, uint64_t n_tracks, uint32_t sample_rate,
+                               uint32_t khop, const sdsp_fingerprint_request* req, sdsp_debug_fingerprint_out* out,
+                               int32_t device);
+typedef struct sdsp_debug_fingerprint_pair {
+    int32_t offset_words;
+    uint32_t eligible, bit_errors, positions; /* has, e, n */
+} sdsp_debug_fingerprint_pair;
+int32_t sdsp_debug_fingerprint_match(const uint32_t* host_words, const uint64_t* n_words, uint64_t n_tracks,
+                                     const sdsp_fingerprint_request* req, sdsp_debug_fingerprint_pair* rec, int32_t device);
+
+/*
+ * The fingerprint kernels of the last sdsp_analyze_batch_device_with call with a fingerprint request
+ * on `device`: HIP event times of k_fp_cells and k_fp_words summed over the sub-batches (vote
+ * stream, so beside a running analysis they include what the kernels shared the device with) and of
+ * k_fp_match summed over its row bands (main stream, after the last join), the words written, the
+ * tracks compared and the pairs.  All zero after a call without a request.
+ */
+typedef struct sdsp_debug_fingerprint_times {
+    double cells_ms, words_ms, match_ms;
+    uint64_t words, compared, pairs;
+} sdsp_debug_fingerprint_times;
+int32_t sdsp_debug_last_fingerprint_times(int32_t device, sdsp_debug_fingerprint_times* out);
+
+/*
  * Stage probe of the candidate selection: the pipeline's own select launch (k_tempo_select with the
  * parameters an analysis call derives from cfg: Pipeline::pass_select from its offset tables on) over
  * uploaded tempogram lists instead of a novelty curve.  Per track t and variant v (full, low, mid,

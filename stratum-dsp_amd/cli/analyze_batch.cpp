@@ -48,10 +48,18 @@
 // (include/stratum_hip.h, sdsp_r128): BS.1770 integrated loudness, loudness range, maximum momentary
 // and short-term loudness and the sample peak; LIST out of true-peak (the 4x true peak) and curves
 // (the momentary and short-term mean squares per block).
+// --fingerprint[=CELL_SEC[:MAX_OFFSET_SEC[:MAX_BER]]] (opt-in; JSONL only): each line's object gets a
+// "fingerprint" member (include/stratum_hip.h, sdsp_fingerprint): the counts and the words as hex, and
+// one last line {"duplicates":[{"a":path,"b":path,"offset_seconds":..,"ber":..}, ...]} lists the pairs
+// of files within MAX_BER at their best alignment within MAX_OFFSET_SEC (sample s of a meets sample
+// s + offset_seconds * rate of b).  Files are compared within one analysis call: the files of one
+// sample rate, at most 512 at a time.  Defaults 0.125 s, 2 s, 0.30; at least 32 words must overlap.
 #include <algorithm>
 #include <atomic>
 #include <chrono>
 #include <map>
+#include <functional>
+#include <mutex>
 #include <thread>
 
 #include "cli_common.hpp"
@@ -79,6 +87,13 @@ struct Item {
     std::string tempo_map; // --tempo-map: the "tempo_map" member's value
     std::string sections;  // --sections: the "sections" member's value
     std::string loudness;  // --loudness: the "loudness" member's value
+    std::string fingerprint;  // --fingerprint: the "fingerprint" member's value
+};
+// --fingerprint: one matched pair of files (positions in the argument list, a < b)
+struct Dup {
+    size_t a, b;
+    double offset_seconds;
+    float ber;
 };
 
 // floats so that an f32 round-trips
@@ -275,6 +290,21 @@ std::string r128_json(const sdsp_r128& m, uint32_t what) {
     return s + "}";
 }
 
+std::string fingerprint_json(const sdsp_fingerprint& m) {
+    char b[256];
+    std::snprintf(b, sizeof b,
+                  "{\"status\":%d,\"n_cells\":%llu,\"n_words\":%llu,\"cell_samples\":%llu,\"first_sample\":%llu,"
+                  "\"n_matches\":%llu,\"words\":\"",
+                  m.status, (unsigned long long)m.n_cells, (unsigned long long)m.n_words, (unsigned long long)m.cell_samples,
+                  (unsigned long long)m.first_sample, (unsigned long long)m.n_matches);
+    std::string s = b;
+    for (uint64_t i = 0; m.words && i < m.n_words; i++) {  // six hex digits per 24-bit word
+        std::snprintf(b, sizeof b, "%06x", m.words[i]);
+        s += b;
+    }
+    return s + "\"}";
+}
+
 // percentile as the example computes it: sort, index round((len-1) * p)
 float percentile(std::vector<float> xs, float p) {
     std::sort(xs.begin(), xs.end());
@@ -368,6 +398,13 @@ int main(int argc, char** argv) {
     bool sections = false;
     sdsp_r128_request r128req{SDSP_R128_LOUDNESS};
     bool loudness = false;
+    sdsp_fingerprint_request fpreq{};
+    fpreq.what = SDSP_FP_WORDS | SDSP_FP_MATCH;
+    fpreq.cell_seconds = 0.125f;
+    fpreq.max_offset_words = 16;
+    fpreq.min_overlap_words = 32;
+    fpreq.max_ber = 0.30f;
+    bool fingerprint = false;
     std::vector<std::string> paths;
     for (size_t i = 0; i < a.size(); i++) {
         const std::string& s = a[i];
@@ -494,6 +531,34 @@ int main(int argc, char** argv) {
                 screq.min_strength = (float)v[4];
             }
             screq.snap_seconds = screq.cell_seconds;
+        } else if (s == "--fingerprint" || s.rfind("--fingerprint=", 0) == 0) {
+            fingerprint = true;
+            if (s.size() > 13) {  // =CELL_SEC[:MAX_OFFSET_SEC[:MAX_BER]]
+                const std::string w = s.substr(14);
+                double v[3] = {0.125, 2.0, 0.30};
+                int n = 0;
+                bool good = !w.empty();
+                for (size_t p0 = 0; good;) {
+                    const size_t p1 = std::min(w.find(':', p0), w.size());
+                    char* end = nullptr;
+                    const std::string part = w.substr(p0, p1 - p0);
+                    good = n < 3 && !part.empty();
+                    if (good) v[n] = std::strtod(part.c_str(), &end), good = end && *end == 0;
+                    n++;
+                    if (p1 == w.size()) break;
+                    p0 = p1 + 1;
+                }
+                const double words = good && v[0] > 0.0 ? std::floor(v[1] / v[0] + 0.5) : -1.0;
+                if (!good || !(v[0] > 0.0) || !(v[1] >= 0.0) || !(words >= 0.0 && words <= 255.0) || !(v[2] >= 0.0 && v[2] <= 1.0)) {
+                    std::fprintf(stderr,
+                                 "Error: --fingerprint takes CELL_SEC[:MAX_OFFSET_SEC[:MAX_BER]] with CELL_SEC > 0, "
+                                 "MAX_OFFSET_SEC >= 0 and at most 255 cells, MAX_BER in [0, 1]\n");
+                    return 1;
+                }
+                fpreq.cell_seconds = (float)v[0];
+                fpreq.max_offset_words = (uint32_t)words;
+                fpreq.max_ber = (float)v[2];
+            }
         } else if (s == "--loudness" || s.rfind("--loudness=", 0) == 0) {
             loudness = true;
             if (s.size() > 10) {  // =LIST
@@ -520,7 +585,8 @@ int main(int argc, char** argv) {
             std::fprintf(stderr,
                          "Usage: analyze_batch [--jobs N] [--devices MASK] [--json] [--gpu-decode] [--overview N | "
                          "--overview-frames K] [--key-timeline SEC[:OVERLAP[:MINCONF]]] [--levels [LIST]] [--tempo-map[=LIST]] "
-                         "[--sections[=CELL_SEC[:K[:GAP[:EWEIGHT[:MINSTRENGTH]]]]]] [--loudness[=LIST]] <file1> <file2> ...\n\n"
+                         "[--sections[=CELL_SEC[:K[:GAP[:EWEIGHT[:MINSTRENGTH]]]]]] [--loudness[=LIST]] "
+                         "[--fingerprint[=CELL_SEC[:MAX_OFFSET_SEC[:MAX_BER]]]] <file1> <file2> ...\n\n"
                          "--jobs N        Decode workers (default: CPU-1)\n"
                          "--devices MASK  GPU bitmask (default: all visible GPUs)\n"
                          "--json          Emit one JSON object per line (JSONL)\n"
@@ -539,7 +605,10 @@ int main(int argc, char** argv) {
                          "                (\"sections\"); defaults 0.5:16:8:1:0.5, starts snapped to downbeats within a cell\n"
                          "--loudness[=LIST]  With --json: add each track's BS.1770 integrated loudness, loudness range, maximum\n"
                          "                momentary and short-term loudness and sample peak (\"loudness\"); LIST out of\n"
-                         "                true-peak,curves adds the 4x true peak and the per-block mean squares\n");
+                         "                true-peak,curves adds the 4x true peak and the per-block mean squares\n"
+                         "--fingerprint[=CELL_SEC[:MAX_OFFSET_SEC[:MAX_BER]]]  With --json: add each track's chroma fingerprint\n"
+                         "                (\"fingerprint\": counts and the words as hex) and one last line \"duplicates\" with the\n"
+                         "                pairs of files that are the same recording; defaults 0.125:2:0.30\n");
             return 0;
         } else {
             paths.push_back(s);
@@ -555,6 +624,7 @@ int main(int argc, char** argv) {
     if (tempo_map && !json) std::fprintf(stderr, "Note: --tempo-map adds to the --json lines only\n");
     if (sections && !json) std::fprintf(stderr, "Note: --sections adds to the --json lines only\n");
     if (loudness && !json) std::fprintf(stderr, "Note: --loudness adds to the --json lines only\n");
+    if (fingerprint && !json) std::fprintf(stderr, "Note: --fingerprint adds to the --json lines only\n");
     if (paths.empty()) {
         std::fprintf(stderr, "ERROR: Provide at least one audio file path. Use --help for usage.\n");
         return 2;
@@ -611,7 +681,8 @@ int main(int argc, char** argv) {
     auto take = [&r128req](Item& it, const sdsp_result& r, const sdsp_overview* ov = nullptr,
                            const sdsp_key_timeline* kt = nullptr, const sdsp_levels* lv = nullptr,
                            const sdsp_tempo_map* tm = nullptr, const sdsp_sections* sc = nullptr,
-                           const sdsp_r128* ld = nullptr) {
+                           const sdsp_r128* ld = nullptr, const sdsp_fingerprint* fp = nullptr) {
+        if (fp) it.fingerprint = fingerprint_json(*fp);
         if (ov) it.overview = overview_json(*ov);
         if (kt) it.timeline = key_timeline_json(*kt);
         if (lv) it.levels = levels_json(*lv);
@@ -644,7 +715,9 @@ int main(int argc, char** argv) {
         std::vector<sdsp_tempo_map> tms;
         std::vector<sdsp_sections> scs;
         std::vector<sdsp_r128> lds;
-        sdsp_request_set_ext2 ext2{};
+        std::vector<sdsp_fingerprint> fps;
+        sdsp_fingerprint_matches fpm{};
+        sdsp_request_set_ext3 ext3{};
     };
     auto requests = [&](size_t n) {
         Requests q;
@@ -654,28 +727,47 @@ int main(int argc, char** argv) {
         q.tms.resize(tempo_map ? n : 0);
         q.scs.resize(sections ? n : 0);
         q.lds.resize(loudness ? n : 0);
+        q.fps.resize(fingerprint ? n : 0);
         return q;
     };
     auto request_set = [&](Requests& q) {
-        sdsp_request_set& set = q.ext2.base.base;
-        set.struct_size = (uint32_t)sizeof(q.ext2);
+        sdsp_request_set_ext2& ext2 = q.ext3.base;
+        sdsp_request_set& set = ext2.base.base;
+        set.struct_size = (uint32_t)sizeof(q.ext3);
         if (overview) set.ov_req = &ovreq, set.overviews = q.ovs.data();
         if (timeline) set.kt_req = &ktreq, set.timelines = q.kts.data();
         if (levels) set.lv_req = &lvreq, set.levels = q.lvs.data();
         if (tempo_map) set.tm_req = &tmreq, set.tempo_maps = q.tms.data();
-        if (sections) q.ext2.base.sc_req = &screq, q.ext2.base.sections = q.scs.data();
-        if (loudness) q.ext2.r128_req = &r128req, q.ext2.r128 = q.lds.data();
+        if (sections) ext2.base.sc_req = &screq, ext2.base.sections = q.scs.data();
+        if (loudness) ext2.r128_req = &r128req, ext2.r128 = q.lds.data();
+        if (fingerprint) q.ext3.fp_req = &fpreq, q.ext3.fingerprints = q.fps.data(), q.ext3.fp_matches = &q.fpm;
         return &set;
     };
     auto take_requests = [&](Item& it, const sdsp_result& r, Requests& q, size_t j) {
         take(it, r, overview ? &q.ovs[j] : nullptr, timeline ? &q.kts[j] : nullptr, levels ? &q.lvs[j] : nullptr,
-             tempo_map ? &q.tms[j] : nullptr, sections ? &q.scs[j] : nullptr, loudness ? &q.lds[j] : nullptr);
+             tempo_map ? &q.tms[j] : nullptr, sections ? &q.scs[j] : nullptr, loudness ? &q.lds[j] : nullptr,
+             fingerprint ? &q.fps[j] : nullptr);
         if (overview) sdsp_overview_free(&q.ovs[j]);
         if (timeline) sdsp_key_timeline_free(&q.kts[j]);
         if (levels) sdsp_levels_free(&q.lvs[j]);
         if (tempo_map) sdsp_tempo_map_free(&q.tms[j]);
         if (sections) sdsp_sections_free(&q.scs[j]);
         if (loudness) sdsp_r128_free(&q.lds[j]);
+        if (fingerprint) sdsp_fingerprint_free(&q.fps[j]);
+    };
+    // --fingerprint: the matches of one analysis call into the run's list; at(j): the file of the call's track j
+    std::vector<Dup> dups;
+    std::mutex dups_mu;
+    auto take_matches = [&](Requests& q, uint32_t sr, const std::function<size_t(size_t)>& at) {
+        if (!fingerprint) return;
+        std::lock_guard<std::mutex> lk(dups_mu);
+        for (uint64_t k = 0; q.fpm.matches && k < q.fpm.n_matches; k++) {
+            const sdsp_fingerprint_match& m = q.fpm.matches[k];
+            Dup d{at((size_t)m.a), at((size_t)m.b), (double)m.offset_samples / (double)std::max<uint32_t>(sr, 1), m.ber};
+            if (d.a > d.b) std::swap(d.a, d.b), d.offset_seconds = -d.offset_seconds;
+            dups.push_back(d);
+        }
+        sdsp_fingerprint_matches_free(&q.fpm);
     };
 
     if (gpu_decode) {
@@ -736,6 +828,7 @@ int main(int argc, char** argv) {
                     take_requests(items[ch.idx[okk[j]]], outs[j], q, j);
                     sdsp_result_free(&outs[j]);
                 }
+                take_matches(q, kv.first, [&](size_t j) { return ch.idx[okk[j]]; });
             }
             if (d_samples) sdsp_device_free(dev, d_samples);
         };
@@ -758,7 +851,7 @@ int main(int argc, char** argv) {
             ptrs.push_back(items[i].samples.data());
             lens.push_back(items[i].samples.size());
         }
-        if (overview || timeline || levels || tempo_map || sections || loudness) {
+        if (overview || timeline || levels || tempo_map || sections || loudness || fingerprint) {
             // the requests entry reads device-resident tracks: upload each group to the first device of
             // the mask in parts of at most 512 tracks or 2 Gi samples
             int dev = 0;
@@ -790,6 +883,7 @@ int main(int argc, char** argv) {
                         items[idx[k]].error = "analysis failed: Processing error: device upload failed";
                     }
                 }
+                if (up) take_matches(q, kv.first, [&](size_t j) { return idx[k0 + j]; });
                 if (d) sdsp_device_free(dev, d);
                 k0 = k1;
             }
@@ -842,6 +936,10 @@ int main(int argc, char** argv) {
                 std::fputs(",\"loudness\":", stdout);
                 std::fputs(o.loudness.c_str(), stdout);
             }
+            if (!o.fingerprint.empty()) {
+                std::fputs(",\"fingerprint\":", stdout);
+                std::fputs(o.fingerprint.c_str(), stdout);
+            }
             std::fputs("}\n", stdout);
         } else {
             if (o.ok)
@@ -852,6 +950,15 @@ int main(int argc, char** argv) {
                 std::printf("[%zu/%zu] %s: ERROR: %s\n", i + 1, items.size(), o.path.c_str(),
                             o.error.empty() ? "unknown error" : o.error.c_str());
         }
+    }
+    if (fingerprint && json) {
+        std::sort(dups.begin(), dups.end(), [](const Dup& x, const Dup& y) { return x.a != y.a ? x.a < y.a : x.b < y.b; });
+        std::fputs("{\"duplicates\":[", stdout);
+        for (size_t k = 0; k < dups.size(); k++)
+            std::printf("%s{\"a\":%s,\"b\":%s,\"offset_seconds\":%.9g,\"ber\":%.9g}", k ? "," : "",
+                        json_str(items[dups[k].a].path).c_str(), json_str(items[dups[k].b].path).c_str(), dups[k].offset_seconds,
+                        (double)dups[k].ber);
+        std::fputs("]}\n", stdout);
     }
     std::vector<float> ok_times;
     for (const Item& o : items)

@@ -499,4 +499,21 @@ void launch_section_novelty(const float* m, const float* g, const uint64_t* cell
                             int n_tracks, uint64_t n_tiles, int K, float w, uint64_t G, float min_strength, float* N,
                             uint8_t* boundary, hipStream_t st);
 
+// ---- k_fingerprint: the fingerprint request (fingerprint_core.hpp has the arithmetic and FpRec) ----
+struct FpRec;
+constexpr int FP_TA = 4, FP_TB = 4;  // k_fp_match's tile: a-tracks (a wave each) by b-tracks
+constexpr int FP_CH = 256;           // ... and the positions it stages per chunk
+// m[12 u + i]: the mean of chroma_s row f's class i over cell u's key frames (khop apart); cells of all
+// tracks back to back, track t's at cell_pfx[t]
+void launch_fp_cells(const float* chroma_s, const uint64_t* frame_pfx, const uint64_t* cell_pfx, int n_tracks,
+                     uint64_t n_cells, uint64_t Cs, uint64_t khop, float* m, hipStream_t st);
+// word w of track t (word_pfx[t + 1] - word_pfx[t] of them, its cells less 2) to words[slot[t] + w]
+void launch_fp_words(const float* m, const uint64_t* cell_pfx, const uint64_t* word_pfx, const uint64_t* slot, int n_tracks,
+                     uint64_t n_words, uint32_t* words, hipStream_t st);
+// The pairs (ia, jb), ia in [row0, row0 + rows), jb in (ia, NC), of the compared tracks: track k's W[k]
+// words (1 <= W[k] < 2^27) at words + slot[k]; the pair's record to rec[(ia - row0) * NC + jb] (the
+// other entries are not written).  O <= 255; need = max(min_overlap_words, 1).
+void launch_fp_match(const uint32_t* words, const uint64_t* slot, const uint32_t* W, int NC, int row0, int rows, int O,
+                     uint32_t need, FpRec* rec, hipStream_t st);
+
 }  // namespace sdsp

@@ -118,6 +118,8 @@ void Pipeline::run(const float* d_samples, const std::vector<uint64_t>& in_off, 
         loudness_prepass(d_samples, in_off, n_raw, res);
     // the programme loudness kernels, on the vote stream beside the first sub-batch (nothing without a request)
     if (r128_out_ && why.empty()) r128_prepass(d_samples, in_off, n_raw, res);
+    // the fingerprint request's word buffer of the call, a slot per track (nothing without a request)
+    if (fp_out_) fingerprint_plan(n_raw);
     // equal shares: the fewest sub-batches that fit the budget, each near total / count (a
     // short last sub-batch runs at a fraction of the chip)
     std::vector<double> need(T, 0.0);
@@ -141,6 +143,7 @@ void Pipeline::run(const float* d_samples, const std::vector<uint64_t>& in_off, 
         if (sc_out_ && !bpm_only_)  // both parities' cell means, novelty and flags
             need[i] += (n / (double)sc_Cs_ + 1.0) * 2.0 * (12.0 * 4.0 + 4.0 + 4.0 + 1.0);
         if (r128_out_) need[i] += n / (double)std::max<uint32_t>(sr_ / 10, 1) * 12.0 + 64.0;  // z and both curves
+        if (fp_out_ && !bpm_only_) need[i] += (n / (double)fp_Cs_ + 1.0) * (4.0 + 12.0 * 4.0);  // its words and cell means
         total_need += need[i];
     }
     const double parts = std::max(1.0, std::ceil(total_need / budget));
@@ -165,6 +168,7 @@ void Pipeline::run(const float* d_samples, const std::vector<uint64_t>& in_off, 
     rerun_tail(finish_key(res, true), res);
     levels_join();  // the one join of the levels folds (nothing without a request)
     r128_join();    // ... and of the programme loudness kernels
+    if (fp_out_) fingerprint_finish(res);  // every join is done: the call's words are complete
     times_.total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     times_.key_reruns = reruns_;  // in-flight reruns (rerun_near), their time inside total_ms
     times_.rerun_ms = rerun_ms_;
@@ -227,7 +231,7 @@ void Pipeline::sub_batch(const float* d_samples, const std::vector<uint64_t>& in
     std::vector<TrackDbg> tdbg(dbg_on() ? (size_t)NR : 0);
     const TempoPassIn bin = base_pass_in(d_samples, f);
     // E: key, on the key stream under B-D
-    KeyLaunch kl = launch_key(d_samples, bin);
+    KeyLaunch kl = launch_key(d_samples, bin, f);
     if (key_only_) {
         join_key_only(kl, f, res);
         htr("E key only");

@@ -14,6 +14,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <deque>
+#include <functional>
 #include <map>
 #include <memory>
 #include <string>
@@ -21,6 +22,7 @@
 
 #include "../../include/sdsp_fft_spec.h"
 #include "../../include/stratum_hip_debug.h"
+#include "fingerprint_core.hpp"
 #include "kernels.hpp"
 #include "levels_core.hpp"
 #include "r128_core.hpp"
@@ -348,6 +350,12 @@ struct SectionsOut {
     uint8_t* d_b = nullptr;
     bool queued = false;  // the novelty is queued: the joins wait for ev[13], not ev[2]
 };
+// The fingerprint request's plan of a sub-batch's key tracks (Pipeline::launch_key): the cell means
+// and the words queued behind the vote; nothing is queued without a request.  The words go to the
+// call's word buffer, which the match reads after the last join, so no join reads anything here.
+struct FingerprintOut {
+    std::vector<uint64_t> cpfx{0}, wpfx{0};  // cell and word prefix over the key tracks
+};
 // Late key join: a sub-batch's key results are read after the next sub-batch's tempo path is
 // queued, so the key stream's tail (mask, HPCP, vote) runs beside that tempo path instead of
 // holding the main stream back.  Uploads read by the key stream and the key output live in
@@ -394,6 +402,7 @@ struct KeyLaunch {
     KeyDbg* d_kdbg = nullptr;
     KeyTimelineOut ktl;
     SectionsOut sc;
+    FingerprintOut fp;
     // the key spectrogram, frame prefix, templates and vote parameters; with tail.ok the band
     // path's state for rerun_tail
     KeyTail tail;
@@ -508,6 +517,26 @@ struct TrackSc {
     std::vector<float> g, N;
     std::vector<uint8_t> b;
 };
+// One track's fingerprint plan on the host; `on` marks a track whose key path ran.
+struct TrackFp {
+    bool on = false;
+    uint64_t first = 0, n_cells = 0, W = 0;
+};
+// The fingerprints of a call (Pipeline::set_fingerprint): every track's plan and its slot in the
+// call's word buffer, the words on the host (SDSP_FP_WORDS) and, with SDSP_FP_MATCH, the matches among
+// the tracks whose status was SDSP_OK when the match ran (run_locked drops a track that fails later).
+struct FpOut {
+    std::vector<TrackFp> tracks;
+    std::vector<uint64_t> slot;  // track t's words at words[slot[t]], tracks[t].W of them
+    std::vector<uint32_t> words;
+    std::vector<sdsp_fingerprint_match> matches;
+};
+// The pairs among NC compared tracks (launch_fp_match's arguments on the device) in row bands whose
+// records stay under a fixed bound: band(r0, r1, rec) receives the rows [r0, r1) on the host, the pair
+// (i, j), i < j, at rec[(i - r0) * NC + j].  Returns the kernel's HIP event time in ms.
+double fp_match_bands(Ctx& c, const std::string& tag, const uint32_t* d_words, const uint64_t* d_slot, const uint32_t* d_W,
+                      int NC, uint32_t O, uint32_t min_overlap_words,
+                      const std::function<void(int, int, const FpRec*)>& band);
 // One track's tempo map on the host (sdsp_tempo_map without its status).  `on`: the track reached
 // the beat stage.
 struct TrackTm {
@@ -631,6 +660,16 @@ class Pipeline {
         r128_out_ = out;
     }
 
+    // Before run(): also compute every track's fingerprint and, with SDSP_FP_MATCH, compare every pair
+    // of the call's tracks (include/stratum_hip.h, sdsp_fingerprint; the request checked by
+    // fingerprint_request_error, Cs its cell) into *out.  A pipeline without a request queues nothing
+    // for it; nested pipelines get none.
+    void set_fingerprint(const sdsp_fingerprint_request& req, uint64_t Cs, FpOut* out) {
+        fp_req_ = req;
+        fp_Cs_ = Cs;
+        fp_out_ = out;
+    }
+
    private:
     Ctx c_;
     DeviceCtx& d_;
@@ -679,6 +718,11 @@ class Pipeline {
     uint32_t r128_what_ = 0;
     std::vector<TrackR128>* r128_out_ = nullptr;  // the call's programme loudness (set_r128), else nullptr
     R128Pending r128_pending_;
+    sdsp_fingerprint_request fp_req_{};
+    uint64_t fp_Cs_ = 0;
+    FpOut* fp_out_ = nullptr;  // the call's fingerprints (set_fingerprint), else nullptr
+    uint32_t* fp_words_ = nullptr;  // the call's word buffer on the device
+    std::vector<std::unique_ptr<Timers>> fp_tm_;  // per sub-batch, on the vote stream: events 0-1 k_fp_cells, 1-2 k_fp_words
     bool map_on() const { return lv_out_ && (lv_what_ & SDSP_LEVELS_SILENCE_MAP); }
 
     // force_legacy_bpm skips the tempogram estimate (src/lib.rs:337): no escalation, no
@@ -741,7 +785,9 @@ class Pipeline {
     void legacy_select(const Front& f, const TempoPassIn& bin, const Onsets& on, Tempo& tp, std::vector<TrackRes>& res);
 
     // pipeline_key.hip
-    KeyLaunch launch_key(const float* d_samples, const TempoPassIn& bin);
+    KeyLaunch launch_key(const float* d_samples, const TempoPassIn& bin, const Front& f);
+    void fingerprint_plan(const std::vector<uint64_t>& n_raw);
+    void fingerprint_finish(const std::vector<TrackRes>& res);
     KeyCond key_condition(const std::string& EP, float* mags8, const std::vector<uint64_t>& kpfx,
                           const std::vector<uint64_t>& ktile, uint64_t* d_kpfx, uint64_t* d_ktile, int* d_kid,
                           hipStream_t st2, Timers& kt);

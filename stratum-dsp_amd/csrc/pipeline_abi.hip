@@ -335,6 +335,70 @@ void fill_r128(const TrackR128& t, int status, sdsp_r128* o) {
     o->short_term = blk + o->n_momentary;
 }
 
+// A checked fingerprint request: its cell Cs, and where the fingerprints and the match list go.
+struct FpCall {
+    sdsp_fingerprint_request req{};
+    uint64_t Cs = 0;
+    sdsp_fingerprint* out = nullptr;
+    sdsp_fingerprint_matches* matches = nullptr;
+};
+// The call's fingerprints and match list from the pipeline's FpOut and the final statuses: a track
+// that failed (also after the match ran: a certification rerun) is not compared and takes its
+// matches with it.
+void fill_fingerprints(const FpOut& f, const std::vector<TrackRes>& res, const FpCall& fc) {
+    const size_t T = res.size();
+    const bool match = (fc.req.what & SDSP_FP_MATCH) != 0;
+    std::vector<sdsp_fingerprint_match> ms;
+    uint64_t compared = 0;
+    for (size_t i = 0; i < T; i++) {
+        sdsp_fingerprint* o = &fc.out[i];
+        std::memset(o, 0, sizeof(*o));
+        o->status = res[i].status;
+        o->cell_samples = fc.Cs;
+        const TrackFp& t = f.tracks[i];
+        if (res[i].status != SDSP_OK || !t.on) continue;  // (not on: the key path did not run, n_cells 0)
+        o->first_sample = t.first;
+        o->n_cells = t.n_cells;
+        o->n_words = t.W;
+        if (t.W > 0) compared++;
+    }
+    if (match)
+        for (const sdsp_fingerprint_match& m : f.matches)
+            if (res[(size_t)m.a].status == SDSP_OK && res[(size_t)m.b].status == SDSP_OK) {
+                ms.push_back(m);
+                fc.out[m.a].n_matches++;
+                fc.out[m.b].n_matches++;
+            }
+    // allocate last, so a failed allocation leaves nothing behind to free
+    sdsp_fingerprint_match* list = nullptr;
+    if (!ms.empty()) {
+        list = (sdsp_fingerprint_match*)std::malloc(ms.size() * sizeof(sdsp_fingerprint_match));
+        if (!list) throw std::bad_alloc();
+        std::memcpy(list, ms.data(), ms.size() * sizeof(sdsp_fingerprint_match));
+    }
+    if (fc.req.what & SDSP_FP_WORDS)
+        for (size_t i = 0; i < T; i++) {
+            sdsp_fingerprint* o = &fc.out[i];
+            if (o->n_words == 0) continue;
+            o->words = (uint32_t*)std::malloc((size_t)o->n_words * sizeof(uint32_t));
+            if (!o->words) {
+                for (size_t j = 0; j < i; j++) sdsp_fingerprint_free(&fc.out[j]);
+                std::free(list);
+                throw std::bad_alloc();
+            }
+            std::memcpy(o->words, f.words.data() + f.slot[i], (size_t)o->n_words * sizeof(uint32_t));
+        }
+    if (fc.matches) {
+        std::memset(fc.matches, 0, sizeof(*fc.matches));
+        if (match) {
+            fc.matches->n_compared = compared;
+            fc.matches->n_pairs = compared * (compared > 0 ? compared - 1 : 0) / 2;
+            fc.matches->n_matches = ms.size();
+            fc.matches->matches = list;
+        }
+    }
+}
+
 // One device-resident batch on `device`.  The engine's main stream first waits for `user_stream`
 // (everything queued on it so far) and for `wait_ev` (a copy's completion), whichever are given.
 // The batch on a context whose mutex the caller holds (run_device, and sdsp_analyze_audio's
@@ -343,7 +407,7 @@ int32_t run_locked(DeviceCtx& d, const float* d_samples, const uint64_t* offsets
                    uint32_t sr, const sdsp_config* cfg, void* user_stream, sdsp_result* outs, int stages,
                    hipEvent_t wait_ev, const sdsp_overview_request* req = nullptr, sdsp_overview* ovs = nullptr,
                    const KtCall* ktc = nullptr, const LvCall* lvc = nullptr, const TmCall* tmc = nullptr,
-                   const ScCall* scc = nullptr, const R128Call* rc = nullptr) {
+                   const ScCall* scc = nullptr, const R128Call* rc = nullptr, const FpCall* fc = nullptr) {
     if (stages != SDSP_STAGES_FULL && stages != SDSP_STAGES_BPM_ONLY) throw HipError("unknown stage mask");
     if (user_stream) {
         hipEvent_t ev;
@@ -374,6 +438,9 @@ int32_t run_locked(DeviceCtx& d, const float* d_samples, const uint64_t* offsets
     std::vector<TrackR128> r128l;
     d.last_r128 = sdsp_debug_r128_times{};
     if (rc) p.set_r128(rc->what, &r128l);
+    FpOut fpo;
+    d.last_fp = sdsp_debug_fingerprint_times{};
+    if (fc) p.set_fingerprint(fc->req, fc->Cs, &fpo);
     try {
         p.run(d_samples, off, ln, res);
         // Certified block energies: a track whose key vote had an energy-dependent
@@ -432,6 +499,7 @@ int32_t run_locked(DeviceCtx& d, const float* d_samples, const uint64_t* offsets
         for (uint64_t i = 0; i < n; i++) fill_sections(scl[(size_t)i], res[(size_t)i], sr, *scc, &scc->out[i]);
     if (rc)
         for (uint64_t i = 0; i < n; i++) fill_r128(r128l[(size_t)i], res[(size_t)i].status, &rc->out[i]);
+    if (fc) fill_fingerprints(fpo, res, *fc);
     return SDSP_OK;
 }
 
@@ -440,12 +508,12 @@ int32_t run_device(int device, const float* d_samples, const uint64_t* offsets, 
                    int stages = SDSP_STAGES_FULL, hipEvent_t wait_ev = nullptr,
                    const sdsp_overview_request* req = nullptr, sdsp_overview* ovs = nullptr,
                    const KtCall* ktc = nullptr, const LvCall* lvc = nullptr, const TmCall* tmc = nullptr,
-                   const ScCall* scc = nullptr, const R128Call* rc = nullptr) {
+                   const ScCall* scc = nullptr, const R128Call* rc = nullptr, const FpCall* fc = nullptr) {
     DeviceCtx& d = device_ctx(device);
     std::lock_guard<std::mutex> lk(d.mu);
     SDSP_HIP_CHECK(hipSetDevice(device));
     return run_locked(d, d_samples, offsets, lens, n, sr, cfg, user_stream, outs, stages, wait_ev, req, ovs, ktc, lvc,
-                      tmc, scc, rc);
+                      tmc, scc, rc, fc);
 }
 
 }  // namespace
@@ -640,7 +708,11 @@ int32_t sdsp_analyze_batch_device_with(const float* d_samples, const uint64_t* o
     const sdsp_r128_request* r128_req = nullptr;  // (sdsp_request_set_ext2's pair, likewise)
     sdsp_r128* r128 = nullptr;
     if (!set_err) request_set_ext2_read(caller_set, &r128_req, &r128);
-    if (!set_err && !ov_req && !kt_req && !lv_req && !tm_req && !sc_req && !r128_req)
+    const sdsp_fingerprint_request* fp_req = nullptr;  // (sdsp_request_set_ext3's fields, likewise)
+    sdsp_fingerprint* fingerprints = nullptr;
+    sdsp_fingerprint_matches* fp_matches = nullptr;
+    if (!set_err) request_set_ext3_read(caller_set, &fp_req, &fingerprints, &fp_matches);
+    if (!set_err && !ov_req && !kt_req && !lv_req && !tm_req && !sc_req && !r128_req && !fp_req)
         return sdsp_analyze_batch_device_ex(d_samples, offsets, lens, n_tracks, sample_rate, cfg, device, stream, stages,
                                             outs);
     auto fail_all = [&](int32_t status, const char* text) {
@@ -672,7 +744,12 @@ int32_t sdsp_analyze_batch_device_with(const float* d_samples, const uint64_t* o
                 std::memset(&r128[i], 0, sizeof(r128[i]));
                 r128[i].status = status;
             }
+            if (fp_req && fingerprints) {
+                std::memset(&fingerprints[i], 0, sizeof(fingerprints[i]));
+                fingerprints[i].status = status;
+            }
         }
+        if (fp_req && fp_matches) std::memset(fp_matches, 0, sizeof(*fp_matches));
         return status;
     };
     if (set_err) return fail_all(SDSP_ERR_INVALID_INPUT, set_err);
@@ -730,13 +807,24 @@ int32_t sdsp_analyze_batch_device_with(const float* d_samples, const uint64_t* o
         rc.what = r128_req->what;
         rc.out = r128;
     }
+    FpCall fpc;
+    if (fp_req) {
+        int32_t why_status = SDSP_OK;
+        if (const char* why = fingerprint_request_error(
+                *fp_req, fingerprints != nullptr, fp_matches != nullptr, stages, sample_rate, kt_khop(*cfg),
+                cfg->enable_key_beat_synchronous && !cfg->enable_key_log_frequency, &fpc.Cs, &why_status))
+            return fail_all(why_status, why);
+        fpc.req = *fp_req;
+        fpc.out = fingerprints;
+        fpc.matches = fp_matches;
+    }
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
         return fail_all(SDSP_ERR_PROCESSING, "Processing error: no HIP device");
     try {
         return run_device(device, d_samples, offsets, lens, n_tracks, sample_rate, cfg, stream, outs, stages, nullptr,
                           ov_req, overviews, kt_req ? &kc : nullptr, lv_req ? &lc : nullptr, tm_req ? &tc : nullptr,
-                          sc_req ? &sc : nullptr, r128_req ? &rc : nullptr);
+                          sc_req ? &sc : nullptr, r128_req ? &rc : nullptr, fp_req ? &fpc : nullptr);
     } catch (const std::exception& e) {
         std::fprintf(stderr, "sdsp_analyze_batch_device_with: %s\n", e.what());
         char text[256];
@@ -751,6 +839,109 @@ void sdsp_sections_free(sdsp_sections* s) {
     s->sections = nullptr;
     s->novelty = s->energy = nullptr;
     s->n_sections = s->n_curve = 0;
+}
+
+void sdsp_fingerprint_free(sdsp_fingerprint* f) {
+    if (!f) return;
+    std::free(f->words);
+    f->words = nullptr;
+}
+
+void sdsp_fingerprint_matches_free(sdsp_fingerprint_matches* m) {
+    if (!m) return;
+    std::free(m->matches);
+    m->matches = nullptr;
+    m->n_matches = 0;
+}
+
+int32_t sdsp_debug_last_fingerprint_times(int32_t device, sdsp_debug_fingerprint_times* out) {
+    try {
+        if (!out) return SDSP_ERR_INVALID_INPUT;
+        DeviceCtx& d = device_ctx(device);
+        std::lock_guard<std::mutex> lk(d.mu);
+        *out = d.last_fp;
+        return SDSP_OK;
+    } catch (const std::exception&) {
+        return SDSP_ERR_PROCESSING;
+    }
+}
+
+// k_fp_cells and k_fp_words over uploaded chroma rows (include/stratum_hip_debug.h).
+int32_t sdsp_debug_fingerprint(const float* host_chroma, const uint64_t* frames, uint64_t n_tracks, uint32_t sample_rate,
+                               uint32_t khop, const sdsp_fingerprint_request* req, sdsp_debug_fingerprint_out* out,
+                               int32_t device) {
+    if (!frames || !req || !out || !out->n_cells || !out->n_words || n_tracks == 0 || n_tracks > (1u << 20) || khop == 0)
+        return SDSP_ERR_INVALID_INPUT;
+    uint64_t Cs = 0;
+    int32_t why_status = SDSP_OK;
+    if (fingerprint_request_error(*req, true, true, SDSP_STAGES_FULL, sample_rate, khop, false, &Cs, &why_status))
+        return SDSP_ERR_INVALID_INPUT;
+    std::vector<uint64_t> kpfx(1, 0), cpfx(1, 0), wpfx(1, 0);
+    for (uint64_t t = 0; t < n_tracks; t++) {
+        if (frames[t] > (1u << 24)) return SDSP_ERR_INVALID_INPUT;
+        kpfx.push_back(kpfx.back() + frames[t]);
+        const uint64_t nc = fp_cells(frames[t], khop, Cs);
+        cpfx.push_back(cpfx.back() + nc);
+        wpfx.push_back(wpfx.back() + fp_words(nc));
+    }
+    if (kpfx.back() > 0 && !host_chroma) return SDSP_ERR_INVALID_INPUT;
+    const uint64_t cells = cpfx.back(), words = wpfx.back();
+    if (cells > out->cell_capacity || words > out->word_capacity || cells / 16 >= 0x7FFFFFFFull) return SDSP_ERR_INVALID_INPUT;
+    if ((cells > 0 && !out->m) || (words > 0 && !out->words)) return SDSP_ERR_INVALID_INPUT;
+    for (uint64_t t = 0; t < n_tracks; t++) {
+        out->n_cells[t] = cpfx[(size_t)t + 1] - cpfx[(size_t)t];
+        out->n_words[t] = wpfx[(size_t)t + 1] - wpfx[(size_t)t];
+    }
+    if (cells == 0) return SDSP_OK;
+    return run_stage_probe("sdsp_debug_fingerprint", device, [&](DeviceCtx& d) {
+        Ctx c(d);
+        c.pre = "D.";
+        const std::vector<float> rows(host_chroma, host_chroma + kpfx.back() * 12);
+        float* d_cs = c.up("fp_chroma", rows);
+        uint64_t* d_kpfx = c.up("fp_kpfx", kpfx);
+        uint64_t* d_cpfx = c.up("fp_cpfx", cpfx);
+        uint64_t* d_wpfx = c.up("fp_wpfx", wpfx);  // (also the slots: the words back to back)
+        float* d_m = c.dev<float>("fp_m", 12 * (size_t)cells);
+        uint32_t* d_w = c.dev<uint32_t>("fp_words", (size_t)std::max<uint64_t>(words, 1));
+        launch_fp_cells(d_cs, d_kpfx, d_cpfx, (int)n_tracks, cells, Cs, khop, d_m, d.stream);
+        launch_fp_words(d_m, d_cpfx, d_wpfx, d_wpfx, (int)n_tracks, words, d_w, d.stream);
+        SDSP_HIP_CHECK(hipGetLastError());
+        const std::vector<float> m = c.down(d_m, 12 * (size_t)cells);
+        const std::vector<uint32_t> w = c.down(d_w, (size_t)words);
+        std::memcpy(out->m, m.data(), m.size() * sizeof(float));
+        if (words) std::memcpy(out->words, w.data(), w.size() * sizeof(uint32_t));
+    });
+}
+
+// k_fp_match over uploaded word arrays (include/stratum_hip_debug.h).
+int32_t sdsp_debug_fingerprint_match(const uint32_t* host_words, const uint64_t* n_words, uint64_t n_tracks,
+                                     const sdsp_fingerprint_request* req, sdsp_debug_fingerprint_pair* rec, int32_t device) {
+    static_assert(sizeof(sdsp_debug_fingerprint_pair) == sizeof(FpRec) && offsetof(sdsp_debug_fingerprint_pair, positions) == offsetof(FpRec, n),
+                  "the probe hands the kernel's records out as they are");
+    if (!host_words || !n_words || !req || !rec || n_tracks == 0 || n_tracks > 4096 || req->max_offset_words > FP_OMAX)
+        return SDSP_ERR_INVALID_INPUT;
+    std::vector<uint64_t> slot(1, 0);
+    std::vector<uint32_t> W;
+    for (uint64_t t = 0; t < n_tracks; t++) {
+        if (n_words[t] == 0 || n_words[t] > (1u << 24)) return SDSP_ERR_INVALID_INPUT;
+        slot.push_back(slot.back() + n_words[t]);
+        W.push_back((uint32_t)n_words[t]);
+    }
+    std::memset(rec, 0, (size_t)(n_tracks * n_tracks) * sizeof(*rec));
+    if (n_tracks < 2) return SDSP_OK;
+    return run_stage_probe("sdsp_debug_fingerprint_match", device, [&](DeviceCtx& d) {
+        Ctx c(d);
+        c.pre = "D.";
+        const std::vector<uint32_t> words(host_words, host_words + slot.back());
+        uint32_t* d_words = c.up("fp_mwords", words);
+        uint64_t* d_slot = c.up("fp_mslot", slot);
+        uint32_t* d_W = c.up("fp_mW", W);
+        const size_t NC = (size_t)n_tracks;
+        fp_match_bands(c, "", d_words, d_slot, d_W, (int)NC, req->max_offset_words, req->min_overlap_words,
+                       [&](int r0, int r1, const FpRec* band) {
+                           std::memcpy(rec + (size_t)r0 * NC, band, (size_t)(r1 - r0) * NC * sizeof(FpRec));
+                       });
+    });
 }
 
 void sdsp_r128_free(sdsp_r128* r) {

@@ -10,7 +10,7 @@ namespace sdsp {
 // forked onto the context's key stream right after trimming and joined before the results are
 // read back: its bandwidth-bound STFT/mask/HPCP kernels run under the latency-bound tempo and beat
 // kernels of the main stream.  bin: the base pass's tracks (the surviving ones).
-KeyLaunch Pipeline::launch_key(const float* d_samples, const TempoPassIn& bin) {
+KeyLaunch Pipeline::launch_key(const float* d_samples, const TempoPassIn& bin, const Front& f) {
     KeyLaunch kl;
     KeyTail& t = kl.tail;
     t.kp = key_vote_params(cfg_, false);  // near_check: set once the conditioning's path is known
@@ -116,6 +116,30 @@ KeyLaunch Pipeline::launch_key(const float* d_samples, const TempoPassIn& bin) {
         o.d_N = c_.dev<float>(EP + "sc_N", cells);
         o.d_b = c_.dev<uint8_t>(EP + "sc_b", cells);
     }
+    // the fingerprint request's cell and word plan (a request only), uploaded on the main stream alike;
+    // the cell means are scratch of the sub-batch on the vote stream, the words go to the call's buffer
+    uint64_t *d_fcpfx = nullptr, *d_fwpfx = nullptr, *d_fslot = nullptr;
+    float* d_fm = nullptr;
+    if (fp_out_) {
+        FingerprintOut& o = kl.fp;
+        std::vector<uint64_t> slot;
+        for (int k = 0; k < NK; k++) {
+            const int i = kl.K[(size_t)k];
+            TrackFp& tf = fp_out_->tracks[f.slot[(size_t)i]];
+            tf.on = true;
+            tf.first = f.ts[(size_t)f.R[(size_t)i]];
+            tf.n_cells = fp_cells(t.kpfx[(size_t)k + 1] - t.kpfx[(size_t)k], (uint64_t)KHOP, fp_Cs_);
+            tf.W = fp_words(tf.n_cells);  // (<= the slot's lens / Cs - 2: the trimmed track is no longer than the raw one)
+            o.cpfx.push_back(o.cpfx.back() + tf.n_cells);
+            o.wpfx.push_back(o.wpfx.back() + tf.W);
+            slot.push_back(fp_out_->slot[f.slot[(size_t)i]]);
+        }
+        if (o.cpfx.back() / 16 >= 0x7FFFFFFFull) throw HipError("fingerprint: too many cells for one launch");
+        d_fcpfx = c_.up(EP + "fp_cpfx", o.cpfx);
+        d_fwpfx = c_.up(EP + "fp_wpfx", o.wpfx);
+        d_fslot = c_.up(EP + "fp_slot", slot);
+        d_fm = c_.dev<float>("F.m", 12 * (size_t)std::max<uint64_t>(o.cpfx.back(), 1));
+    }
     // the template upload above is on the main stream too; the vote follows the chroma on st2
     kt.mark(8);
     kt.mark(11, st2);
@@ -141,6 +165,19 @@ KeyLaunch Pipeline::launch_key(const float* d_samples, const TempoPassIn& bin) {
         launch_section_chroma(d_cs, t.d_kpfx, kl.sc.d_cpfx, NK, kl.sc.cpfx.back(), sc_Cs_, (uint64_t)KHOP, kl.sc.d_m, st3);
         SDSP_HIP_CHECK(hipGetLastError());
         kt.mark(4, st3);
+    }
+    // The fingerprint request's cell means and words read the same rows, under the same ordering; the
+    // words land in the call's buffer (fp_words_), which only the match after the last join reads.
+    if (fp_out_ && kl.fp.wpfx.back() > 0) {
+        fp_tm_.emplace_back(new Timers());
+        Timers& ft = *fp_tm_.back();
+        ft.init(d_);
+        ft.mark(0, st3);
+        launch_fp_cells(d_cs, t.d_kpfx, d_fcpfx, NK, kl.fp.cpfx.back(), fp_Cs_, (uint64_t)KHOP, d_fm, st3);
+        ft.mark(1, st3);
+        launch_fp_words(d_fm, d_fcpfx, d_fwpfx, d_fslot, NK, kl.fp.wpfx.back(), fp_words_, st3);
+        SDSP_HIP_CHECK(hipGetLastError());
+        ft.mark(2, st3);
     }
     kt.mark(2, st3);
     if (!nested_) SDSP_HIP_CHECK(hipEventRecord(d_.vote_done, st3));
@@ -382,6 +419,86 @@ void Pipeline::sections_results(const SectionsOut& sc, Timers& kt, const std::ve
         o.N.assign(N.begin() + a, N.begin() + e);
         o.b.assign(b.begin() + a, b.begin() + e);
     }
+}
+
+// The fingerprint request before the first sub-batch: the call's word buffer with a slot per track at
+// a prefix of lens[t] / Cs, an upper bound of its words known now, so no sub-batch waits for another.
+void Pipeline::fingerprint_plan(const std::vector<uint64_t>& n_raw) {
+    FpOut& o = *fp_out_;
+    const size_t T = n_raw.size();
+    o = FpOut{};
+    o.tracks.assign(T, TrackFp{});
+    o.slot.assign(T + 1, 0);
+    for (size_t i = 0; i < T; i++) {
+        const uint64_t cap = n_raw[i] / fp_Cs_;
+        if (cap >= FP_WMAX) throw HipError("fingerprint: a track of 2^27 words or more");
+        o.slot[i + 1] = o.slot[i] + cap;
+    }
+    fp_words_ = c_.dev<uint32_t>("F.words", (size_t)std::max<uint64_t>(o.slot[T], 1));
+    fp_tm_.clear();
+}
+
+namespace detail {
+double fp_match_bands(Ctx& c, const std::string& tag, const uint32_t* d_words, const uint64_t* d_slot, const uint32_t* d_W,
+                      int NC, uint32_t O, uint32_t min_overlap_words,
+                      const std::function<void(int, int, const FpRec*)>& band) {
+    if (NC < 2) return 0.0;
+    // at most 64 MB of records per launch, whole tiles of rows
+    const uint64_t per_row = (uint64_t)NC * sizeof(FpRec);
+    const int rows_max = (int)std::max<uint64_t>(FP_TA, ((uint64_t)64 << 20) / per_row / FP_TA * FP_TA);
+    const int rows_band = std::min(rows_max, (NC - 1 + FP_TA - 1) / FP_TA * FP_TA);  // (the last track has no pair of its own)
+    FpRec* d_rec = c.dev<FpRec>(tag + "fp_rec", (size_t)rows_band * (size_t)NC);
+    Timers tm;
+    tm.init(c.d);
+    double ms = 0.0;
+    for (int r0 = 0; r0 < NC - 1; r0 += rows_band) {
+        const int rows = std::min(rows_band, NC - 1 - r0);
+        SDSP_HIP_CHECK(hipMemsetAsync(d_rec, 0, (size_t)rows * per_row, c.d.stream));
+        tm.mark(0);
+        launch_fp_match(d_words, d_slot, d_W, NC, r0, rows, (int)O, fp_min_overlap(min_overlap_words), d_rec, c.d.stream);
+        SDSP_HIP_CHECK(hipGetLastError());
+        tm.mark(1);
+        const std::vector<FpRec> rec = c.down(d_rec, (size_t)rows * (size_t)NC);
+        ms += tm.ms(0, 1);
+        band(r0, r0 + rows, rec.data());
+    }
+    return ms;
+}
+}  // namespace detail
+
+// The fingerprint request after the last join: every sub-batch's words are in the call's buffer (the
+// main stream has waited for the vote stream's last event).  Downloads the words when asked for, and
+// with SDSP_FP_MATCH compares every pair of the tracks with a word and status SDSP_OK on the device
+// and keeps the pairs within max_ber.
+void Pipeline::fingerprint_finish(const std::vector<TrackRes>& res) {
+    FpOut& o = *fp_out_;
+    const size_t T = o.tracks.size();
+    sdsp_debug_fingerprint_times& lt = d_.last_fp;
+    for (auto& ft : fp_tm_) lt.cells_ms += ft->ms(0, 1), lt.words_ms += ft->ms(1, 2);
+    fp_tm_.clear();
+    for (size_t i = 0; i < T; i++) lt.words += o.tracks[i].W;
+    if (fp_req_.what & SDSP_FP_WORDS) o.words = c_.down(fp_words_, (size_t)o.slot[T]);
+    if (!(fp_req_.what & SDSP_FP_MATCH)) return;
+    std::vector<uint64_t> who, slot, first(T, 0);
+    std::vector<uint32_t> W;
+    for (size_t i = 0; i < T; i++) {
+        first[i] = o.tracks[i].first;
+        if (res[i].status != SDSP_OK || !o.tracks[i].on || o.tracks[i].W == 0) continue;
+        who.push_back(i);
+        slot.push_back(o.slot[i]);
+        W.push_back((uint32_t)o.tracks[i].W);
+    }
+    const int NC = (int)who.size();
+    lt.compared = (uint64_t)NC;
+    lt.pairs = (uint64_t)NC * (uint64_t)(NC > 0 ? NC - 1 : 0) / 2;
+    if (NC < 2) return;
+    uint64_t* d_slot = c_.up("F.slot", slot);
+    uint32_t* d_W = c_.up("F.W", W);
+    lt.match_ms += fp_match_bands(c_, "F.", fp_words_, d_slot, d_W, NC, fp_req_.max_offset_words, fp_req_.min_overlap_words,
+                                  [&](int r0, int r1, const FpRec* rec) {
+                                      fp_assemble(rec, who, (size_t)r0, (size_t)r1, first.data(), fp_Cs_, fp_req_.max_ber,
+                                                  &o.matches);
+                                  });
 }
 
 // The pending key results (the previous sub-batch's, or at the end of run() the last one's) into

@@ -93,6 +93,7 @@ struct DeviceCtx {
     sdsp_debug_tempo_map_times last_tm{}; // the last call with a tempo map request (Pipeline::sub_batch)
     sdsp_debug_sections_times last_sc{};  // the last call with a sections request (Pipeline::sections_results)
     sdsp_debug_r128_times last_r128{};    // the last call with an r128 request (Pipeline::r128_join)
+    sdsp_debug_fingerprint_times last_fp{}; // the last call with a fingerprint request (Pipeline::fingerprint_finish)
     DevBuf& buf(const std::string& name) {
         auto& b = bufs[name];
         if (!b) {

@@ -21,7 +21,9 @@ from sdsp_abi import (ERROR_NAMES, FLAG_NAMES, SdspAudioDecodeStats, SdspConfide
                       SdspRequestSet, SdspSilenceRegion, LEVELS_BITS, SdspDebugTempoMapTimes, SdspTempoMap,
                       SdspTempoMapRequest, SdspTempoSegment, TEMPO_MAP_BITS, SdspDebugSectionsOut,
                       SdspDebugSectionsTimes, SdspSection, SdspSections, SdspSectionsRequest, SECTIONS_BITS, SdspRequestSetExt,
-                      SdspDebugR128Times, SdspR128, SdspR128Request, SdspRequestSetExt2, R128_BITS)
+                      SdspDebugR128Times, SdspR128, SdspR128Request, SdspRequestSetExt2, R128_BITS,
+                      SdspDebugFingerprintOut, SdspDebugFingerprintPair, SdspDebugFingerprintTimes, SdspFingerprint,
+                      SdspFingerprintMatch, SdspFingerprintMatches, SdspFingerprintRequest, SdspRequestSetExt3, FP_BITS)
 
 PKG = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LIB_PATH = os.environ.get("SDSP_LIB_PATH") or os.path.join(PKG, "lib", "libstratum_hip.so")  # override: layout/ablation builds
@@ -97,6 +99,12 @@ def _load(path):
         L.sdsp_sections_free.restype = None
         L.sdsp_debug_last_sections_times.argtypes = [C.c_int32, C.POINTER(SdspDebugSectionsTimes)]
         L.sdsp_debug_last_sections_times.restype = C.c_int32
+        L.sdsp_fingerprint_free.argtypes = [C.POINTER(SdspFingerprint)]
+        L.sdsp_fingerprint_free.restype = None
+        L.sdsp_fingerprint_matches_free.argtypes = [C.POINTER(SdspFingerprintMatches)]
+        L.sdsp_fingerprint_matches_free.restype = None
+        L.sdsp_debug_last_fingerprint_times.argtypes = [C.c_int32, C.POINTER(SdspDebugFingerprintTimes)]
+        L.sdsp_debug_last_fingerprint_times.restype = C.c_int32
         L.sdsp_r128_free.argtypes = [C.POINTER(SdspR128)]
         L.sdsp_r128_free.restype = None
         L.sdsp_debug_last_r128_times.argtypes = [C.c_int32, C.POINTER(SdspDebugR128Times)]
@@ -851,9 +859,50 @@ def r128_times(device=0):
     return {k: getattr(t, k) for k, _ in SdspDebugR128Times._fields_}
 
 
+FP_MATCH_FIELDS = ("a", "b", "offset_words", "offset_samples", "bit_errors", "bits_compared", "ber")
+
+
+def fingerprint_request(cell_seconds=0.0, cell_samples=0, max_offset_words=16, min_overlap_words=32, max_ber=0.30,
+                        what=("words", "match")):
+    """An sdsp_fingerprint_request: cells of cell_seconds, or of cell_samples samples (exactly one
+    of the two); `what` a mask of sdsp_fingerprint_what bits, or names out of words, match."""
+    if not isinstance(what, int):
+        mask = 0
+        for name in what:
+            mask |= FP_BITS[name]
+        what = mask
+    return SdspFingerprintRequest(what, cell_seconds, cell_samples, max_offset_words, min_overlap_words, max_ber)
+
+
+def fingerprint_to_dict(f):
+    """One sdsp_fingerprint: its integer fields as int and `words` a uint32 array (empty without
+    the words)."""
+    d = {k: int(getattr(f, k)) for k in ("status", "n_cells", "n_words", "cell_samples", "first_sample", "n_matches")}
+    d["words"] = _records(f.words, d["n_words"] if f.words else 0, C.c_uint32).astype(np.uint32)
+    return d
+
+
+def fingerprint_matches_to_dict(m):
+    """One sdsp_fingerprint_matches: n_compared, n_pairs, n_matches and `matches`, a dict of numpy
+    arrays, one per field (FP_MATCH_FIELDS; ber float32)."""
+    d = {k: int(getattr(m, k)) for k in ("n_compared", "n_pairs", "n_matches")}
+    rec = _records(m.matches, d["n_matches"], SdspFingerprintMatch)
+    d["matches"] = {k: rec[k].copy() for k in FP_MATCH_FIELDS}
+    return d
+
+
+def fingerprint_times(device=0):
+    """sdsp_debug_last_fingerprint_times: the event times of the three fingerprint kernels of the
+    last call with a fingerprint request on `device`."""
+    t = SdspDebugFingerprintTimes()
+    if lib().sdsp_debug_last_fingerprint_times(device, C.byref(t)) != 0:
+        raise RuntimeError("sdsp_debug_last_fingerprint_times failed")
+    return {k: getattr(t, k) for k, _ in SdspDebugFingerprintTimes._fields_}
+
+
 def analyze_batch_device_with(d_ptr, offsets, lens, sample_rate=44100, config=None, device=0, stream=None,
                               stages=STAGES_FULL, overview=None, key_timeline=None, levels=None, request_set=True,
-                              tempo_map=None, sections=None, loudness=None):
+                              tempo_map=None, sections=None, loudness=None, fingerprint=None):
     """sdsp_analyze_batch_device_with: analyze_batch_device(raw=True) with any of the optional
     requests: an SdspOverviewRequest, an SdspKeyTimelineRequest, an SdspLevelsRequest
     (levels_request()), an SdspTempoMapRequest (tempo_map_request()); None leaves a request out.
@@ -862,7 +911,10 @@ def analyze_batch_device_with(d_ptr, offsets, lens, sample_rate=44100, config=No
     a tempo_map_to_dict(); each list [] without its request.  Raises AnalysisError when the call as
     a whole fails (a refused request).  With a sections request (sections_request()) the sections,
     each a sections_to_dict(), are one more element at the end of the tuple, and with a loudness
-    request (loudness_request()) the programme loudness, each an r128_to_dict(), one more after that."""
+    request (loudness_request()) the programme loudness, each an r128_to_dict(), one more after that.
+    With a fingerprint request (fingerprint_request()) one more element at the very end: a dict with
+    `fingerprints`, a fingerprint_to_dict() per track, and `matches`, the call's
+    fingerprint_matches_to_dict()."""
     offs = np.ascontiguousarray(offsets, dtype=np.uint64)
     ln = np.ascontiguousarray(lens, dtype=np.uint64)
     n = ln.size
@@ -875,10 +927,14 @@ def analyze_batch_device_with(d_ptr, offsets, lens, sample_rate=44100, config=No
     cfg = config if config is not None else default_config()
     _schedule_from_env()
     r128s = (SdspR128 * max(n, 1))() if loudness is not None else None
-    ext2 = SdspRequestSetExt2()  # (a call without the later requests passes the older structs' sizes)
+    fps = (SdspFingerprint * max(n, 1))() if fingerprint is not None else None
+    fpm = SdspFingerprintMatches() if fingerprint is not None else None
+    ext3 = SdspRequestSetExt3()  # (a call without the later requests passes the older structs' sizes)
+    ext2 = ext3.base
     ext = ext2.base
     rs = ext.base
-    rs.struct_size = C.sizeof(SdspRequestSetExt2 if loudness is not None else
+    rs.struct_size = C.sizeof(SdspRequestSetExt3 if fingerprint is not None else
+                              SdspRequestSetExt2 if loudness is not None else
                               SdspRequestSetExt if sections is not None else SdspRequestSet)
     if overview is not None:
         rs.ov_req = C.pointer(overview)
@@ -898,6 +954,10 @@ def analyze_batch_device_with(d_ptr, offsets, lens, sample_rate=44100, config=No
     if loudness is not None:
         ext2.r128_req = C.pointer(loudness)
         ext2.r128 = r128s
+    if fingerprint is not None:
+        ext3.fp_req = C.pointer(fingerprint)
+        ext3.fingerprints = fps
+        ext3.fp_matches = C.pointer(fpm)
     u64p = C.POINTER(C.c_uint64)
     st = lib().sdsp_analyze_batch_device_with(C.c_void_p(d_ptr), offs.ctypes.data_as(u64p), ln.ctypes.data_as(u64p), n,
                                               sample_rate, C.byref(cfg), device, C.c_void_p(stream or 0), stages, outs,
@@ -931,6 +991,15 @@ def analyze_batch_device_with(d_ptr, offsets, lens, sample_rate=44100, config=No
         ret += (secs,)
     if loudness is not None:
         ret += (louds,)
+    if fingerprint is not None:
+        prints = []
+        for i in range(n if request_set else 0):
+            prints.append(fingerprint_to_dict(fps[i]))
+            lib().sdsp_fingerprint_free(C.byref(fps[i]))
+        matches = fingerprint_matches_to_dict(fpm) if request_set else None
+        if request_set:
+            lib().sdsp_fingerprint_matches_free(C.byref(fpm))
+        ret += (dict(fingerprints=prints, matches=matches),)
     return ret
 
 
@@ -1555,6 +1624,57 @@ def debug_sections(rows, energies, request, sample_rate=44100, khop=512, hop=512
                         novelty=nov[at:at + k].copy(), boundary=bnd[at:at + k].copy()))
         at += k
     return out
+
+
+def debug_fingerprint(rows, request, sample_rate=44100, khop=512, device=0):
+    """k_fp_cells and k_fp_words over uploaded chroma rows (sdsp_debug_fingerprint).  rows[t]:
+    (F_t, 12) float32, khop samples apart.  Returns per track a dict with n_cells, n_words,
+    m (n_cells, 12) float32 and words (uint32)."""
+    T = len(rows)
+    rs = [np.ascontiguousarray(r, np.float32).reshape(-1, 12) for r in rows]
+    frames = np.array([r.shape[0] for r in rs], np.uint64)
+    allr = np.ascontiguousarray(np.concatenate([r.ravel() for r in rs] + [np.zeros(12, np.float32)]))
+    cs = int(request.cell_samples) or int(np.float32(request.cell_seconds) * np.float32(sample_rate))
+    cells = [int(f) * khop // cs for f in frames] if cs > 0 else [0] * T
+    cap, wcap = sum(cells), sum(max(c - 2, 0) for c in cells)
+    nc, nw = np.zeros(max(T, 1), np.uint64), np.zeros(max(T, 1), np.uint64)
+    m, words = np.zeros(12 * max(cap, 1), np.float32), np.zeros(max(wcap, 1), np.uint32)
+    u64p, u32p = C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)
+    o = SdspDebugFingerprintOut(cap, wcap, nc.ctypes.data_as(u64p), nw.ctypes.data_as(u64p), _fp(m),
+                                words.ctypes.data_as(u32p))
+    f = lib().sdsp_debug_fingerprint
+    f.argtypes = [C.POINTER(C.c_float), u64p, C.c_uint64, C.c_uint32, C.c_uint32, C.POINTER(SdspFingerprintRequest),
+                  C.POINTER(SdspDebugFingerprintOut), C.c_int32]
+    f.restype = C.c_int32
+    st = f(_fp(allr), frames.ctypes.data_as(u64p), T, sample_rate, khop, C.byref(request), C.byref(o), device)
+    if st != 0:
+        raise AnalysisError(st, "debug_fingerprint failed")
+    out, at, wat = [], 0, 0
+    for t in range(T):
+        k, w = int(nc[t]), int(nw[t])
+        out.append(dict(n_cells=k, n_words=w, m=m[12 * at:12 * (at + k)].reshape(k, 12).copy(), words=words[wat:wat + w].copy()))
+        at += k
+        wat += w
+    return out
+
+
+def debug_fingerprint_match(words, request, device=0):
+    """k_fp_match over uploaded word arrays (sdsp_debug_fingerprint_match), every track compared.
+    words[t]: uint32, at least one word.  Returns a record array (T, T) with offset_words, eligible,
+    bit_errors, positions: the pair (a, b), a < b, at [a, b], the other entries zero."""
+    T = len(words)
+    ws = [np.ascontiguousarray(w, np.uint32).ravel() for w in words]
+    nw = np.array([w.size for w in ws], np.uint64)
+    allw = np.ascontiguousarray(np.concatenate(ws))
+    rec = (SdspDebugFingerprintPair * (T * T))()
+    u64p, u32p = C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)
+    f = lib().sdsp_debug_fingerprint_match
+    f.argtypes = [u32p, u64p, C.c_uint64, C.POINTER(SdspFingerprintRequest), C.POINTER(SdspDebugFingerprintPair), C.c_int32]
+    f.restype = C.c_int32
+    st = f(allw.ctypes.data_as(u32p), nw.ctypes.data_as(u64p), T, C.byref(request), rec, device)
+    if st != 0:
+        raise AnalysisError(st, "debug_fingerprint_match failed")
+    return np.frombuffer(bytes(rec), dtype=np.dtype(SdspDebugFingerprintPair)).reshape(T, T).copy()
 
 
 def debug_tempo_map(tracks, what=("segments", "onsets"), sample_rate=44100, config=None, device=0):

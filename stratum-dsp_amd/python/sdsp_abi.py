@@ -657,6 +657,69 @@ class SdspDebugR128Times(C.Structure):
                 ("steps", u64)]
 
 
+FP_WORDS, FP_MATCH = 1, 2
+FP_BITS = {"words": FP_WORDS, "match": FP_MATCH}
+
+
+class SdspFingerprintRequest(C.Structure):
+    """sdsp_fingerprint_request."""
+
+    _fields_ = [("what", u32), ("cell_seconds", f32), ("cell_samples", u64), ("max_offset_words", u32),
+                ("min_overlap_words", u32), ("max_ber", f32)]
+
+
+class SdspFingerprint(C.Structure):
+    """sdsp_fingerprint: one track's fingerprint (the words library-owned)."""
+
+    _fields_ = [("status", C.c_int32), ("n_cells", u64), ("n_words", u64), ("cell_samples", u64), ("first_sample", u64),
+                ("n_matches", u64), ("words", C.POINTER(u32))]
+
+
+class SdspFingerprintMatch(C.Structure):
+    """sdsp_fingerprint_match."""
+
+    _fields_ = [("a", u64), ("b", u64), ("offset_words", C.c_int32), ("offset_samples", C.c_int64), ("bit_errors", u64),
+                ("bits_compared", u64), ("ber", f32)]
+
+
+class SdspFingerprintMatches(C.Structure):
+    """sdsp_fingerprint_matches: a call's match list (library-owned)."""
+
+    _fields_ = [("n_compared", u64), ("n_pairs", u64), ("n_matches", u64), ("matches", C.POINTER(SdspFingerprintMatch))]
+
+
+class SdspRequestSetExt3(C.Structure):
+    """sdsp_request_set_ext3: sdsp_request_set_ext2, then the fingerprint request's fields.  Pass
+    byref(ext3.base.base.base) with its struct_size = sizeof(ext3)."""
+
+    _fields_ = [
+        ("base", SdspRequestSetExt2),
+        ("fp_req", C.POINTER(SdspFingerprintRequest)),
+        ("fingerprints", C.POINTER(SdspFingerprint)),
+        ("fp_matches", C.POINTER(SdspFingerprintMatches)),
+    ]
+
+
+class SdspDebugFingerprintOut(C.Structure):
+    """sdsp_debug_fingerprint_out (include/stratum_hip_debug.h)."""
+
+    _fields_ = [("cell_capacity", u64), ("word_capacity", u64), ("n_cells", C.POINTER(u64)), ("n_words", C.POINTER(u64)),
+                ("m", C.POINTER(f32)), ("words", C.POINTER(u32))]
+
+
+class SdspDebugFingerprintPair(C.Structure):
+    """sdsp_debug_fingerprint_pair (include/stratum_hip_debug.h)."""
+
+    _fields_ = [("offset_words", C.c_int32), ("eligible", u32), ("bit_errors", u32), ("positions", u32)]
+
+
+class SdspDebugFingerprintTimes(C.Structure):
+    """sdsp_debug_fingerprint_times (include/stratum_hip_debug.h)."""
+
+    _fields_ = [("cells_ms", C.c_double), ("words_ms", C.c_double), ("match_ms", C.c_double), ("words", u64),
+                ("compared", u64), ("pairs", u64)]
+
+
 class SdspDebugLevelsTimes(C.Structure):
     """sdsp_debug_levels_times (include/stratum_hip_debug.h)."""
 
